@@ -328,12 +328,21 @@ bool attn_bwd_mfma_supported(int dtype, int N, int S, int C);
 int launch_attn_bwd_mfma(int dtype, const void* qkv, const void* O, const void* dO, const float* lse, int N, int S, int C, void* P, void* dS,
                          void* dqkv, hipStream_t s);
 
-int launch_time_sinusoid(const int64_t* t, int nt, const float* freqs, int half, float* out, hipStream_t s);
+// Which form of the forward last wrote a workspace, kept ON THE DEVICE: the forward's first launch (the sinusoid) stores one of the two
+// marks into a word of the workspace, and the backward's first launch (dY into NHWC) reads it.  A replayed graph of either form passes
+// through no entry point, so the host-side guard (dmme_plan::nograd_ws) cannot see it; this word can.  A backward that finds the no-grad
+// mark fills dY with NaN (every gradient it produces is NaN) and raises the plan's host-visible status word to kErrNogradBackward.
+constexpr unsigned kFwdMarkKeep = 0x4B454550u, kFwdMarkNograd = 0x4E4F4752u;
+constexpr unsigned kErrNogradBackward = 0x80000000u;  // (the level engine's values are 1 + run index)
+int launch_time_sinusoid(const int64_t* t, int nt, const float* freqs, int half, float* out, hipStream_t s, unsigned* mark = nullptr,
+                         unsigned mark_val = 0);
 // out[nt][Nout] = act(in[nt][K] . W[Nout][K]^T + b); in/out fp32, W in dtype
 int launch_linear_wave(int dtype, const float* in, int nt, int K, const void* W, const float* bias, int Nout,
                        int out_silu, float* out, hipStream_t s);
 
-int launch_nchw_to_nhwc(int dtype, const float* src, int N, int C, int HW, void* dst, hipStream_t s);
+// mark / err (nullable): the backward's dY conversion checks the forward's mark (kFwdMarkNograd: NaN out, err = kErrNogradBackward)
+int launch_nchw_to_nhwc(int dtype, const float* src, int N, int C, int HW, void* dst, hipStream_t s, const unsigned* mark = nullptr,
+                        unsigned* err = nullptr);
 int launch_nhwc_to_nchw(int dtype, const void* src, int N, int C, int HW, float* dst, hipStream_t s);
 int launch_pack_weight(int dtype, const float* src, int Cout, int Cin, int taps, void* dst, hipStream_t s);
 // fp32 -> 16-bit copy of a tensor (numel % 8 == 0): where a conv of a mixed plan's 16-bit levels reads a tensor of its fp32 level

@@ -525,8 +525,9 @@ int launch_gn_modulate(float* scale, float* shift, const float* t_shift, const f
 
 // ------------------------------------------------------------------ time embedding pieces
 // SinusoidalPositionEmbeddings.forward (models/ddpm.py:347-348): [sin(t f), cos(t f)]
-__global__ void time_sinusoid_kernel(const int64_t* t, int nt, const float* freqs, int half, float* out) {
+__global__ void time_sinusoid_kernel(const int64_t* t, int nt, const float* freqs, int half, float* out, unsigned* mark, unsigned mark_val) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && mark) *mark = mark_val;  // the forward form's mark (common.h: kFwdMarkKeep / kFwdMarkNograd)
     if (i >= nt * half) return;
     const int r = i / half, k = i % half;
     const float arg = (float)t[r] * freqs[k];
@@ -534,9 +535,9 @@ __global__ void time_sinusoid_kernel(const int64_t* t, int nt, const float* freq
     out[(int64_t)r * 2 * half + half + k] = cosf(arg);
 }
 
-int launch_time_sinusoid(const int64_t* t, int nt, const float* freqs, int half, float* out, hipStream_t s) {
+int launch_time_sinusoid(const int64_t* t, int nt, const float* freqs, int half, float* out, hipStream_t s, unsigned* mark, unsigned mark_val) {
     const int total = nt * half;
-    hipLaunchKernelGGL(time_sinusoid_kernel, dim3((total + 255) / 256), dim3(256), 0, s, t, nt, freqs, half, out);
+    hipLaunchKernelGGL(time_sinusoid_kernel, dim3((total + 255) / 256), dim3(256), 0, s, t, nt, freqs, half, out, mark, mark_val);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -582,12 +583,15 @@ int launch_linear_wave(int dtype, const float* in, int nt, int K, const void* W,
 
 // ------------------------------------------------------------------ layout converters
 template <typename T>
-__global__ void nchw_to_nhwc_kernel(const float* src, int C, int HW, T* dst, int64_t total) {
+__global__ void nchw_to_nhwc_kernel(const float* src, int C, int HW, T* dst, int64_t total, const unsigned* mark, unsigned* err) {
+    const bool nograd = mark && *mark == kFwdMarkNograd;  // (the backward's dY: common.h, kFwdMarkNograd)
+    if (nograd && blockIdx.x == 0 && threadIdx.x == 0 && err)
+        __hip_atomic_store(err, kErrNogradBackward, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
         const int64_t p = i / C;  // n*HW + hw
         const int64_t n = p / HW, hw = p % HW;
-        dst[i] = from_f<T>(src[(n * C + c) * HW + hw]);
+        dst[i] = from_f<T>(nograd ? __builtin_nanf("") : src[(n * C + c) * HW + hw]);
     }
 }
 template <typename T>
@@ -603,14 +607,14 @@ static inline unsigned grid_for(int64_t total) {
     int64_t b = (total + 255) / 256;
     return (unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
 }
-int launch_nchw_to_nhwc(int dtype, const float* src, int N, int C, int HW, void* dst, hipStream_t s) {
+int launch_nchw_to_nhwc(int dtype, const float* src, int N, int C, int HW, void* dst, hipStream_t s, const unsigned* mark, unsigned* err) {
     const int64_t total = (int64_t)N * C * HW;
     if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, s, src, C, HW, (bf16*)dst, total);
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, s, src, C, HW, (bf16*)dst, total, mark, err);
     else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, s, src, C, HW, (f16*)dst, total);
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, s, src, C, HW, (f16*)dst, total, mark, err);
     else
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, src, C, HW, (float*)dst, total);
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, src, C, HW, (float*)dst, total, mark, err);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

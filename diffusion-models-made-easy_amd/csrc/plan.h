@@ -137,6 +137,7 @@ struct dmme_plan {
     std::unordered_map<std::string, int> named;  // module name -> tensor id
     int64_t ref_numel = 0, packed_bytes = 0, ws_bytes = 0, dropmask_numel = 0;
     int64_t ws_tsin = 0, ws_th1 = 0, ws_temb = 0, ws_tproj = 0, ws_gnpart = 0;
+    int64_t ws_mark = 0;  // the forward form's mark (common.h: kFwdMarkKeep / kFwdMarkNograd)
     int64_t ws_tz1 = -1, ws_tz2 = -1;  // pre-activations of the two time-MLP layers (written at training batch; the backward's SiLU')
     int64_t ws_splitk = 0, splitk_floats = 0;  // split-K partial sums of the small-map convolutions (forward and data gradient)
     int tproj_cols = 0;
@@ -193,8 +194,9 @@ struct dmme_plan {
     std::vector<LvlRun> lvl_runs;     // level-engine launches (small maps)
     // every workgroup of an engine launch must be resident at once: grids are sized by what the device holds (assign_levels)
     int lvl_max_wg = LVL_MAX_WG;
-    // host-visible status word of the engine's bounded hand-off waits (pinned, device-mapped; null: no engine run in this plan):
-    // non-zero = 1 + index of a run in which a wait timed out, i.e. the outputs since are invalid (lvl_check)
+    // host-visible status word (pinned, device-mapped; null: plan without a device): non-zero = 1 + index of an engine run in which a
+    // bounded hand-off wait timed out, or kErrNogradBackward (a backward found the no-grad form's mark): the outputs since are invalid
+    // (lvl_check)
     unsigned* err_host = nullptr;
     // the workspace the last forward wrote WITHOUT the tensors only a backward pass reads (dmme_unet_forward_nograd, dmme_chain_step):
     // dmme_unet_backward refuses it instead of differentiating stale activations (null: the last forward kept everything)

@@ -259,6 +259,7 @@ int build_plan(dmme_plan* P) {
         P->tensors.push_back(t);
         return (int)P->tensors.size() - 1;
     };
+    P->ws_mark = ws_alloc(16);
     P->ws_tsin = ws_alloc((int64_t)B * c.pos_dim * 4);
     P->ws_th1 = ws_alloc((int64_t)B * c.emb_dim * 4);
     P->ws_temb = ws_alloc((int64_t)B * c.emb_dim * 4);
@@ -1134,7 +1135,8 @@ int run_op(const dmme_plan* P, const Op& o, const char* pk, const float* x, cons
     switch (o.kind) {
         case OP_SINUS:
             return launch_time_sinusoid(t, nt, (const float*)(pk + P->params[P->freqs_param].packed_off),
-                                        P->cfg.pos_dim / 2, (float*)(ws + P->ws_tsin), s);
+                                        P->cfg.pos_dim / 2, (float*)(ws + P->ws_tsin), s, (unsigned*)(ws + P->ws_mark),
+                                        keep_ctx ? kFwdMarkKeep : kFwdMarkNograd);
         case OP_LINEAR: {
             const char* w = o.lin_w >= 0 ? pk + P->params[o.lin_w].packed_off : pk + P->tproj_w_off;
             const float* b = (const float*)(o.lin_b >= 0 ? pk + P->params[o.lin_b].packed_off : pk + P->tproj_b_off);
@@ -1282,7 +1284,7 @@ void op_account(const dmme_plan* P, const Op& o, char* label, int cap, double* f
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 105; }  // 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 106; }  // 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1597,10 +1599,9 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
             if (e == hipSuccess) e = hipMalloc((void**)&G->jobs_dev, G->jobs.size() * sizeof(WgJob));
             if (e == hipSuccess) e = hipMemcpy(G->jobs_dev, G->jobs.data(), G->jobs.size() * sizeof(WgJob), hipMemcpyHostToDevice);
         }
-        if (!P->lvl_runs.empty()) {
-            if (e == hipSuccess) e = hipHostMalloc((void**)&P->err_host, 64, hipHostMallocMapped | hipHostMallocCoherent);
-            if (e == hipSuccess) memset(P->err_host, 0, 64);
-        }
+        // (every device plan: the backward reports a no-grad forward's workspace through this word too)
+        if (e == hipSuccess) e = hipHostMalloc((void**)&P->err_host, 64, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) memset(P->err_host, 0, 64);
         for (LvlRun& R : P->lvl_runs) {
             const size_t words = 16 + R.ops.size() * 2 * (size_t)R.NG * LVL_NS;
             if (e == hipSuccess) e = hipMalloc((void**)&R.ops_dev, R.ops.size() * sizeof(LvlOp));
@@ -1819,6 +1820,27 @@ DMME_API int dmme_unet_debug_read(const dmme_plan* plan, const void* workspace, 
                  (long long)numel_cap);
     if (numel_out) *numel_out = n;
     return launch_nhwc_to_nchw(t.f32 ? DMME_F32 : plan->dtype, (const char*)workspace + t.off, plan->B, t.C, t.H * t.W, dst, s);
+}
+
+// gradient buffers of the reverse walk (plan_bwd.hip): every forward tensor has its own (gt_off); the aliases the plan sets up share a
+// buffer only between tensors whose gradients are equal (a block's 1x1 residual output and the block output), so after
+// dmme_unet_backward the buffer of every named tensor holds its full gradient.  The time embedding's is the exception: the MLP backward
+// turns d(temb) into d(pre-activation) in place.
+DMME_API int dmme_unet_debug_read_grad(const dmme_plan* plan, const void* bwd_workspace, const char* name, float* dst,
+                                       int64_t numel_cap, int64_t* numel_out, void* stream) {
+    DMME_REQUIRE(plan && bwd_workspace && name && dst, DMME_ERR_INVALID, "debug_read_grad: null argument");
+    DMME_REQUIRE(strcmp(name, "condition") != 0, DMME_ERR_INVALID,
+                 "debug_read_grad: the gradient of 'condition' is not kept (the time-MLP backward overwrites it in place with the gradient "
+                 "of the pre-activation); compare the condition.* parameter gradients instead");
+    auto it = plan->named.find(name);
+    DMME_REQUIRE(it != plan->named.end(), DMME_ERR_INVALID, "debug_read_grad: unknown module '%s'", name);
+    const Tensor& t = plan->tensors[it->second];
+    const int64_t n = (int64_t)plan->B * t.C * t.H * t.W;
+    DMME_REQUIRE(n <= numel_cap, DMME_ERR_INVALID, "debug_read_grad: destination too small (%lld > %lld)", (long long)n,
+                 (long long)numel_cap);
+    if (numel_out) *numel_out = n;
+    return launch_nhwc_to_nchw(plan->dtype, (const char*)bwd_workspace + plan->gt_off[it->second], plan->B, t.C, t.H * t.W, dst,
+                               (hipStream_t)stream);
 }
 
 DMME_API int dmme_dropout_masks(const dmme_plan* plan, uint64_t seed, uint64_t offset, float* masks, void* stream) {

@@ -168,7 +168,8 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
     float* wimage = (float*)(bws + P->bws_wimage);
     float* dtproj = (float*)(bws + P->bws_dtproj);
     char* tmp = bws + P->bws_tmp;
-    int rc = launch_nchw_to_nhwc(dt, d_y, B, P->out_channels, P->H * P->W, bws + P->bws_dy, s);
+    // (the first launch: it checks the device-side mark of the forward form, which a replayed no-grad graph sets without the host seeing it)
+    int rc = launch_nchw_to_nhwc(dt, d_y, B, P->out_channels, P->H * P->W, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host);
     if (rc != DMME_OK) return rc;
     const bool buckets = ready != nullptr && !P->gb.empty();  // bucketed mode: deferred work flushed per gradient bucket
     const int emb = P->cfg.emb_dim, pos = P->cfg.pos_dim, tc = P->tproj_cols;

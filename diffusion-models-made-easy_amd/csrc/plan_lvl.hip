@@ -447,6 +447,12 @@ int lvl_check(const dmme_plan* P, const char* where, hipStream_t stream, bool ha
         __atomic_store_n(P->err_host, 0u, __ATOMIC_RELEASE);
         if (sw) (void)hipSetDevice(cur);
     }
+    if (v == kErrNogradBackward) {
+        set_error("%s: a dmme_unet_backward ran on a workspace whose last forward was the no-grad form (a replayed graph of "
+                  "dmme_unet_forward_nograd / dmme_chain_step, which leave out the tensors only a backward pass reads): that backward's "
+                  "gradients are NaN.  Run dmme_unet_forward before dmme_unet_backward.", where);
+        return DMME_ERR_INVALID;
+    }
     const int ri = (int)v - 1;
     const LvlRun* R = ri >= 0 && ri < (int)P->lvl_runs.size() ? &P->lvl_runs[ri] : nullptr;
     set_error("%s: a hand-off wait of the level engine timed out (run %d, %dx%d maps, %d workgroups that must all be resident at once; the device "

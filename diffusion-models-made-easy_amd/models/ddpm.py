@@ -530,3 +530,16 @@ class UNet(nn.Module):
         n = C.c_int64()
         _lib.check(plan.lib.dmme_unet_debug_read(plan.h, _lib.ptr(plan.workspace), name.encode(), _lib.ptr(buf), cap, C.byref(n), _lib.stream_ptr()), "dmme_unet_debug_read")
         return buf[: n.value].clone()
+
+    def debug_gradient(self, name: str) -> Tensor:
+        """fp32 NCHW copy of d loss / d(output of module `name`) from the last backward of the last forward's plan (parity tests;
+        include/dmme_hip.h: dmme_unet_debug_read_grad)."""
+        plan = self._last_plan
+        if getattr(plan, "bws", None) is None:
+            raise RuntimeError("debug_gradient: no backward pass has run on this plan")
+        cap = plan.B * 4096 * max(plan.H * plan.W, 1)
+        buf = torch.empty(cap, dtype=torch.float32, device=plan.bws.device)
+        n = C.c_int64()
+        _lib.check(plan.lib.dmme_unet_debug_read_grad(plan.h, _lib.ptr(plan.bws), name.encode(), _lib.ptr(buf), cap, C.byref(n), _lib.stream_ptr()),
+                   "dmme_unet_debug_read_grad")
+        return buf[: n.value].clone()

@@ -131,7 +131,10 @@ DMME_API int dmme_unet_forward(const dmme_plan* plan, const void* packed, const 
  * diffusion_models/ddpm.py:113-133): tensors that only the backward pass reads - the context of an attention block whose proj
  * conv runs inside the attention launch (models/ddpm.py:66-75), raw conv outputs of the level engine that only their norm's
  * pre-activated copy stands for - are not written.  Same arguments, same result y.  dmme_unet_backward on that workspace fails
- * with DMME_ERR_INVALID until a dmme_unet_forward has filled it again.
+ * with DMME_ERR_INVALID until a dmme_unet_forward has filled it again.  A REPLAYED graph of this form passes through no entry point:
+ * the forward's first launch leaves a mark in the workspace, and a dmme_unet_backward enqueued after such a replay (with no
+ * dmme_unet_forward in between) finds it on the device, writes NaN into every gradient it produces and raises the plan's status word,
+ * so that dmme_unet_plan_check (and the next entry point) fails with DMME_ERR_INVALID naming this form.
  * dmme_chain_step and dmme_unet_forward_profiled run this form. */
 DMME_API int dmme_unet_forward_nograd(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len,
                       float* y, void* workspace, const float* drop_masks, void* stream);
@@ -253,6 +256,12 @@ DMME_API int dmme_grad_unpack_bf16(const void* src_bf16, int64_t numel, float* g
  * "input_conv", "condition") out of the workspace as fp32 NCHW for parity tests.
  * numel_cap guards the destination size. */
 DMME_API int dmme_unet_debug_read(const dmme_plan* plan, const void* workspace, const char* name, float* dst,
+                         int64_t numel_cap, int64_t* numel_out, void* stream);
+/* The same for gradients: after dmme_unet_backward, copy dL/d(output of module `name`) out of the backward workspace
+ * (bwd_workspace) as fp32 NCHW.  Every name dmme_unet_debug_read takes holds its full gradient then (every consumer's contribution
+ * summed: the next block's, the residual branch's, the concat half of the up block that reads it as a skip).  "condition" fails
+ * with DMME_ERR_INVALID: the time-MLP backward overwrites d(temb) in place. */
+DMME_API int dmme_unet_debug_read_grad(const dmme_plan* plan, const void* bwd_workspace, const char* name, float* dst,
                          int64_t numel_cap, int64_t* numel_out, void* stream);
 
 /* Dropout2d multipliers from the library's own Philox stream (train mode without

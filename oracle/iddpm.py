@@ -134,7 +134,8 @@ def make_state_dict(cfg: IUNetConfig, seed: int, gn_jitter: bool = True) -> Dict
 # --------------------------------------------------------------------------- forward
 
 
-def multi_head_attention(sd: Dict[str, Tensor], p: str, x: Tensor, groups: int, heads: int) -> Tensor:
+def multi_head_attention(sd: Dict[str, Tensor], p: str, x: Tensor, groups: int, heads: int,
+                         q: Optional[Callable[[Tensor], Tensor]] = None) -> Tensor:
     """MultiHeadAttention.forward / forward_attention (models/iddpm.py:35-59), as shipped:
 
     * heads are split with "b (head c) h w -> (b head) (h w) c" (:38): head h owns the 3C/heads
@@ -142,30 +143,35 @@ def multi_head_attention(sd: Dict[str, Tensor], p: str, x: Tensor, groups: int, 
     * K is scaled by dim**-0.5 with dim = the full channel count, not the head width (:32,:40);
     * the merge reads the batch axis as "(head b)" (:44-46) although it was built as "(b head)":
       row i = b*heads + head of the attention output lands at batch i % B, head i // B.  For B > 1
-      this mixes samples; restated exactly."""
+      this mixes samples; restated exactly.
+    ``q``: rounding points of a 16-bit implementation, as in oracle.unet.attention_block."""
+    rq = q or U._ident
     b, c, hh, ww = x.shape
     d = c // heads
-    h = F.group_norm(x, groups, sd[p + ".norm.weight"], sd[p + ".norm.bias"], eps=1e-5)
-    qkv = F.conv2d(h, sd[p + ".qkv_proj.weight"], sd[p + ".qkv_proj.bias"])  # b, 3c, h, w
+    h = rq(F.group_norm(x, groups, sd[p + ".norm.weight"], sd[p + ".norm.bias"], eps=1e-5))
+    qkv = rq(F.conv2d(h, sd[p + ".qkv_proj.weight"], sd[p + ".qkv_proj.bias"]))  # b, 3c, h, w
     qkv = qkv.reshape(b, heads, 3 * d, hh * ww).permute(0, 1, 3, 2).reshape(b * heads, hh * ww, 3 * d)
     q, k, v = qkv[:, :, :d], qkv[:, :, d : 2 * d], qkv[:, :, 2 * d :]
     k = k.transpose(1, 2) * (c**-0.5)
     w = torch.softmax(torch.bmm(q, k), dim=2)
     o = torch.bmm(w, v)  # (b*heads, s, d), row index = b*heads + head
     o = o.reshape(heads, b, hh * ww, d)  # ... re-read as (head', b')
-    o = o.permute(1, 0, 3, 2).reshape(b, c, hh, ww)
+    o = rq(o.permute(1, 0, 3, 2).reshape(b, c, hh, ww))
     o = F.conv2d(o, sd[p + ".proj.weight"], sd[p + ".proj.bias"])
     return o + x
 
 
-def res_block(sd: Dict[str, Tensor], cfg: IUNetConfig, n: U.Node, x: Tensor, temb: Tensor, drop_mask: Optional[Tensor] = None) -> Tensor:
+def res_block(sd: Dict[str, Tensor], cfg: IUNetConfig, n: U.Node, x: Tensor, temb: Tensor, drop_mask: Optional[Tensor] = None,
+              q: Optional[Callable[[Tensor], Tensor]] = None) -> Tensor:
     """iddpm.ResBlock.forward (models/iddpm.py:106-122): scale-shift conditioning.  The time
     projection has 2*c_out outputs chunked as (shift, scale) (:117); h = GN(conv1(x)) * (scale+1) + shift,
-    then SiLU -> Dropout2d -> conv (:94,:119)."""
+    then SiLU -> Dropout2d -> conv (:94,:119).  ``q``: rounding points of a 16-bit implementation, as in
+    oracle.unet.res_block."""
+    rq = q or U._ident
     p = n.prefix
     g = cfg.num_groups
-    h = F.silu(F.group_norm(x, g, sd[p + ".conv1.0.weight"], sd[p + ".conv1.0.bias"], eps=1e-5))
-    h = F.conv2d(h, sd[p + ".conv1.2.weight"], sd[p + ".conv1.2.bias"], padding=1)
+    h = rq(F.silu(F.group_norm(x, g, sd[p + ".conv1.0.weight"], sd[p + ".conv1.0.bias"], eps=1e-5)))
+    h = rq(F.conv2d(h, sd[p + ".conv1.2.weight"], sd[p + ".conv1.2.bias"], padding=1))
     cond = F.linear(temb, sd[p + ".condition.0.weight"], sd[p + ".condition.0.bias"])[:, :, None, None]
     shift, scale = cond.chunk(2, dim=1)
     h = F.group_norm(h, g, sd[p + ".norm.weight"], sd[p + ".norm.bias"], eps=1e-5) * (scale + 1) + shift
@@ -173,13 +179,13 @@ def res_block(sd: Dict[str, Tensor], cfg: IUNetConfig, n: U.Node, x: Tensor, tem
     if drop_mask is not None:
         h = h * drop_mask[:, :, None, None]
     ck = f"{p}.conv2.{_conv2_index(cfg)}"
-    h = F.conv2d(h, sd[ck + ".weight"], sd[ck + ".bias"], padding=1)
+    h = F.conv2d(rq(h), sd[ck + ".weight"], sd[ck + ".bias"], padding=1)
     if n.c_in != n.c_out:
         h = h + F.conv2d(x, sd[p + ".residual.weight"], sd[p + ".residual.bias"])
     else:
         h = h + x
     if n.attn:
-        h = multi_head_attention(sd, p + ".attention", h, g, cfg.num_heads)
+        h = multi_head_attention(sd, p + ".attention", rq(h), g, cfg.num_heads, q)
     return h
 
 

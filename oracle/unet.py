@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -213,48 +213,65 @@ def _gn(sd, p, x, groups):
     return F.group_norm(x, groups, sd[p + ".weight"], sd[p + ".bias"], eps=1e-5)
 
 
-def attention_block(sd: Dict[str, Tensor], p: str, x: Tensor, groups: int) -> Tensor:
+def _ident(t: Tensor) -> Tensor:
+    return t
+
+
+def attention_block(sd: Dict[str, Tensor], p: str, x: Tensor, groups: int, q: Optional[Callable[[Tensor], Tensor]] = None) -> Tensor:
     """Attention.forward / forward_attention (models/ddpm.py:54-75).
 
     Single head over H*W tokens; q,k,v are the three channel thirds of the 1x1 qkv
     conv; K is scaled by dim**-0.5 *before* the product (:50,:58).
+    ``q`` (default: identity) is applied where a 16-bit implementation rounds: the
+    normalised input of the qkv conv, the qkv tensor and the context in front of proj.
     """
+    rq = q or _ident
     b, c, hh, ww = x.shape
-    h = _gn(sd, p + ".norm", x, groups)
-    qkv = F.conv2d(h, sd[p + ".qkv_proj.weight"], sd[p + ".qkv_proj.bias"])
+    h = rq(_gn(sd, p + ".norm", x, groups))
+    qkv = rq(F.conv2d(h, sd[p + ".qkv_proj.weight"], sd[p + ".qkv_proj.bias"]))
     qkv = qkv.reshape(b, 3 * c, hh * ww).transpose(1, 2)  # b, s, 3c
     q, k, v = qkv[:, :, :c], qkv[:, :, c : 2 * c], qkv[:, :, 2 * c :]
     k = k.transpose(1, 2) * (c**-0.5)
     w = torch.softmax(torch.bmm(q, k), dim=2)
-    o = torch.bmm(w, v).transpose(1, 2).reshape(b, c, hh, ww)
+    o = rq(torch.bmm(w, v).transpose(1, 2).reshape(b, c, hh, ww))
     o = F.conv2d(o, sd[p + ".proj.weight"], sd[p + ".proj.bias"])
     return o + x
 
 
 def res_block(
-    sd: Dict[str, Tensor], cfg: UNetConfig, n: Node, x: Tensor, temb: Tensor, drop_mask: Optional[Tensor] = None
+    sd: Dict[str, Tensor],
+    cfg: UNetConfig,
+    n: Node,
+    x: Tensor,
+    temb: Tensor,
+    drop_mask: Optional[Tensor] = None,
+    q: Optional[Callable[[Tensor], Tensor]] = None,
 ) -> Tensor:
     """ResBlock.forward (models/ddpm.py:118-133).
 
     ``drop_mask`` (B, c_out) holds the Dropout2d multipliers (0 or 1/(1-p)) for the
-    conv2 branch (:29, :106); None means eval mode.
+    conv2 branch (:29, :106); None means eval mode.  ``q`` (default: identity) is
+    applied where a 16-bit implementation rounds a tensor: the activated input of each
+    conv, the conv1 output (time row included) and, in front of attention, the block's
+    own output.
     """
+    q = q or _ident
     p = n.prefix
     g = cfg.num_groups
-    h = F.silu(_gn(sd, p + ".conv1.0", x, g))
+    h = q(F.silu(_gn(sd, p + ".conv1.0", x, g)))
     h = F.conv2d(h, sd[p + ".conv1.2.weight"], sd[p + ".conv1.2.bias"], padding=1)
-    h = h + F.linear(temb, sd[p + ".condition.0.weight"], sd[p + ".condition.0.bias"])[:, :, None, None]
+    h = q(h + F.linear(temb, sd[p + ".condition.0.weight"], sd[p + ".condition.0.bias"])[:, :, None, None])
     h2 = F.silu(_gn(sd, p + ".conv2.0", h, g))
     if drop_mask is not None:
         h2 = h2 * drop_mask[:, :, None, None]
     ck = f"{p}.conv2.{_conv2_index(cfg)}"
-    h2 = F.conv2d(h2, sd[ck + ".weight"], sd[ck + ".bias"], padding=1)
+    h2 = F.conv2d(q(h2), sd[ck + ".weight"], sd[ck + ".bias"], padding=1)
     if n.c_in != n.c_out:
         h2 = h2 + F.conv2d(x, sd[p + ".residual.weight"], sd[p + ".residual.bias"])
     else:
         h2 = h2 + x
     if n.attn:
-        h2 = attention_block(sd, p + ".attention", h2, g)
+        h2 = attention_block(sd, p + ".attention", q(h2), g, q)
     return h2
 
 

@@ -45,6 +45,25 @@ def pack_w(w_oihw, dt):
     return out
 
 
+def bwd_summary(net, B, H):
+    """dmme_unet_plan_bwd_summary of the net's (B, H, H) plan as a dict: which backward kernel families the plan runs, and how often"""
+    plan = net._plan_for(B, H, H, torch.device("cuda", 0))
+    buf = C.create_string_buffer(4096)
+    _lib.check(_lib.lib().dmme_unet_plan_bwd_summary(plan.h, buf, 4096))
+    return dict(kv.split("=") for kv in buf.value.decode().split())
+
+
+def fwd_labels(net, B, H):
+    """the kernel label of every forward op of the net's (B, H, H) plan"""
+    plan = net._plan_for(B, H, H, torch.device("cuda", 0))
+    lib, buf, f, b = _lib.lib(), C.create_string_buffer(128), C.c_double(), C.c_double()
+    out = []
+    for i in range(lib.dmme_unet_plan_num_ops(plan.h)):
+        _lib.check(lib.dmme_unet_plan_op_info(plan.h, i, buf, 128, C.byref(f), C.byref(b)))
+        out.append(buf.value.decode())
+    return out
+
+
 def conv2d(dt, x1, w, b, x2=None, scale=None, shift=None, dmask=None, tproj=None, res=None, stride=1, upsample=False,
            pro_silu=False, out_silu=False, force_generic=False, out_nchw=False):
     """x1/x2/res: fp32 NCHW cuda tensors; w: (Cout, Cin, k, k); returns fp32 NCHW (out_nchw: written that way by the kernel itself,

@@ -197,3 +197,71 @@ def test_backward_refuses_the_workspace_of_a_no_grad_forward():
     net(x, t).float().pow(2).mean().backward()  # a forward with autograd fills the workspace again
     torch.cuda.synchronize()
     assert float(net.flat_grad().float().abs().sum()) > 0
+
+
+def test_backward_after_a_replayed_no_grad_graph_does_not_return_other_gradients():
+    """C-ABI level, one stream: dmme_unet_forward (keep) -> REPLAY of a captured dmme_unet_forward_nograd graph -> dmme_unet_backward.
+    A replay passes through no entry point, so only the device can tell that the workspace's last forward left out the fused
+    blocks' context and the engine's raw conv outputs.  The backward must either fail naming the no-grad form or give the gradients
+    of a fresh dmme_unet_forward + backward at the replayed input; it must not silently differentiate the mixed workspace."""
+    import dmme_amd
+    from dmme_amd import _lib
+    from tests.gpu_util import fwd_labels
+
+    torch.manual_seed(0)
+    net = dmme_amd.UNet(precision="bf16").cuda().train()
+    B = 128
+    x_keep = torch.randn(B, 3, 32, 32, device="cuda")
+    x_graph = torch.randn(B, 3, 32, 32, device="cuda")  # another input: its context differs from the one the keep forward left behind
+    t = (torch.arange(B, device="cuda") * 7 % 1000).to(torch.int64)
+    net(x_keep, t).float().pow(2).mean().backward()  # plan, backward workspace, packed backward weights, drawn masks
+    plan = net._last_plan
+    lib = plan.lib
+    labels = fwd_labels(net, B, 32)
+    assert any(l.startswith("attn_full_kernel") and l.endswith(",proj>") for l in labels), labels  # the fused attention block (its context is what the no-grad form skips)
+    packed = net._packed_for(plan)
+    y = torch.empty(B, 3, 32, 32, device="cuda")
+    d = torch.randn(B, 3, 32, 32, device="cuda")
+    g = net.flat_grad()
+
+    def fwd(fn, x):
+        return fn(plan.h, _lib.ptr(packed), _lib.ptr(x), _lib.ptr(t), B, _lib.ptr(y), _lib.ptr(plan.workspace), _lib.ptr(plan.masks), _lib.stream_ptr())
+
+    def bwd(x):
+        g.zero_()
+        return lib.dmme_unet_backward(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(x), _lib.ptr(t), B, _lib.ptr(d), _lib.ptr(plan.workspace),
+                                      _lib.ptr(plan.bws), _lib.ptr(plan.masks), _lib.ptr(g), None, _lib.stream_ptr())
+
+    # the gradients a fresh forward + backward at x_graph give (twice: the run-to-run spread of the atomics' order)
+    refs = []
+    for _ in range(2):
+        _lib.check(fwd(lib.dmme_unet_forward, x_graph))
+        _lib.check(bwd(x_graph))
+        torch.cuda.synchronize()
+        refs.append(g.clone())
+    spread = float((refs[0] - refs[1]).norm() / refs[0].norm())
+    # capture the no-grad forward at x_graph
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        _lib.check(fwd(lib.dmme_unet_forward_nograd, x_graph))
+    torch.cuda.synchronize()
+    _lib.check(fwd(lib.dmme_unet_forward, x_keep))  # keep: the host-side guard is clear again
+    graph.replay()
+    rc = bwd(x_graph)
+    torch.cuda.synchronize()
+    rc_check = lib.dmme_unet_plan_check(plan.h) if rc == 0 else rc
+    msg = lib.dmme_last_error()
+    rel = float((g - refs[0]).norm() / refs[0].norm())
+    print(f"backward after the replay: rc {rc}, plan_check {rc_check}, gradient vs fresh {rel:.3e} (two fresh runs differ by {spread:.3e})")
+    if rc == 0 and rc_check == 0:
+        assert rel <= max(4 * spread, 1e-3), f"silently other gradients: {rel:.3e} from a fresh forward + backward (spread {spread:.3e})"
+    else:
+        assert b"dmme_unet_forward_nograd" in msg, msg
+        if rc == 0:  # failed on the device: no gradient of that backward is usable
+            assert not bool(torch.isfinite(torch.cat([p.grad.reshape(-1) for p in net.parameters()])).any())
+    # the workspace recovers with the next dmme_unet_forward
+    _lib.check(fwd(lib.dmme_unet_forward, x_graph))
+    _lib.check(bwd(x_graph))
+    torch.cuda.synchronize()
+    _lib.check(lib.dmme_unet_plan_check(plan.h))
+    assert float((g - refs[0]).norm() / refs[0].norm()) <= max(4 * spread, 1e-3)

@@ -4,8 +4,6 @@ grouped column sums.  The mean-loss gradient is linear in the batch mean, so a b
 timesteps, noise and Dropout2d masks per copy) has exactly the gradient of the 2-image batch, which torch autograd of the fp32
 CPU oracle provides in seconds.  Reference: DDPM.training_step, src/dmme/diffusion_models/ddpm.py:53-81."""
 
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -13,6 +11,8 @@ import torch
 from oracle import diffusion as D
 from oracle import synth
 from oracle import unet as O
+from tests.gpu_util import bwd_summary as _bwd_summary
+from tests.gpu_util import fwd_labels as _fwd_labels
 
 pytestmark = pytest.mark.gpu
 
@@ -63,27 +63,6 @@ def _class_errors(got, want, classes):
         if rel > worst.get(c, (0.0, ""))[0]:
             worst[c] = (rel, "<pooled small tensors>")
     return worst
-
-
-def _bwd_summary(net, B, H):
-    from dmme_amd import _lib
-
-    plan = net._plan_for(B, H, H, torch.device("cuda", 0))
-    buf = C.create_string_buffer(4096)
-    _lib.check(_lib.lib().dmme_unet_plan_bwd_summary(plan.h, buf, 4096))
-    return dict(kv.split("=") for kv in buf.value.decode().split())
-
-
-def _fwd_labels(net, B, H):
-    from dmme_amd import _lib
-
-    plan = net._plan_for(B, H, H, torch.device("cuda", 0))
-    lib, buf, f, b = _lib.lib(), C.create_string_buffer(128), C.c_double(), C.c_double()
-    out = []
-    for i in range(lib.dmme_unet_plan_num_ops(plan.h)):
-        _lib.check(lib.dmme_unet_plan_op_info(plan.h, i, buf, 128, C.byref(f), C.byref(b)))
-        out.append(buf.value.decode())
-    return out
 
 
 def test_ddpm_batch128_bf16_train_gradients_vs_fp32_oracle():
