@@ -264,14 +264,29 @@ DMME_API int dmme_unet_debug_read(const dmme_plan* plan, const void* workspace, 
 DMME_API int dmme_unet_debug_read_grad(const dmme_plan* plan, const void* bwd_workspace, const char* name, float* dst,
                          int64_t numel_cap, int64_t* numel_out, void* stream);
 
+/* ---- the device random stream (dmme_dropout_masks, dmme_randn, the noise of dmme_chain_update) -----------------------
+ * Philox4x32-10 (Salmon et al., SC'11).  A draw is a span (seed, offset, numel); the offset counts quads of 4 values.
+ *   counter   quad q of the span uses the 64-bit counter offset + q (mod 2^64) as the counter words {lo, hi, 0, 0}
+ *   key       the 64-bit seed as the key words {lo, hi}
+ *   order     quad q fills elements 4q .. 4q+3 from its output words x0 .. x3; the last quad is cut off at numel (its other
+ *             words are discarded), so a span consumes ceil(numel / 4) counters and the next span starts there
+ *   uniform   u(x) = ((x >> 8) + 1) / 2^24, on the grid k / 2^24 with k = 1 .. 2^24: u lies in (0, 1], exact in fp32
+ *   normals   (z0, z1) = r (cos a, sin a) with r = sqrt(-2 ln u(x0)), a = fp32(2 pi) * u(x1) rounded to fp32; (z2, z3) the
+ *             same from (x2, x3).  u >= 2^-24 bounds every value: |z| <= sqrt(48 ln 2) = 5.768
+ *   masks     element i is 0 where u(x_i) <= p (fp32 compare), else 1 / (1 - p) in fp32: drop probability floor(p 2^24) / 2^24
+ * The Python side takes the seed and the offset (its offset / 4) from torch's CUDA generator and advances it by 4 ceil(numel / 4)
+ * per span; mask draws use the key seed ^ 0x5DEECE66D, a key apart from the noise's under the same seed.
+ * tests/philox_ref.py restates this contract in numpy; tests/test_gpu_random.py holds the kernels to it. */
+
 /* Dropout2d multipliers from the library's own Philox stream (train mode without
- * injected masks): keep with probability 1-p, value 1/(1-p). */
+ * injected masks): keep with probability 1-p, value 1/(1-p); dmme_unet_plan_dropmask_numel values of the stream above. */
 DMME_API int dmme_dropout_masks(const dmme_plan* plan, uint64_t seed, uint64_t offset, float* masks, void* stream);
 
 /* ---- diffusion process (elementwise; all NCHW fp32) --------------------------------- */
 
 /* standard normal fill from the library's Philox4x32-10 stream: replaces dmme.gaussian
- * (src/dmme/common/noise.py:4-6) / the draw inside Normal.sample(). */
+ * (src/dmme/common/noise.py:4-6) / the draw inside Normal.sample().  out[0 .. numel) receives the normals of the span
+ * (seed, offset, numel) of the stream above; nothing past numel is written. */
 DMME_API int dmme_randn(float* out, int64_t numel, uint64_t seed, uint64_t offset, void* stream);
 
 /* forward noising: replaces forward_process(...).sample() and the target re-derivation
