@@ -16,7 +16,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 F16R32 = 4  # F16 below the full-resolution level; that level in fp32 tensors with three-pass split-fp16 products (within 1e-3 of fp32; inference)
 F32, BF16, BF16X3, F16 = 0, 1, 2, 3  # BF16X3: fp32 buffers, three-pass bf16 MFMA convolutions (the accurate mode); F16: IEEE half (inference)
-CHAIN_DDPM, CHAIN_DDIM, CHAIN_IDDPM = 0, 1, 2
+CHAIN_DDPM, CHAIN_DDIM, CHAIN_IDDPM, CHAIN_DDPM_GUIDED, CHAIN_DDIM_GUIDED = 0, 1, 2, 3, 4
+ARCH_DDPM, ARCH_IDDPM, ARCH_CLASSIFIER = 0, 1, 2
 DTYPES = {"fp32": F32, "float32": F32, "32": F32, "bf16": BF16, "bfloat16": BF16, "16": BF16, "bf16-mixed": BF16, "16-mixed": BF16,
           "bf16x3": BF16X3, "fp16": F16, "float16": F16, "half": F16, "fp16r32": F16R32}
 
@@ -38,6 +39,7 @@ class UNetCfg(C.Structure):
         ("attention_depths", C.c_int * 8),
         ("arch", C.c_int),
         ("num_heads", C.c_int),
+        ("num_classes", C.c_int),
     ]
 
 
@@ -96,6 +98,7 @@ PROTOTYPES = {
     "dmme_unet_pack_params_bwd": (_i, [_vp, _vp, _vp, _vp]),
     "dmme_unet_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmme_unet_backward_buckets": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, BUCKET_FN, _vp]),
+    "dmme_unet_backward_input": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmme_unet_plan_grad_buckets": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i), _i]),
     "dmme_unet_plan_bwd_summary": (_i, [_vp, C.c_char_p, _i]),
     "dmme_grad_norm": (_i, [_vp, _i64, _vp, _vp, _vp]),
@@ -116,6 +119,9 @@ PROTOTYPES = {
     "dmme_chain_set": (_i, [_vp, _i64, _vp, _u64, _u64, _vp]),
     "dmme_chain_update": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "dmme_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dmme_log_softmax_grad": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "dmme_chain_update_guided": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
+    "dmme_guided_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "dmme_mse_loss": (_i, [_vp, _vp, _i64, _vp, _vp, _f, _vp, _vp]),
     "dmme_image_batch": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "dmme_iddpm_step": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _i64, _vp]),

@@ -371,7 +371,17 @@ int launch_ddpm_step(float* x, const float* eps, const float* z, float c1, float
 int launch_ddim_step(float* x, const float* eps, float s1, float s2, int64_t numel, hipStream_t s);
 int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s);
 int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
-                        hipStream_t s);
+                        hipStream_t s, const float* grad = nullptr, const float* noise = nullptr);
+// guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
+// the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient
+int launch_cls_head_fwd(int dtype, const void* top, int B, int HW, int C, int G, const float* gamma, const float* beta, const float* W,
+                        const float* bias, int K, float* logits, hipStream_t s);
+int launch_cls_head_bwd(int dtype, const void* top, int B, int HW, int C, int G, const float* gamma, const float* beta, const float* W, int K,
+                        const float* dlog, void* dtop, float* pooled, float* rows, hipStream_t s);
+int launch_cls_head_wgrad(const float* dlog, const float* pooled, const float* rows, int B, int K, int C, float* dW, float* db, float* dgamma,
+                          float* dbeta, hipStream_t s);
+int launch_log_softmax_grad(const float* logits, const int64_t* y, int B, int K, int mode, float scale, float* loss, float* dlog, int* status,
+                            hipStream_t s);
 int launch_image_batch(const uint8_t* data, const int64_t* idx, const uint8_t* flip, int B, int C, int H, int W, float* out, hipStream_t s);
 int launch_iddpm_step(float* x, const float* out, const float* z, float c1, float c2, float log_beta, float log_beta_tilde, int add_noise,
                       int B, int64_t chw, hipStream_t s);

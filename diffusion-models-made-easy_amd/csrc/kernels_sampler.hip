@@ -348,9 +348,13 @@ __global__ void chain_set_kernel(ChainState* st, long long i, const long long* _
 
 // KIND 0: DDPM (coef = 1/sqrt(alpha), beta/sqrt(1-abar), sqrt(beta)), 1: DDIM (sqrt(1-abar_tau_i), sqrt(abar_tau_{i-1})),
 //      2: IDDPM (1/sqrt(alpha), beta/sqrt(1-abar), log beta, log max(beta~, 1e-12)); `out` has 2*chw values per image then
+//      3: classifier-guided DDPM (coef 0..2 as DDPM, coef[3] = s beta_t): x = mean + s beta_t g (+ sqrt(beta_t) z)
+//      4: classifier-guided DDIM (coef 0..1 as DDIM, coef[2] = s sqrt(1-abar_tau_i)): eps' = eps - s sqrt(1-abar_tau_i) g, then DDIM
+// g: d log p(y | x_t, t) / d x_t (guided kinds); zin (nullable, guided kinds): normals to use instead of the drawn ones (tests)
 template <int KIND>
 __global__ void __launch_bounds__(256) chain_update_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ coef,
-                                                           const long long* __restrict__ t_table, ChainState* st, int64_t chw, int64_t n4) {
+                                                           const long long* __restrict__ t_table, ChainState* st, int64_t chw, int64_t n4,
+                                                           const float* __restrict__ g = nullptr, const float* __restrict__ zin = nullptr) {
     const long long i = st->i, t = st->t;
     const unsigned long long off = st->offset, seed = st->seed;
     const float c0 = coef[4 * i], c1 = coef[4 * i + 1], c2 = coef[4 * i + 2], c3 = coef[4 * i + 3];
@@ -364,6 +368,35 @@ __global__ void __launch_bounds__(256) chain_update_kernel(float* __restrict__ x
             const float* es = reinterpret_cast<const float*>(&ev);
 #pragma unroll
             for (int j = 0; j < 4; ++j) xs[j] = __fmul_rn(c1, __fdiv_rn(__fsub_rn(xs[j], __fmul_rn(c0, es[j])), c1));
+        } else if (KIND == 4) {
+            const float4 ev = *reinterpret_cast<const float4*>(out + b);
+            const float4 gv = *reinterpret_cast<const float4*>(g + b);
+            const float* es = reinterpret_cast<const float*>(&ev);
+            const float* gs = reinterpret_cast<const float*>(&gv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float e = __fsub_rn(es[j], __fmul_rn(c2, gs[j]));
+                xs[j] = __fmul_rn(c1, __fdiv_rn(__fsub_rn(xs[j], __fmul_rn(c0, e)), c1));
+            }
+        } else if (KIND == 3) {
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (add_noise) {
+                if (zin) {
+                    const float4 zv = *reinterpret_cast<const float4*>(zin + b);
+                    z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+                } else {
+                    normal4(seed, off + (uint64_t)q, z);
+                }
+            }
+            const float4 ev = *reinterpret_cast<const float4*>(out + b);
+            const float4 gv = *reinterpret_cast<const float4*>(g + b);
+            const float* es = reinterpret_cast<const float*>(&ev);
+            const float* gs = reinterpret_cast<const float*>(&gv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float m = __fadd_rn(__fmul_rn(c0, __fsub_rn(xs[j], __fmul_rn(c1, es[j]))), __fmul_rn(c3, gs[j]));  // (the shift stays at t == 1)
+                xs[j] = add_noise ? __fadd_rn(m, __fmul_rn(c2, z[j])) : m;
+            }
         } else {
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (add_noise) normal4(seed, off + (uint64_t)q, z);  // the reference draws and discards at t == 1: the offset still advances
@@ -408,8 +441,9 @@ int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t se
 }
 
 int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
-                        hipStream_t s) {
-    DMME_REQUIRE(kind >= 0 && kind <= 2, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
+                        hipStream_t s, const float* grad, const float* noise) {
+    DMME_REQUIRE(kind >= 0 && kind <= 4, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
+    DMME_REQUIRE((kind >= 3) == (grad != nullptr), DMME_ERR_INVALID, "chain_update: the guided kinds (3, 4) and only they take a gradient");
     DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "chain_update: image size %lld is not a multiple of 4", (long long)chw);
     const int64_t n4 = (int64_t)B * chw / 4;
     if (n4 <= 0) return DMME_OK;
@@ -420,8 +454,12 @@ int launch_chain_update(int kind, float* x, const float* out, const float* coef,
         hipLaunchKernelGGL(chain_update_kernel<0>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
     else if (kind == 1)
         hipLaunchKernelGGL(chain_update_kernel<1>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
-    else
+    else if (kind == 2)
         hipLaunchKernelGGL(chain_update_kernel<2>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
+    else if (kind == 3)
+        hipLaunchKernelGGL(chain_update_kernel<3>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    else
+        hipLaunchKernelGGL(chain_update_kernel<4>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

@@ -130,7 +130,11 @@ struct dmme_plan {
     int x3 = 0;            // DMME_BF16X3: dtype is DMME_F32 (storage), the convolutions take the three-pass bf16 MFMA path
     int mix = 0;           // DMME_F16R32: dtype is DMME_F16; the tensors of the full-resolution level are fp32 and its convolutions run
                            // three fp16 MFMA passes on hi / lo halves (or, for the few small ones, the fp32-tensor kernels above)
-    int out_channels = 0;  // in_channels (DDPM) or 2 * in_channels (IDDPM: eps, v)
+    int out_channels = 0;  // in_channels (DDPM) or 2 * in_channels (IDDPM: eps, v); DMME_ARCH_CLASSIFIER: num_classes (logits)
+    // DMME_ARCH_CLASSIFIER: the head `out` (GroupNorm, SiLU, spatial mean, Linear) behind the op list, reading tensor head_src (the
+    // middle layers' output); its parameters: out.0 (gamma, beta) and out.2 (weight [K][C_top], bias), fp32 in the packed buffer
+    int head_src = -1, p_hgw = -1, p_hgb = -1, p_hw = -1, p_hb = -1;
+    int64_t bws_hpool = 0, bws_hrows = 0;  // backward: pooled activations [B][C_top], per-image d beta / d gamma [B][2][C_top]
     std::vector<Param> params;
     std::vector<Tensor> tensors;
     std::vector<Op> ops;
@@ -155,6 +159,7 @@ struct dmme_plan {
     int64_t bws_zero = 0, bws_zero_bytes = 0, bws_wimage = 0, bws_gnS = 0, bws_zpage = 0;  // region cleared once per backward
     PackItem* items_unpack_dev = nullptr;
     int n_items_unpack = 0;
+    int64_t bws_sink = 0, sink_half = 0;  // input-only backward: where the GroupNorm backward's (unused) d gamma / d beta go (2 x sink_half floats)
     int64_t bws_tmp = 0, bws_dy = 0, bws_rowsum = 0, bws_dtproj = 0, bws_dtemb = 0, bws_dh1 = 0, bws_z = 0, bws_wT = 0, bws_attP = 0,
             bws_attdS = 0;
     PackItem* items_bwd_dev = nullptr;

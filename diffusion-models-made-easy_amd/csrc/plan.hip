@@ -180,6 +180,8 @@ int build_plan(dmme_plan* P) {
     bld.lin("condition.3", c.emb_dim, c.emb_dim, l2w, l2b);
     P->p_l1w = l1w; P->p_l1b = l1b; P->p_l2w = l2w; P->p_l2b = l2b;
     bld.conv("input_conv", c.in_channels, chans[0], 3, icw, icb);
+    const bool cls = c.arch == DMME_ARCH_CLASSIFIER;  // the encoder half + head: no up path, no output conv
+    if (cls) up.clear();
     for (auto* seq : {&down, &up, &mid})
         for (auto& n : *seq) {
             if (n.kind == 0)
@@ -189,9 +191,18 @@ int build_plan(dmme_plan* P) {
             else
                 bld.conv(n.prefix + ".conv", n.cin, n.cout, 3, n.cw, n.cb);
         }
-    bld.gn("output_conv.0", chans[0], ogw, ogb);
-    P->out_channels = c.arch == DMME_ARCH_IDDPM ? 2 * c.in_channels : c.in_channels;
-    bld.conv("output_conv.2", chans[0], P->out_channels, 3, ocw, ocb);
+    if (cls) {  // out = GroupNorm(C_top) -> SiLU -> mean over H x W -> Linear(C_top, num_classes); all four stay fp32 when packed
+        const int top = chans[L - 1];
+        bld.gn("out.0", top, P->p_hgw, P->p_hgb);
+        P->p_hw = bld.add_param("out.2.weight", {c.num_classes, top}, false, true, c.num_classes, top, 1);
+        P->p_hb = bld.add_param("out.2.bias", {c.num_classes}, false, true, 1, c.num_classes, 1);
+        P->out_channels = c.num_classes;
+        ogw = ogb = ocw = ocb = -1;
+    } else {
+        bld.gn("output_conv.0", chans[0], ogw, ogb);
+        P->out_channels = c.arch == DMME_ARCH_IDDPM ? 2 * c.in_channels : c.in_channels;
+        bld.conv("output_conv.2", chans[0], P->out_channels, 3, ocw, ocb);
+    }
     P->ref_numel = bld.ref_cursor;
 
     // ---- packed layout: the per-block time projections form one [sumCout][emb] matrix ----
@@ -445,7 +456,9 @@ int build_plan(dmme_plan* P) {
             P->named[n.prefix] = cur_t;
         }
     }
-    {
+    if (cls) {
+        P->head_src = cur_t;
+    } else {
         const int g = emit_gn(cur_t, -1, ogw, ogb);
         Op o{};
         o.kind = OP_CONV;
@@ -558,8 +571,14 @@ int build_plan(dmme_plan* P) {
             }
             P->bws_gnS = balloc((int64_t)B * c.num_groups * 2 * 4);
         }
+        P->sink_half = (int64_t)2 * cmax;  // (a concatenated GroupNorm input has up to 2 x the widest tensor's channels)
+        P->bws_sink = balloc(2 * P->sink_half * 4);
+        if (cls) {
+            P->bws_hpool = balloc((int64_t)B * P->tensors[P->head_src].C * 4);
+            P->bws_hrows = balloc((int64_t)B * 2 * P->tensors[P->head_src].C * 4);
+        }
         P->bws_tmp = balloc(tmp_max);
-        P->bws_dy = balloc((int64_t)B * P->H * P->W * P->out_channels * es);
+        P->bws_dy = balloc(cls ? (int64_t)B * P->out_channels * 4 : (int64_t)B * P->H * P->W * P->out_channels * es);  // (classifier: d logits, fp32)
         P->bws_rowsum = balloc((int64_t)B * cmax * 3 * 4);  // qkv convs have 3*C outputs
         P->bws_dtproj = balloc((int64_t)B * tcols * 4);
         P->bws_dtemb = balloc((int64_t)B * c.emb_dim * 4);
@@ -1284,7 +1303,7 @@ void op_account(const dmme_plan* P, const Op& o, char* label, int cap, double* f
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 106; }  // 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 107; }  // 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1306,7 +1325,13 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
                  "plan_create: bad depth/blocks");
     DMME_REQUIRE(cfg->num_attention_depths >= 0 && cfg->num_attention_depths <= 8, DMME_ERR_INVALID, "bad attention_depths");
     DMME_REQUIRE(cfg->pos_dim >= 4 && cfg->pos_dim % 2 == 0, DMME_ERR_INVALID, "pos_dim must be even and >= 4");
-    DMME_REQUIRE(cfg->arch == DMME_ARCH_DDPM || cfg->arch == DMME_ARCH_IDDPM, DMME_ERR_INVALID, "plan_create: unknown arch %d", cfg->arch);
+    DMME_REQUIRE(cfg->arch == DMME_ARCH_DDPM || cfg->arch == DMME_ARCH_IDDPM || cfg->arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+                 "plan_create: unknown arch %d", cfg->arch);
+    if (cfg->arch == DMME_ARCH_CLASSIFIER) {
+        DMME_REQUIRE(!x3 && !mix, DMME_ERR_UNSUPPORTED, "plan_create: the classifier runs in fp32, bf16 or fp16 (not %s)", x3 ? "bf16x3" : "fp16r32");
+        DMME_REQUIRE(cfg->num_classes >= 1, DMME_ERR_INVALID, "plan_create: classifier num_classes=%d", cfg->num_classes);
+        DMME_REQUIRE(cfg->channels_per_depth[cfg->num_depths - 1] <= 1024, DMME_ERR_UNSUPPORTED, "plan_create: classifier head wider than 1024 channels");
+    }
     if (cfg->arch == DMME_ARCH_IDDPM) {
         DMME_REQUIRE(cfg->num_heads >= 1, DMME_ERR_INVALID, "plan_create: num_heads must be >= 1");
     }
@@ -1439,7 +1464,7 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
                 }
             }
             cuts.push_back(0);
-            bool clean = cuts.size() > 2 && !getenv("DMME_NO_GRAD_BUCKETS");
+            bool clean = cuts.size() > 2 && !getenv("DMME_NO_GRAD_BUCKETS") && P->cfg.arch != DMME_ARCH_CLASSIFIER;  // (no buckets for the classifier)
             if (clean) {
                 P->gb.resize(cuts.size() - 1);
                 for (size_t b = 0; b + 1 < cuts.size(); ++b) {
@@ -1709,6 +1734,12 @@ static int unet_forward_impl(const dmme_plan* plan, const void* packed, const fl
         const int rc = run_op(P, o, pk, x, t, nt, y, ws, drop_masks, s, keep_ctx);
         if (rc != DMME_OK) return rc;
     }
+    if (P->head_src >= 0) {  // classifier head: GroupNorm + SiLU + spatial mean + Linear -> logits (B, K), one launch
+        const Tensor& tt = P->tensors[P->head_src];
+        return launch_cls_head_fwd(P->dtype, ws + tt.off, P->B, tt.H * tt.W, tt.C, P->cfg.num_groups, (const float*)(pk + P->params[P->p_hgw].packed_off),
+                                   (const float*)(pk + P->params[P->p_hgb].packed_off), (const float*)(pk + P->params[P->p_hw].packed_off),
+                                   (const float*)(pk + P->params[P->p_hb].packed_off), P->out_channels, y, s);
+    }
     return DMME_OK;
 }
 DMME_API int dmme_unet_forward(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len,
@@ -1886,6 +1917,8 @@ DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x
                              const float* step_coef, const int64_t* t_table, void* state, void* stream) {
     DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state, DMME_ERR_INVALID, "chain_step: null argument");
     if (int rc0 = lvl_check(plan, "chain_step", (hipStream_t)stream, true)) return rc0;
+    DMME_REQUIRE(kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_IDDPM && plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+                 "chain_step: sampler kind %d / architecture %d (guided kinds: dmme_guided_chain_step)", kind, plan->cfg.arch);
     DMME_REQUIRE((kind == DMME_CHAIN_IDDPM) == (plan->out_channels == 2 * plan->cfg.in_channels), DMME_ERR_INVALID,
                  "chain_step: sampler kind %d does not fit a network with %d output channels", kind, plan->out_channels);
     // the timestep the network is evaluated at is the second word of the device-resident loop state
@@ -1894,6 +1927,42 @@ DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x
     if (rc != DMME_OK) return rc;
     return launch_chain_update(kind, x, model_out, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
                                (hipStream_t)stream);
+}
+
+DMME_API int dmme_log_softmax_grad(const float* logits, const int64_t* y, int B, int K, int mode, float scale, float* loss, float* d_logits,
+                                   int* status, void* stream) {
+    return launch_log_softmax_grad(logits, y, B, K, mode, scale, loss, d_logits, status, (hipStream_t)stream);
+}
+
+DMME_API int dmme_chain_update_guided(int kind, float* x, const float* model_out, const float* grad, const float* noise, const float* step_coef,
+                                      const int64_t* t_table, void* state, int B, int64_t chw, void* stream) {
+    DMME_REQUIRE(x && model_out && grad && step_coef && t_table && state && B > 0 && chw > 0, DMME_ERR_INVALID, "chain_update_guided: bad argument");
+    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED, DMME_ERR_INVALID, "chain_update_guided: kind %d is not a guided kind", kind);
+    return launch_chain_update(kind, x, model_out, step_coef, t_table, state, B, chw, (hipStream_t)stream, grad, noise);
+}
+
+// Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM) as one launch sequence with every per-step value device-resident (capturable)
+DMME_API int dmme_guided_chain_step(const dmme_plan* plan, const void* packed, const dmme_plan* cls, const void* cls_packed,
+                                    const void* cls_packed_bwd, float* x, float* model_out, void* workspace, void* cls_workspace,
+                                    void* cls_bwd_workspace, const int64_t* y, float* logits, float* d_logits, float* grad, int* status,
+                                    int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && cls && cls_packed && cls_packed_bwd && x && model_out && workspace && cls_workspace && cls_bwd_workspace && y &&
+                 logits && d_logits && grad && step_coef && t_table && state, DMME_ERR_INVALID, "guided_chain_step: null argument");
+    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED, DMME_ERR_INVALID, "guided_chain_step: kind %d is not a guided kind", kind);
+    DMME_REQUIRE(plan->cfg.arch == DMME_ARCH_DDPM && cls->cfg.arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+                 "guided_chain_step: needs a DDPM UNet plan and a classifier plan (got architectures %d, %d)", plan->cfg.arch, cls->cfg.arch);
+    DMME_REQUIRE(plan->B == cls->B && plan->H == cls->H && plan->W == cls->W && plan->cfg.in_channels == cls->cfg.in_channels, DMME_ERR_INVALID,
+                 "guided_chain_step: the UNet plan (B=%d %dx%d) and the classifier plan (B=%d %dx%d) differ", plan->B, plan->H, plan->W, cls->B, cls->H, cls->W);
+    if (int rc0 = lvl_check(plan, "guided_chain_step", (hipStream_t)stream, true)) return rc0;
+    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
+    int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false);
+    if (rc == DMME_OK) rc = unet_forward_impl(cls, cls_packed, x, t_dev, 1, logits, cls_workspace, nullptr, stream, true);
+    if (rc == DMME_OK) rc = launch_log_softmax_grad(logits, y, cls->B, cls->out_channels, 1, 1.0f, nullptr, d_logits, status, (hipStream_t)stream);
+    if (rc == DMME_OK)
+        rc = dmme_unet_backward_input(cls, cls_packed, cls_packed_bwd, x, t_dev, 1, d_logits, cls_workspace, cls_bwd_workspace, nullptr, grad, stream);
+    if (rc != DMME_OK) return rc;
+    return launch_chain_update(kind, x, model_out, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
+                               (hipStream_t)stream, grad, nullptr);
 }
 
 DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64_t* idx, const uint8_t* flip, int B, int C, int H, int W,

@@ -128,7 +128,9 @@ DMME_API int dmme_unet_pack_params_bwd(const dmme_plan* plan, const float* ref_f
 static int backward_impl(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t, int t_len,
                          const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks, float* grad_flat, float* d_x,
                          void* stream, dmme_bucket_fn ready, void* user) {
-    DMME_REQUIRE(plan && packed && packed_bwd && x && t && d_y && workspace && bwd_workspace && grad_flat, DMME_ERR_INVALID,
+    // grad_flat == nullptr: the input-only backward (dmme_unet_backward_input) - d_x alone, no weight-gradient launch of any kind
+    const bool weights = grad_flat != nullptr;
+    DMME_REQUIRE(plan && packed && packed_bwd && x && t && d_y && workspace && bwd_workspace && (weights || d_x), DMME_ERR_INVALID,
                  "unet_backward: null argument");
     DMME_REQUIRE(t_len == 1 || t_len == plan->B, DMME_ERR_INVALID, "unet_backward: bad t_len %d", t_len);
     if (int rc0 = lvl_check(plan, "unet_backward", (hipStream_t)stream, true)) return rc0;  // (the forward this backward differentiates ran through the engine)
@@ -164,14 +166,33 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
         return launch_grad_acc(dt, src, gptr(id), nullptr, t.C, 0, acc, 0, 0, B, t.H, t.W, s);
     };
 
-    DMME_CHECK_HIP(hipMemsetAsync(bws + P->bws_zero, 0, (size_t)P->bws_zero_bytes, s));
+    // (the region holds only accumulators of weight gradients and column sums: the input-only form reads none of it)
+    if (weights) DMME_CHECK_HIP(hipMemsetAsync(bws + P->bws_zero, 0, (size_t)P->bws_zero_bytes, s));
     float* wimage = (float*)(bws + P->bws_wimage);
     float* dtproj = (float*)(bws + P->bws_dtproj);
     char* tmp = bws + P->bws_tmp;
+    float* sink = (float*)(bws + P->bws_sink);  // input-only form: the GroupNorm backward's d gamma / d beta land here, unread
+    auto pgrad = [&](int param, int which) -> float* { return weights ? grad_flat + P->params[param].ref_off : sink + which * P->sink_half; };
     // (the first launch: it checks the device-side mark of the forward form, which a replayed no-grad graph sets without the host seeing it)
-    int rc = launch_nchw_to_nhwc(dt, d_y, B, P->out_channels, P->H * P->W, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host);
+    // classifier: d_y is d logits (B, K) fp32 - copied as is (HW = 1, fp32) through the same mark check
+    int rc = P->head_src >= 0 ? launch_nchw_to_nhwc(DMME_F32, d_y, B, P->out_channels, 1, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host)
+                              : launch_nchw_to_nhwc(dt, d_y, B, P->out_channels, P->H * P->W, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host);
     if (rc != DMME_OK) return rc;
-    const bool buckets = ready != nullptr && !P->gb.empty();  // bucketed mode: deferred work flushed per gradient bucket
+    if (P->head_src >= 0) {  // the head: d logits -> d(top map), written whole; its parameters' gradients (weights form only)
+        const Tensor& tt = P->tensors[P->head_src];
+        const float* dlog = (const float*)(bws + P->bws_dy);
+        float* pool = weights ? (float*)(bws + P->bws_hpool) : nullptr;
+        float* hrows = weights ? (float*)(bws + P->bws_hrows) : nullptr;
+        rc = launch_cls_head_bwd(dt, ws + tt.off, B, tt.H * tt.W, tt.C, G, (const float*)(pk + P->params[P->p_hgw].packed_off),
+                                 (const float*)(pk + P->params[P->p_hgb].packed_off), (const float*)(pk + P->params[P->p_hw].packed_off), P->out_channels, dlog,
+                                 gptr(P->head_src), pool, hrows, s);
+        if (rc == DMME_OK && weights)
+            rc = launch_cls_head_wgrad(dlog, pool, hrows, B, P->out_channels, tt.C, grad_flat + P->params[P->p_hw].ref_off, grad_flat + P->params[P->p_hb].ref_off,
+                                       grad_flat + P->params[P->p_hgw].ref_off, grad_flat + P->params[P->p_hgb].ref_off, s);
+        if (rc != DMME_OK) return rc;
+        written[P->head_src] = 1;
+    }
+    const bool buckets = weights && ready != nullptr && !P->gb.empty();  // bucketed mode: deferred work flushed per gradient bucket
     const int emb = P->cfg.emb_dim, pos = P->cfg.pos_dim, tc = P->tproj_cols;
     const float* temb = (const float*)(ws + P->ws_temb);
     // deferred launches of one gradient bucket (b >= 0) or of everything (b = -1): bias + time rows, grouped weight gradients, unpack,
@@ -226,7 +247,7 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
         for (const auto& r : P->gb[b].ranges) ready(user, b, r.first, r.second);
     };
     int next_bucket = 0;  // the bucket whose stretch the reverse walk is in
-    if (P->cfg.arch == DMME_ARCH_IDDPM && nt == 1)  // shared timestep row: the GroupNorm backward accumulates into it atomically
+    if (weights && P->cfg.arch == DMME_ARCH_IDDPM && nt == 1)  // shared timestep row: the GroupNorm backward accumulates into it atomically
         DMME_CHECK_HIP(hipMemsetAsync(dtproj, 0, (size_t)P->tproj_cols * 4, s));
 
     for (int oi = (int)P->ops.size() - 1; oi >= 0 && rc == DMME_OK; --oi) {
@@ -272,7 +293,9 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
         const int Cin = a.C1 + a.C2;
         float* rowsum = (float*)(bws + o.b_rowsum);
         // 1. bias and time-embedding-row gradients (column sums of dY)
-        if (o.bias_deferred && P->bias_jobs_dev && P->col_jobs_dev)
+        if (!weights)
+            rc = DMME_OK;  // (input-only form)
+        else if (o.bias_deferred && P->bias_jobs_dev && P->col_jobs_dev)
             rc = DMME_OK;  // its column sums come from the grouped launch of the flush
         else if (o.bias_deferred && P->bias_jobs_dev)
             rc = launch_colsum_fast(dt, dy, B, a.Hout * a.Wout, a.Cout, rowsum, nullptr, nullptr, P->tproj_cols, nt, s);
@@ -284,7 +307,9 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
                                o.tproj_col >= 0 ? dtproj + o.tproj_col : nullptr, P->tproj_cols, nt, s);
         if (rc != DMME_OK) break;
         // 2. weight gradient: deferred to the grouped launch below, or per layer (packed image / reference layout)
-        if (o.wg_layer >= 0 && (buckets ? P->gb[next_bucket].wg[wg_index(o)].jobs_dev : P->wg[wg_index(o)].jobs_dev))
+        if (!weights)
+            rc = DMME_OK;  // (input-only form)
+        else if (o.wg_layer >= 0 && (buckets ? P->gb[next_bucket].wg[wg_index(o)].jobs_dev : P->wg[wg_index(o)].jobs_dev))
             rc = DMME_OK;
         else if (wgrad_mfma_supported(dt, a))
             rc = launch_wgrad_mfma(dt, a, dy, wimage + P->params[o.w].wp_off, s);
@@ -363,15 +388,15 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
                 if (gn_bwd_fast_supported(dt, t1.H * t1.W, a.C1, a.C2))
                     rc = launch_gn_bwd_fast(dt, tmp, a.src1, a.src2, B, t1.H * t1.W, a.C1, a.C2, G,
                                             (const float*)(pk + P->params[gop.gn_gamma].packed_off), (const float*)(ws + gop.gn_mr), a.scale,
-                                            a.shift, a.dmask, a.pro_silu, g1, g2, acc1, acc2, grad_flat + P->params[gop.gn_gamma].ref_off,
-                                            grad_flat + P->params[gop.gn_beta].ref_off, (float*)(bws + o.b_ab), (float*)(bws + P->bws_gnS), mod, s,
-                                            o.wg_act >= 0 ? bws + o.wg_act : nullptr,
-                                            o.gn_rows_deferred && P->bias_jobs_dev ? (float*)(bws + o.b_gnrows) : nullptr, extra);
+                                            a.shift, a.dmask, a.pro_silu, g1, g2, acc1, acc2, pgrad(gop.gn_gamma, 0),
+                                            pgrad(gop.gn_beta, 1), (float*)(bws + o.b_ab), (float*)(bws + P->bws_gnS), mod, s,
+                                            weights && o.wg_act >= 0 ? bws + o.wg_act : nullptr,
+                                            weights && o.gn_rows_deferred && P->bias_jobs_dev ? (float*)(bws + o.b_gnrows) : nullptr, extra);
                 else
                 rc = launch_gn_bwd_generic(dt, tmp, a.src1, a.src2, B, t1.H * t1.W, a.C1, a.C2, G,
                                            (const float*)(pk + P->params[gop.gn_gamma].packed_off), (const float*)(ws + gop.gn_mr),
                                            a.scale, a.shift, a.dmask, a.pro_silu, g1, g2, acc1, acc2,
-                                           grad_flat + P->params[gop.gn_gamma].ref_off, grad_flat + P->params[gop.gn_beta].ref_off, mod, s);
+                                           pgrad(gop.gn_gamma, 0), pgrad(gop.gn_beta, 1), mod, s);
             } else if (!dgrad_direct) {
                 rc = launch_grad_acc(dt, tmp, g1, g2, a.C1, a.C2, acc1, acc2, o.up == 1 ? 1 : 0, B, t1.H, t1.W, s);
             }
@@ -412,7 +437,7 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
         }
     }
     for (int id = 0; id < (int)pending.size() && rc == DMME_OK; ++id) rc = flush_pending(id);
-    if (rc != DMME_OK) return rc;
+    if (rc != DMME_OK || !weights) return rc;
     rc = flush(buckets ? (int)P->gb.size() - 1 : -1);
     if (rc != DMME_OK) return rc;
 
@@ -454,12 +479,21 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
 DMME_API int dmme_unet_backward(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x,
                                 const int64_t* t, int t_len, const float* d_y, void* workspace, void* bwd_workspace,
                                 const float* drop_masks, float* grad_flat, float* d_x, void* stream) {
+    DMME_REQUIRE(grad_flat, DMME_ERR_INVALID, "unet_backward: null argument (grad_flat)");
     return backward_impl(plan, packed, packed_bwd, x, t, t_len, d_y, workspace, bwd_workspace, drop_masks, grad_flat, d_x, stream, nullptr, nullptr);
+}
+
+DMME_API int dmme_unet_backward_input(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t,
+                                      int t_len, const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks, float* d_x,
+                                      void* stream) {
+    DMME_REQUIRE(d_x, DMME_ERR_INVALID, "unet_backward_input: d_x is required");
+    return backward_impl(plan, packed, packed_bwd, x, t, t_len, d_y, workspace, bwd_workspace, drop_masks, nullptr, d_x, stream, nullptr, nullptr);
 }
 
 DMME_API int dmme_unet_backward_buckets(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x,
                                         const int64_t* t, int t_len, const float* d_y, void* workspace, void* bwd_workspace,
                                         const float* drop_masks, float* grad_flat, float* d_x, void* stream, dmme_bucket_fn ready, void* user) {
+    DMME_REQUIRE(grad_flat, DMME_ERR_INVALID, "unet_backward: null argument (grad_flat)");
     DMME_REQUIRE(ready, DMME_ERR_INVALID, "unet_backward_buckets: null callback");
     return backward_impl(plan, packed, packed_bwd, x, t, t_len, d_y, workspace, bwd_workspace, drop_masks, grad_flat, d_x, stream, ready, user);
 }

@@ -58,12 +58,16 @@ class ChainRunner:
         )
         self.plan.fwd_gen = getattr(self.plan, "fwd_gen", 0) + 1  # the workspace was overwritten (pending backwards must refuse)
 
+    def _weights_key(self):
+        """identifies the packed weights the captured graph reads"""
+        return (self.plan.packed_version, self.plan.packed.data_ptr())
+
     def step(self):
         model = self.model
         if model.training:
             raise RuntimeError("ChainRunner: sampling chains run in eval mode (no dropout masks inside the replayed step)")
         packed = model._packed_for(self.plan)  # re-packs when the parameters changed
-        wkey = (self.plan.packed_version, self.plan.packed.data_ptr())
+        wkey = self._weights_key()
         if not self.use_graph or self.capture_error is not None:
             self._launch(packed)
             return self.x
@@ -100,7 +104,7 @@ class ChainRunner:
 
     def run(self, first: int, count: int):
         """`count` steps from loop index `first` downwards, drawing from torch's CUDA generator like the eager loop"""
-        if self.kind == _lib.CHAIN_DDIM:  # the DDIM update draws nothing: torch's generator stays where the eager loop leaves it
+        if self.kind in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED):  # the DDIM update draws nothing: torch's generator stays where the eager loop leaves it
             seed, off = 0, 0
         else:
             seed, off = philox_reserve(self.x.device, self.x.numel() * count)

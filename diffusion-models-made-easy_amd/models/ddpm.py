@@ -23,9 +23,10 @@ class _Scope(nn.Module):
     """Parameter container used to reproduce the reference's dotted state_dict keys."""
 
 
-def _cfg_struct(in_channels, pos_dim, emb_dim, num_groups, dropout, channels_per_depth, num_blocks, attention_depths, arch=0, num_heads=1):
+def _cfg_struct(in_channels, pos_dim, emb_dim, num_groups, dropout, channels_per_depth, num_blocks, attention_depths, arch=0, num_heads=1,
+                num_classes=0):
     cfg = _lib.UNetCfg()
-    cfg.arch, cfg.num_heads = int(arch), int(num_heads)
+    cfg.arch, cfg.num_heads, cfg.num_classes = int(arch), int(num_heads), int(num_classes)
     cfg.in_channels, cfg.pos_dim, cfg.emb_dim, cfg.num_groups = in_channels, pos_dim, emb_dim, num_groups
     cfg.dropout = float(dropout)
     if not 1 <= len(channels_per_depth) <= 8 or len(attention_depths) > 8:
@@ -98,6 +99,7 @@ class UNet(nn.Module):
         precision: str = "fp32",
         _arch: int = 0,
         _num_heads: int = 1,
+        _num_classes: int = 0,
     ):
         super().__init__()
         self.in_channels = in_channels
@@ -105,7 +107,8 @@ class UNet(nn.Module):
         self.dropout = float(dropout)
         self.precision = precision
         self._dtype = _lib.dtype_code(precision)
-        self._cfg = _cfg_struct(in_channels, pos_dim, emb_dim, num_groups, dropout, tuple(channels_per_depth), num_blocks, tuple(attention_depths), _arch, _num_heads)
+        self._cfg = _cfg_struct(in_channels, pos_dim, emb_dim, num_groups, dropout, tuple(channels_per_depth), num_blocks, tuple(attention_depths), _arch, _num_heads,
+                                _num_classes)
         self._plans: Dict[Tuple, _Plan] = {}
         self._injected_masks: Optional[Tensor] = None
         self._mask_calls = 0
@@ -370,16 +373,7 @@ class UNet(nn.Module):
         lib = plan.lib
         dev = xin.device
         dx = torch.empty_like(xin) if want_dx else None
-        if getattr(plan, "bws", None) is None:
-            plan.bws = torch.empty(int(lib.dmme_unet_plan_bwd_workspace_bytes(plan.h)), dtype=torch.uint8, device=dev)
-            plan.packed_bwd = torch.empty(int(lib.dmme_unet_plan_packed_bwd_bytes(plan.h)), dtype=torch.uint8, device=dev)
-            plan.packed_bwd_version = None
-        flat = self._ensure_flat()
-        packed = self._packed_for(plan)
-        ver = self._weights_key(flat)
-        if plan.packed_bwd_version != ver:
-            _lib.check(lib.dmme_unet_pack_params_bwd(plan.h, _lib.ptr(flat), _lib.ptr(plan.packed_bwd), _lib.stream_ptr()), "dmme_unet_pack_params_bwd")
-            plan.packed_bwd_version = ver
+        packed = self._bwd_buffers(plan)
         g = self.flat_grad()
         d = dy.detach().to(torch.float32).contiguous()
         amp = self.amp_state(dev)
@@ -427,6 +421,40 @@ class UNet(nn.Module):
             dx.div_(amp[0])
         return dx
 
+    def _bwd_buffers(self, plan: _Plan) -> Tensor:
+        """backward workspace and data-gradient weights of `plan` (created / re-packed when needed); returns the packed weights"""
+        lib = plan.lib
+        dev = plan.workspace.device
+        if getattr(plan, "bws", None) is None:
+            plan.bws = torch.empty(int(lib.dmme_unet_plan_bwd_workspace_bytes(plan.h)), dtype=torch.uint8, device=dev)
+            plan.packed_bwd = torch.empty(int(lib.dmme_unet_plan_packed_bwd_bytes(plan.h)), dtype=torch.uint8, device=dev)
+            plan.packed_bwd_version = None
+        flat = self._ensure_flat()
+        packed = self._packed_for(plan)
+        ver = self._weights_key(flat)
+        if plan.packed_bwd_version != ver:
+            _lib.check(lib.dmme_unet_pack_params_bwd(plan.h, _lib.ptr(flat), _lib.ptr(plan.packed_bwd), _lib.stream_ptr()), "dmme_unet_pack_params_bwd")
+            plan.packed_bwd_version = ver
+        return packed
+
+    def _backward_input_impl(self, saved, dy: Tensor) -> Tensor:
+        """d loss / d x alone (dmme_unet_backward_input): the parameters' gradient buffer is not touched"""
+        plan, xin, t, masks, gen = saved
+        if gen != plan.fwd_gen:
+            raise RuntimeError("input gradient: another forward of the same shape overwrote the saved activations")
+        packed = self._bwd_buffers(plan)
+        d = dy.detach().to(torch.float32).contiguous()
+        dx = torch.empty_like(xin)
+        _lib.check(
+            plan.lib.dmme_unet_backward_input(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(d),
+                                              _lib.ptr(plan.workspace), _lib.ptr(plan.bws), _lib.ptr(masks), _lib.ptr(dx), _lib.stream_ptr()),
+            "dmme_unet_backward_input",
+        )
+        return dx
+
+    def _out_shape(self, B: int, H: int, W: int) -> Tuple[int, ...]:
+        return (B, self.out_channels, H, W)
+
     def _forward_impl(self, x: Tensor, c: Tensor, want_ctx: bool = False):
         if getattr(self, "_exchange_in_flight", False):
             # a gradient exchange of this model is still on its side stream (distributed.OverlappedGradReducer between its first
@@ -442,7 +470,7 @@ class UNet(nn.Module):
             # takes int64 - refuse rather than truncate
             raise NotImplementedError("fractional timesteps are not supported by the HIP path (integer t only)")
         t = c.detach().reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
-        y = torch.empty((B, self.out_channels, H, W), dtype=torch.float32, device=x.device)
+        y = torch.empty(self._out_shape(B, H, W), dtype=torch.float32, device=x.device)
         masks = None
         if self.training and self.dropout > 0:
             if self._injected_masks is not None:

@@ -64,8 +64,14 @@ typedef enum { DMME_F32 = 0, DMME_BF16 = 1, DMME_BF16X3 = 2, DMME_F16 = 3, DMME_
 /* Which of the reference's two UNets the plan builds. */
 typedef enum {
     DMME_ARCH_DDPM = 0,  /* dmme.models.ddpm.UNet (src/dmme/models/ddpm.py:176-316): eps only */
-    DMME_ARCH_IDDPM = 1  /* dmme.models.iddpm.UNet (src/dmme/models/iddpm.py:125-265): scale-shift ResBlocks,
+    DMME_ARCH_IDDPM = 1, /* dmme.models.iddpm.UNet (src/dmme/models/iddpm.py:125-265): scale-shift ResBlocks,
                             multi-head attention, 2*in_channels outputs (eps, v) */
+    DMME_ARCH_CLASSIFIER = 2 /* the noise-aware classifier of classifier guidance (Dhariwal & Nichol 2021, the ADM "half UNet";
+                            the reference's src/dmme/guidance/classifier.py sketch): the DDPM UNet's time MLP, input_conv,
+                            down_layers and middle_layers (same keys and layouts), then the head `out` = GroupNorm -> SiLU ->
+                            mean over H x W -> Linear(C_top, num_classes).  No up path, no output conv.  The output y is the
+                            fp32 logits (B, num_classes).  fp32 / bf16 / fp16 only (bf16x3 / fp16r32: DMME_ERR_UNSUPPORTED);
+                            per-op launches (no level engine); no gradient buckets. */
 } dmme_unet_arch;
 
 /* Constructor arguments of the reference UNet (src/dmme/models/ddpm.py:190-200, models/iddpm.py:139-149). */
@@ -83,6 +89,7 @@ typedef struct {
     int arch;      /* dmme_unet_arch */
     int num_heads; /* DMME_ARCH_IDDPM: heads of MultiHeadAttention (the reference hard-codes 4, models/iddpm.py:82);
                       ignored (1) for DMME_ARCH_DDPM */
+    int num_classes; /* DMME_ARCH_CLASSIFIER: classes of the head (>= 1); ignored otherwise */
 } dmme_unet_cfg;
 
 typedef struct dmme_plan dmme_plan;
@@ -194,6 +201,14 @@ typedef void (*dmme_bucket_fn)(void* user, int bucket, int64_t offset, int64_t n
 DMME_API int dmme_unet_backward_buckets(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x,
                                const int64_t* t, int t_len, const float* d_y, void* workspace, void* bwd_workspace,
                                const float* drop_masks, float* grad_flat, float* d_x, void* stream, dmme_bucket_fn ready, void* user);
+/* The input gradient alone: the same backward pass as dmme_unet_backward, but only d_x (required) is written.  No weight-gradient
+ * launch runs (grouped or per-layer weight gradients, column sums, bias / time-projection reductions, the packed-image unpack, the
+ * time-MLP backward) and grad_flat does not exist here: what a guidance step needs, d log p(y | x_t, t) / d x_t, without paying for
+ * the parameters' gradients.  Either architecture (a DMME_ARCH_CLASSIFIER plan takes d_y = d logits, (B, num_classes) fp32).  No host
+ * synchronisation: capturable. */
+DMME_API int dmme_unet_backward_input(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t,
+                                      int t_len, const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks, float* d_x,
+                                      void* stream);
 DMME_API int dmme_unet_plan_grad_buckets(const dmme_plan* plan, int64_t* offsets, int64_t* numels, int* bucket_of, int cap);
 /* test / diagnostic: the kernels a backward of this plan launches, as space-separated key=value pairs
  * ("wgrad_group3x3_jobs=..", "colsum_group_jobs=..", "dgrad[conv3x3_ws2_kernel<11>]=..") */
@@ -346,12 +361,38 @@ DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64
  * the offset advances all the same (the reference draws and discards, diffusion_models/ddpm.py:107-110).  After the update the
  * state moves on: i -= 1, t = t_table[i], offset += B*chw/4.  dmme_chain_step = dmme_unet_forward at t = state.t followed by
  * dmme_chain_update; x is updated in place, model_out receives the network output.  chw must be a multiple of 4. */
-enum { DMME_CHAIN_DDPM = 0, DMME_CHAIN_DDIM = 1, DMME_CHAIN_IDDPM = 2 };
+enum { DMME_CHAIN_DDPM = 0, DMME_CHAIN_DDIM = 1, DMME_CHAIN_IDDPM = 2, DMME_CHAIN_DDPM_GUIDED = 3, DMME_CHAIN_DDIM_GUIDED = 4 };
 DMME_API int dmme_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t philox_seed, uint64_t philox_offset, void* stream);
 DMME_API int dmme_chain_update(int kind, float* x, const float* model_out, const float* step_coef, const int64_t* t_table, void* state,
                       int B, int64_t chw, void* stream);
 DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
                     const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
+/* ---- classifier guidance (Dhariwal & Nichol 2021, Algorithms 1 and 2; the reference's src/dmme/guidance/classifier.py sketch) ----
+ * dmme_log_softmax_grad: row-wise log-softmax of logits (B, K) fp32 against int64 labels y[B].
+ *   mode 0 (training): loss[0] = mean_i -log p(y_i | x_i); d_logits = scale * (softmax_i - onehot(y_i)) / B
+ *   mode 1 (guidance): loss[0] = sum_i log p(y_i | x_i);   d_logits = scale * (onehot(y_i) - softmax_i), the gradient of
+ *                      scale * sum_i log p(y_i | x_i, t), row by row (no label of one image reaches another's row).
+ *   loss / d_logits nullable.  A label outside [0, K) is never used as an index: its row and loss[0] become NaN and *status
+ *   (nullable, device int) is set to 1 (the host reads it when it can synchronise; the argument check cannot see device labels).
+ * dmme_chain_update_guided: the chain update of DMME_CHAIN_DDPM_GUIDED / DMME_CHAIN_DDIM_GUIDED with grad = d log p(y | x_t, t) / d x_t:
+ *   DDPM_GUIDED step_coef {1/sqrt(alpha_t), beta_t/sqrt(1-abar_t), sqrt(beta_t), s*beta_t}:
+ *               x = mean + s*beta_t*grad (+ sqrt(beta_t) z, not at t == 1: the mean shift stays)
+ *   DDIM_GUIDED step_coef {sqrt(1-abar_tau_i), sqrt(abar_tau_{i-1}), s*sqrt(1-abar_tau_i), -}:
+ *               eps' = eps - s*sqrt(1-abar_tau_i)*grad, then the DDIM update with eps'
+ *   The Philox stream is consumed exactly as by the unguided kinds; noise (nullable) replaces the drawn normals (tests).
+ * dmme_guided_chain_step: one capturable guided step: the UNet's no-grad forward at t = state.t -> model_out; the classifier's
+ *   forward (the form a backward follows) at the same device-resident t -> logits; dmme_log_softmax_grad mode 1 (scale 1) against
+ *   y -> d_logits; dmme_unet_backward_input -> grad; dmme_chain_update_guided.  Both plans have the same B, H, W; cls is a
+ *   DMME_ARCH_CLASSIFIER plan, kind DMME_CHAIN_DDPM_GUIDED or DMME_CHAIN_DDIM_GUIDED.  status: as above (nullable). */
+DMME_API int dmme_log_softmax_grad(const float* logits, const int64_t* y, int B, int K, int mode, float scale, float* loss, float* d_logits,
+                                   int* status, void* stream);
+DMME_API int dmme_chain_update_guided(int kind, float* x, const float* model_out, const float* grad, const float* noise, const float* step_coef,
+                                      const int64_t* t_table, void* state, int B, int64_t chw, void* stream);
+DMME_API int dmme_guided_chain_step(const dmme_plan* plan, const void* packed, const dmme_plan* cls, const void* cls_packed,
+                                    const void* cls_packed_bwd, float* x, float* model_out, void* workspace, void* cls_workspace,
+                                    void* cls_bwd_workspace, const int64_t* y, float* logits, float* d_logits, float* grad, int* status,
+                                    int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
