@@ -9,7 +9,7 @@ before the timed region.  With --gpus N every rank runs its own independent batc
 (sampling shards with no data-path collective: weak scaling).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sample|ddim|train|cpu-plumbing] [--precision bf16|fp16|bf16x3|fp32]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
 
 K is the number of timed steps in all, run back to back and timed in --reps blocks; `ms_per_step` is the median block's time
 per step.  --dump-outputs writes what the timed path computed in its last step (sampling: the images x_{t-1} and the UNet's
@@ -18,8 +18,10 @@ arguments give equal inputs.
 
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment starts its N ranks itself
 (`python -m torch.distributed.run`, before this process touches the GPU) and relays rank 0's line.
-Prints ONE JSON line (rank 0) carrying `roofline` (dominant kernel, measured live with HIP events
-on the launch stream) and `cpu_baseline` (the CPU oracle timed on this host's cores, rank 0, N=1).
+Prints ONE JSON line (rank 0).  A plain run measures the headline alone: set-up, warm-up, the timed steps, --dump-outputs, the
+line.  --full adds everything else after the timed steps: `roofline` (dominant kernel, measured live with HIP events on the launch
+stream), `cpu_baseline` (the CPU oracle timed on this host's cores, rank 0, N=1), `box_mfma_tfps`, the accurate-precision, DDIM
+batch-512 and small-batch legs and the training leg (at N > 1 with its data-parallel figures).
 """
 
 import argparse
@@ -57,14 +59,16 @@ def parse():
     ap.add_argument("--model", default="ddpm", choices=["ddpm", "iddpm64"],
                     help="ddpm: BASELINE configs[1]/[2] (default UNet, 32x32); iddpm64: configs[3] (IDDPM ImageNet-64 UNet, attention at "
                          "16x16/8x8, cosine schedule, T=4000; use --batch 32 for the 256-over-8-GPUs shard)")
-    ap.add_argument("--train-steps", type=int, default=30, help="training steps timed for train_images_per_s (0: skip)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else the line can carry (roofline, CPU baseline, "
+                                                       "MFMA calibration, other precisions / batch sizes, the training leg); off: the headline alone")
+    ap.add_argument("--train-steps", type=int, default=None, help="--full: training steps timed for train_images_per_s (default 30; 0: skip)")
     ap.add_argument("--no-graph", action="store_true", help="issue the step's launches eagerly instead of replaying the captured hipGraph")
     ap.add_argument("--graph", action="store_true", help=argparse.SUPPRESS)  # accepted for older command lines: the graph is the default now
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-accurate-leg", action="store_true", help="skip the short bf16x3 (accurate mode) and fp16 throughput legs")
-    ap.add_argument("--no-small-batch-leg", action="store_true", help="skip the batch-1 / batch-32 legs of the N = 1 line")
-    ap.add_argument("--no-ddim-leg", action="store_true", help="skip the BASELINE configs[2] leg (DDIM 50 steps, batch 512) of the N = 1 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel roofline")
+    ap.add_argument("--no-accurate-leg", action="store_true", help="--full: skip the short bf16x3 (accurate mode) and fp16 throughput legs")
+    ap.add_argument("--no-small-batch-leg", action="store_true", help="--full: skip the batch-1 / batch-32 legs of the N = 1 line")
+    ap.add_argument("--no-ddim-leg", action="store_true", help="--full: skip the BASELINE configs[2] leg (DDIM 50 steps, batch 512) of the N = 1 line")
     ap.add_argument("--config", default=None, help="cpu-plumbing: the LightningCLI YAML to drive (default configs/ddpm/cifar10.yaml)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; rank 0's "
@@ -75,6 +79,10 @@ def parse():
     args.warmup = (0 if cpu else 10) if args.warmup is None else args.warmup
     if args.steps < 1 or args.warmup < 0 or args.reps < 1:
         ap.error("--steps and --reps must be at least 1, --warmup at least 0")
+    if args.train_steps is None:
+        args.train_steps = 30 if args.full else 0
+    elif args.train_steps > 0 and not args.full:
+        ap.error("--train-steps: the training leg runs with --full only")
     return args
 
 
@@ -599,13 +607,14 @@ def main():
         "train_images_per_s": None,
         "launches_per_step": int(runner.plan.lib.dmme_unet_plan_num_launches(runner.plan.h)) + 1,
         "hip_graph": bool(runner.graph is not None),
-        "box_mfma_tfps": mfma_calibration(dev),
     }
+    if args.full:
+        out["box_mfma_tfps"] = mfma_calibration(dev)
 
     plan = runner.plan
 
     def rank0_legs():  # the per-kernel roofline of the measured forward and the CPU baseline
-        if rank == 0:
+        if rank == 0 and args.full:
             if not args.no_roofline:
                 xin = dmme_amd.gaussian((B, 3, side, side), device=dev)
                 model._last_plan = plan
@@ -619,7 +628,7 @@ def main():
         fp16 with the full-resolution level in fp32 tensors and three-pass split-fp16 products - max|err| 6-7e-4, INSIDE north_star's 1e-3),
         precision="bf16x3" (fp32 tensors everywhere, three bf16 passes - 1.7e-5) and precision="fp16" (IEEE half, the reference's own AMP
         dtype, same kernels and rate as bf16 - 1.5e-3)"""
-        if args.no_accurate_leg or args.precision != "bf16" or args.model != "ddpm" or args.mode != "sample":
+        if not args.full or args.no_accurate_leg or args.precision != "bf16" or args.model != "ddpm" or args.mode != "sample":
             return
         for key, prec in (("accurate_mode", "fp16r32"), ("bf16x3_mode", "bf16x3"), ("fp16_mode", "fp16")):
             if prec not in dmme_amd._lib.DTYPES:
@@ -651,7 +660,7 @@ def main():
 
     def ddim_leg():
         """BASELINE configs[2] as a secondary key of the N = 1 line: DDIM, 50-step quadratic tau, batch 512, the full chain once"""
-        if args.no_ddim_leg or world != 1 or args.precision != "bf16" or args.model != "ddpm" or args.mode != "sample":
+        if not args.full or args.no_ddim_leg or world != 1 or args.precision != "bf16" or args.model != "ddpm" or args.mode != "sample":
             return
         try:
             torch.manual_seed(1337)
@@ -670,7 +679,7 @@ def main():
 
     def small_batch_leg():
         """the same captured step at batch 1 and batch 32 (the launch-bound end of `DDPM.generate`), secondary keys of the N = 1 line"""
-        if args.no_small_batch_leg or world != 1 or args.precision != "bf16" or args.model != "ddpm" or args.mode != "sample" or B != 128:
+        if not args.full or args.no_small_batch_leg or world != 1 or args.precision != "bf16" or args.model != "ddpm" or args.mode != "sample" or B != 128:
             return
         out["small_batch"] = {}
         for bs in (1, 32):

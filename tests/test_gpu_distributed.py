@@ -139,7 +139,7 @@ def test_bench_two_ranks_on_one_device_reports_both_exchanges():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--reps", "1", "--batch", "16", "--train-steps", "2",
-           "--no-cpu-baseline", "--no-roofline", "--no-accurate-leg", "--no-ddim-leg", "--no-small-batch-leg"]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-accurate-leg", "--no-ddim-leg", "--no-small-batch-leg"]
     for attempt in range(2):  # (the launcher's rendezvous port is picked, released and re-bound: one retry for that race; the first failure is printed)
         res = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
         lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
@@ -172,7 +172,7 @@ def test_bench_two_ranks_exits_nonzero_when_an_exchange_leg_fails():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reps", "1", "--batch", "8", "--train-steps", "1",
-           "--no-cpu-baseline", "--no-roofline", "--no-accurate-leg", "--no-ddim-leg", "--no-small-batch-leg"]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-accurate-leg", "--no-ddim-leg", "--no-small-batch-leg"]
     res = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
     assert lines and res.returncode != 0, (res.returncode, res.stdout[-1000:], res.stderr[-1000:])

@@ -390,6 +390,28 @@ def test_bench_defaults_and_rank_launcher_command(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "4", "--steps", "7"]
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_other_legs(monkeypatch):
+    """a plain `python bench.py` runs no training leg; --full runs it (30 steps unless --train-steps says otherwise), and
+    --train-steps without --full is refused rather than ignored"""
+    import importlib
+    import sys as _sys
+
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.train_steps == 0 and a.steps == 5 and a.warmup == 2
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and a.train_steps == 30
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--full", "--train-steps", "0"])
+    assert bench.parse().train_steps == 0
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--train-steps", "0"])
+    assert bench.parse().train_steps == 0
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--train-steps", "5"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_bench_cpu_plumbing_mode_runs_the_reference_yaml_on_the_oracle():
     """BASELINE configs[0]: `python bench.py --mode cpu-plumbing` - the shipped YAML through the product's parser and constructors, ten
     sampling steps and two training steps at batch 1 in the CPU oracle, ONE JSON line with finite numbers (no GPU involved)"""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # After `gpurun -- bash tools/round_profiles.sh <tag>`: condense gpurun_out/prof_<tag>* into the tracked files under profiles/.
-# usage: bash tools/collect_round.sh r04
+# usage: bash tools/collect_round.sh r04 [bench line dir, as given to round_profiles.sh]
 set -e
 TAG=${1:-r04}
 cd "$(dirname "$0")/.."
@@ -14,5 +14,5 @@ cp "$(newest "gpurun_out/prof_${TAG}it_stats/*/*kernel_stats.csv")" profiles/${T
 cp "$(newest "gpurun_out/prof_${TAG}x_stats/*/*kernel_stats.csv")" profiles/${TAG}_sample_b128_bf16x3_kernel_stats.csv
 cp "$(newest "gpurun_out/prof_${TAG}r_stats/*/*kernel_stats.csv")" profiles/${TAG}_sample_b128_fp16r32_kernel_stats.csv
 cp "$(newest "gpurun_out/prof_${TAG}th_stats/*/*kernel_stats.csv")" profiles/${TAG}_train_b128_fp16_kernel_stats.csv
-for f in gpurun_out/${TAG}_bench_*.json; do [ -s "$f" ] && cp "$f" profiles/; done
+for f in ${2:-bench_lines}/${TAG}_bench_*.json; do [ -s "$f" ] && cp "$f" profiles/; done  # round_profiles.sh wrote them there
 ls -la profiles/${TAG}_* | awk '{print $5, $9}'
