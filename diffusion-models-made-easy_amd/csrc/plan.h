@@ -1,5 +1,6 @@
-// Shared definitions of the plan translation units (plan.hip: layer graph, layouts, forward; plan_lvl.hip: level-engine planning
-// and status; plan_bwd.hip: backward pass, gradient buckets): the plan's data model and the helpers that cross those files.
+// Shared definitions of the plan translation units (plan.hip: layer graph, layouts, plan creation and its device tables, forward;
+// plan_lvl.hip: level-engine planning and status; plan_bwd.hip: backward planning - gradient buckets, deferred tables - and the
+// backward pass): the plan's data model and the helpers that cross those files.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>
@@ -7,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -17,6 +19,50 @@
 namespace dmme {
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// A table in device memory that frees itself (on whatever device is current then): what a plan allocated, deleting the plan frees.
+template <typename T>
+class DevTable {
+    T* p_ = nullptr;
+
+public:
+    DevTable() = default;
+    DevTable(const DevTable&) = delete;
+    DevTable& operator=(const DevTable&) = delete;
+    DevTable(DevTable&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }  // (its holders live in std::vectors)
+    ~DevTable() { if (p_) (void)hipFree(p_); }
+    int upload(const std::vector<T>& v) {  // (an empty table stays null)
+        if (v.empty()) return DMME_OK;
+        DMME_CHECK_HIP(hipMalloc((void**)&p_, v.size() * sizeof(T)));
+        DMME_CHECK_HIP(hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return DMME_OK;
+    }
+    int zeroed(size_t n) {
+        DMME_CHECK_HIP(hipMalloc((void**)&p_, n * sizeof(T)));
+        DMME_CHECK_HIP(hipMemset(p_, 0, n * sizeof(T)));
+        return DMME_OK;
+    }
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+
+// The plan's status word: pinned host memory the device writes through its mapping, freed with the plan.
+class PinnedWord {
+    unsigned* p_ = nullptr;
+
+public:
+    PinnedWord() = default;
+    PinnedWord(const PinnedWord&) = delete;
+    PinnedWord& operator=(const PinnedWord&) = delete;
+    ~PinnedWord() { if (p_) (void)hipHostFree(p_); }
+    int alloc() {
+        DMME_CHECK_HIP(hipHostMalloc((void**)&p_, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(p_, 0, 64);
+        return DMME_OK;
+    }
+    unsigned* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
 
 struct Param {
     std::string name;
@@ -110,13 +156,13 @@ struct LvlRun {
     int sh = 0, NG = 0, NGS = 0, GB = 1, NJ = 1;
     std::vector<LvlOp> ops;
     std::vector<std::pair<int, int>> made;  // (tensor id, index of the op that produces / normalises it): later runs attach norms there
-    LvlOp* ops_dev = nullptr;
+    DevTable<LvlOp> ops_dev;
     // the op table of forwards no backward pass follows (run_op's keep_ctx == false): convs whose RAW output no forward op reads - a
     // ResBlock's conv1 (only its norm's pre-activated copy is read), the qkv slices kept in LDS - do not store it (assign_lvl_nograd)
     std::vector<LvlOp> ops_nograd;
-    LvlOp* ops_nograd_dev = nullptr;
+    DevTable<LvlOp> ops_nograd_dev;
     int raw_skipped = 0;
-    unsigned* sync_dev = nullptr;   // [16] control words (epoch, done, error), then the flag rows [n_ops * 2][NG][LVL_NS]
+    DevTable<unsigned> sync_dev;    // [16] control words (epoch, done, error), then the flag rows [n_ops * 2][NG][LVL_NS]
     double flops = 0, bytes = 0;
 };
 
@@ -147,7 +193,7 @@ struct dmme_plan {
     int tproj_cols = 0;
     int64_t tproj_w_off = 0, tproj_b_off = 0;  // packed byte offsets of the concatenated projection
     int freqs_param = -1;
-    PackItem* items_dev = nullptr;
+    DevTable<PackItem> items_dev;
     int n_items = 0;
     int n_launches = 0;
     // ---- training (backward) ----
@@ -157,20 +203,20 @@ struct dmme_plan {
     int64_t packed_bwd_bytes = 0, bws_bytes = 0;
     std::vector<int64_t> gt_off;           // gradient buffer of every forward tensor
     int64_t bws_zero = 0, bws_zero_bytes = 0, bws_wimage = 0, bws_gnS = 0, bws_zpage = 0;  // region cleared once per backward
-    PackItem* items_unpack_dev = nullptr;
+    DevTable<PackItem> items_unpack_dev;
     int n_items_unpack = 0;
     int64_t bws_sink = 0, sink_half = 0;  // input-only backward: where the GroupNorm backward's (unused) d gamma / d beta go (2 x sink_half floats)
     int64_t bws_tmp = 0, bws_dy = 0, bws_rowsum = 0, bws_dtproj = 0, bws_dtemb = 0, bws_dh1 = 0, bws_z = 0, bws_wT = 0, bws_attP = 0,
             bws_attdS = 0;
-    PackItem* items_bwd_dev = nullptr;
+    DevTable<PackItem> items_bwd_dev;
     int n_items_bwd = 0;
     // grouped weight gradients (one launch per backward)
     struct WgGroup {
         int taps = 0;
         std::vector<WgLayer> layers;
         std::vector<WgJob> jobs;
-        WgLayer* layers_dev = nullptr;
-        WgJob* jobs_dev = nullptr;
+        DevTable<WgLayer> layers_dev;
+        DevTable<WgJob> jobs_dev;
         int dma = 0;  // every layer's second operand is one prologue-free tensor: the LDS-DMA kernel runs the table
         int stride = 1;
     } wg[3];  // 3x3, 1x1, 3x3 stride 2 (LDS-DMA kernel only)
@@ -189,20 +235,21 @@ struct dmme_plan {
     std::vector<GradBucket> gb;                            // empty: no clean cut for this configuration (one piece)
     // batched time-projection gradients: destination (float offset into grad_flat) of every 64-row tile of
     // dtproj^T temb, then of every 32-column tile of the bias sums
-    int64_t* tp_tiles_dev = nullptr;
+    std::vector<int64_t> tp_tiles;  // (empty: a block width is no multiple of 64 - per-block launches)
+    DevTable<int64_t> tp_tiles_dev;
     int tp_n64 = 0;
     // deferred bias / time-projection reductions (one launch per backward)
     std::vector<BiasJob> bias_jobs;
-    BiasJob* bias_jobs_dev = nullptr;
+    DevTable<BiasJob> bias_jobs_dev;
     std::vector<ColJob> col_jobs;     // column sums of dY of every bias-deferred conv: one grouped launch per flush
-    ColJob* col_jobs_dev = nullptr;
+    DevTable<ColJob> col_jobs_dev;
     std::vector<LvlRun> lvl_runs;     // level-engine launches (small maps)
     // every workgroup of an engine launch must be resident at once: grids are sized by what the device holds (assign_levels)
     int lvl_max_wg = LVL_MAX_WG;
     // host-visible status word (pinned, device-mapped; null: plan without a device): non-zero = 1 + index of an engine run in which a
     // bounded hand-off wait timed out, or kErrNogradBackward (a backward found the no-grad form's mark): the outputs since are invalid
     // (lvl_check)
-    unsigned* err_host = nullptr;
+    PinnedWord err_host;
     // the workspace the last forward wrote WITHOUT the tensors only a backward pass reads (dmme_unet_forward_nograd, dmme_chain_step):
     // dmme_unet_backward refuses it instead of differentiating stale activations (null: the last forward kept everything)
     mutable const void* nograd_ws = nullptr;
@@ -229,7 +276,9 @@ void assign_rseg(dmme_plan* P);
 int run_level(const dmme_plan* P, const LvlRun& R, const char* pk, char* ws, int nt, const float* drop_masks, hipStream_t s, bool keep_ctx = true);
 void assign_lvl_nograd(dmme_plan* P);
 int lvl_check(const dmme_plan* P, const char* where, hipStream_t stream = nullptr, bool have_stream = false);
-// plan_bwd.hip: the grouped (deferred) weight-gradient tables of ops [op_lo, op_hi)
-void build_wgrad_group(dmme_plan* P, dmme_plan::WgGroup& G, int gi, int op_lo = 0, int op_hi = 1 << 30);
+// plan.hip: the weight-gradient image's unpack table, in parameter order (the gradient buckets cut it)
+void build_unpack_items(const dmme_plan* P, std::vector<PackItem>& items);
+// plan_bwd.hip: everything a backward of this plan is decided by at plan time (host arithmetic: plans without a device run it too)
+void plan_backward(dmme_plan* P);
 
 }  // namespace dmme

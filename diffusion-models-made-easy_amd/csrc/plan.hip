@@ -631,18 +631,16 @@ static void push_pack_items(const Param& p, int64_t dst_off, int as_f32, bool wi
         }
 }
 
-int build_pack_items(dmme_plan* P, std::vector<PackItem>& items) {
+void build_pack_items(const dmme_plan* P, std::vector<PackItem>& items) {
     for (const Param& p : P->params) push_pack_items(p, p.packed_off, p.pack_code >= 0 ? p.pack_code : p.as_f32 ? 1 : 0, false, items);
-    return DMME_OK;
 }
 
-int build_pack_items_bwd(dmme_plan* P, std::vector<PackItem>& items) {
+void build_pack_items_bwd(const dmme_plan* P, std::vector<PackItem>& items) {
     for (const Param& p : P->params)
         if (p.packed_bwd_off >= 0) push_pack_items(p, p.packed_bwd_off, 2, true, items);
-    return DMME_OK;
 }
 
-int build_unpack_items(dmme_plan* P, std::vector<PackItem>& items) {
+void build_unpack_items(const dmme_plan* P, std::vector<PackItem>& items) {
     const int64_t CHUNK = 16384;
     for (const Param& p : P->params) {
         if (p.wp_off < 0) continue;
@@ -664,7 +662,6 @@ int build_unpack_items(dmme_plan* P, std::vector<PackItem>& items) {
             items.push_back(it);
         }
     }
-    return DMME_OK;
 }
 
 // ---- which kernel runs a convolution -----------------------------------------------------------------------------------------------
@@ -1297,6 +1294,101 @@ void op_account(const dmme_plan* P, const Op& o, char* label, int cap, double* f
     }
 }
 
+
+// ---- plan creation, phase by phase (dmme_unet_plan_create) -------------------------------------------------------------------------
+static int check_cfg(const dmme_unet_cfg* cfg, int B, int H, int W, int dtype) {
+    DMME_REQUIRE(B > 0 && H > 0 && W > 0, DMME_ERR_INVALID, "plan_create: bad shape B=%d H=%d W=%d", B, H, W);
+    DMME_REQUIRE(dtype == DMME_F32 || dtype == DMME_BF16 || dtype == DMME_BF16X3 || dtype == DMME_F16 || dtype == DMME_F16R32, DMME_ERR_INVALID,
+                 "plan_create: bad dtype %d", dtype);
+    DMME_REQUIRE(cfg->num_depths >= 1 && cfg->num_depths <= 8 && cfg->num_blocks >= 1, DMME_ERR_INVALID,
+                 "plan_create: bad depth/blocks");
+    DMME_REQUIRE(cfg->num_attention_depths >= 0 && cfg->num_attention_depths <= 8, DMME_ERR_INVALID, "bad attention_depths");
+    DMME_REQUIRE(cfg->pos_dim >= 4 && cfg->pos_dim % 2 == 0, DMME_ERR_INVALID, "pos_dim must be even and >= 4");
+    DMME_REQUIRE(cfg->arch == DMME_ARCH_DDPM || cfg->arch == DMME_ARCH_IDDPM || cfg->arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+                 "plan_create: unknown arch %d", cfg->arch);
+    if (cfg->arch == DMME_ARCH_CLASSIFIER) {
+        const bool x3 = dtype == DMME_BF16X3, mix = dtype == DMME_F16R32;
+        DMME_REQUIRE(!x3 && !mix, DMME_ERR_UNSUPPORTED, "plan_create: the classifier runs in fp32, bf16 or fp16 (not %s)", x3 ? "bf16x3" : "fp16r32");
+        DMME_REQUIRE(cfg->num_classes >= 1, DMME_ERR_INVALID, "plan_create: classifier num_classes=%d", cfg->num_classes);
+        DMME_REQUIRE(cfg->channels_per_depth[cfg->num_depths - 1] <= 1024, DMME_ERR_UNSUPPORTED, "plan_create: classifier head wider than 1024 channels");
+    }
+    if (cfg->arch == DMME_ARCH_IDDPM) {
+        DMME_REQUIRE(cfg->num_heads >= 1, DMME_ERR_INVALID, "plan_create: num_heads must be >= 1");
+    }
+    for (int d = 0; d < cfg->num_depths; ++d)
+        DMME_REQUIRE(cfg->channels_per_depth[d] > 0 && cfg->channels_per_depth[d] % cfg->num_groups == 0,
+                     DMME_ERR_INVALID, "channels_per_depth[%d]=%d not divisible by num_groups=%d", d,
+                     cfg->channels_per_depth[d], cfg->num_groups);
+    return DMME_OK;
+}
+
+// precision fp16r32: every conv of the fp32 level must have its kernel - there is no fall-back to a 16-bit path that would read fp32 as halves
+static int check_mix_kernels(const dmme_plan* P) {
+    if (!P->mix) return DMME_OK;
+    for (const Op& o : P->ops) {
+        if (o.kind != OP_CONV || !(o.mix || o.route_f32)) continue;
+        ConvArgs a{};
+        fill_conv(P, o, (const char*)4096, (const float*)4096, (float*)4096, (char*)4096, nullptr, 1, a);
+        const bool ok = o.mix == 3 ? conv_out_thin_supported(P->dtype, a) : o.mix == 4 ? conv1x1_pipe_supported(P->dtype, a) : o.mix ? conv_pipe_supported(P->dtype, a) : true;
+        DMME_REQUIRE(ok, DMME_ERR_UNSUPPORTED, "plan_create: precision fp16r32 has no kernel for the %dx%d conv %d+%d -> %d channels on the %dx%d level (B = %d)",
+                     o.taps == 9 ? 3 : 1, o.taps == 9 ? 3 : 1, a.C1, a.C2, a.Cout, a.Hout, a.Wout, P->B);
+    }
+    return DMME_OK;
+}
+
+static int count_launches(const dmme_plan* P) {
+    int n = 0;
+    for (const Op& o : P->ops) {
+        if (o.fused_away) continue;
+        if (o.lvl >= 0)
+            n += o.lvl_first;
+        else if (o.kind == OP_GN)
+            n += !(o.gn_direct || o.gn_in_consumer);
+        else
+            ++n;
+    }
+    return n;
+}
+
+#define DMME_TRY(expr)                 \
+    do {                               \
+        if (int rc_ = (expr)) return rc_; \
+    } while (0)
+
+// every table a device plan keeps on its device, and the pinned status word
+static int upload_tables(dmme_plan* P) {
+    DMME_CHECK_HIP(hipSetDevice(P->device));
+    std::vector<PackItem> items, bitems, uitems;
+    build_pack_items(P, items);
+    build_pack_items_bwd(P, bitems);
+    build_unpack_items(P, uitems);
+    P->n_items = (int)items.size();
+    P->n_items_bwd = (int)bitems.size();
+    P->n_items_unpack = (int)uitems.size();
+    DMME_TRY(P->items_dev.upload(items));
+    DMME_TRY(P->items_bwd_dev.upload(bitems));
+    DMME_TRY(P->items_unpack_dev.upload(uitems));
+    DMME_TRY(P->tp_tiles_dev.upload(P->tp_tiles));
+    DMME_TRY(P->col_jobs_dev.upload(P->col_jobs));
+    DMME_TRY(P->bias_jobs_dev.upload(P->bias_jobs));
+    std::vector<dmme_plan::WgGroup*> all_groups{&P->wg[0], &P->wg[1], &P->wg[2]};
+    for (auto& B_ : P->gb)
+        for (int k = 0; k < 3; ++k) all_groups.push_back(&B_.wg[k]);
+    for (dmme_plan::WgGroup* G : all_groups) {
+        if (G->jobs.empty()) continue;
+        DMME_TRY(G->layers_dev.upload(G->layers));
+        DMME_TRY(G->jobs_dev.upload(G->jobs));
+    }
+    // (every device plan: the backward reports a no-grad forward's workspace through this word too)
+    DMME_TRY(P->err_host.alloc());
+    for (LvlRun& R : P->lvl_runs) {
+        DMME_TRY(R.ops_dev.upload(R.ops));
+        if (R.raw_skipped > 0) DMME_TRY(R.ops_nograd_dev.upload(R.ops_nograd));
+        DMME_TRY(R.sync_dev.zeroed(16 + R.ops.size() * 2 * (size_t)R.NG * LVL_NS));
+    }
+    return DMME_OK;
+}
+
 }  // namespace dmme
 
 // ======================================================================== extern "C"
@@ -1312,61 +1404,19 @@ DMME_API int dmme_device_count(void) {
 
 DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W, int dtype, int device, dmme_plan** out) {
     DMME_REQUIRE(cfg && out, DMME_ERR_INVALID, "plan_create: null argument");
-    DMME_REQUIRE(B > 0 && H > 0 && W > 0, DMME_ERR_INVALID, "plan_create: bad shape B=%d H=%d W=%d", B, H, W);
-    DMME_REQUIRE(dtype == DMME_F32 || dtype == DMME_BF16 || dtype == DMME_BF16X3 || dtype == DMME_F16 || dtype == DMME_F16R32, DMME_ERR_INVALID,
-                 "plan_create: bad dtype %d", dtype);
-    const int x3 = dtype == DMME_BF16X3;
-    if (x3) dtype = DMME_F32;
-    const int mix = dtype == DMME_F16R32;
-    if (mix) {
-        dtype = DMME_F16;  // (both architectures: the check below refuses a configuration whose fp32 level has a conv without a kernel)
-    }
-    DMME_REQUIRE(cfg->num_depths >= 1 && cfg->num_depths <= 8 && cfg->num_blocks >= 1, DMME_ERR_INVALID,
-                 "plan_create: bad depth/blocks");
-    DMME_REQUIRE(cfg->num_attention_depths >= 0 && cfg->num_attention_depths <= 8, DMME_ERR_INVALID, "bad attention_depths");
-    DMME_REQUIRE(cfg->pos_dim >= 4 && cfg->pos_dim % 2 == 0, DMME_ERR_INVALID, "pos_dim must be even and >= 4");
-    DMME_REQUIRE(cfg->arch == DMME_ARCH_DDPM || cfg->arch == DMME_ARCH_IDDPM || cfg->arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
-                 "plan_create: unknown arch %d", cfg->arch);
-    if (cfg->arch == DMME_ARCH_CLASSIFIER) {
-        DMME_REQUIRE(!x3 && !mix, DMME_ERR_UNSUPPORTED, "plan_create: the classifier runs in fp32, bf16 or fp16 (not %s)", x3 ? "bf16x3" : "fp16r32");
-        DMME_REQUIRE(cfg->num_classes >= 1, DMME_ERR_INVALID, "plan_create: classifier num_classes=%d", cfg->num_classes);
-        DMME_REQUIRE(cfg->channels_per_depth[cfg->num_depths - 1] <= 1024, DMME_ERR_UNSUPPORTED, "plan_create: classifier head wider than 1024 channels");
-    }
-    if (cfg->arch == DMME_ARCH_IDDPM) {
-        DMME_REQUIRE(cfg->num_heads >= 1, DMME_ERR_INVALID, "plan_create: num_heads must be >= 1");
-    }
-    for (int d = 0; d < cfg->num_depths; ++d)
-        DMME_REQUIRE(cfg->channels_per_depth[d] > 0 && cfg->channels_per_depth[d] % cfg->num_groups == 0,
-                     DMME_ERR_INVALID, "channels_per_depth[%d]=%d not divisible by num_groups=%d", d,
-                     cfg->channels_per_depth[d], cfg->num_groups);
-    dmme_plan* P = new dmme_plan();
+    DMME_TRY(check_cfg(cfg, B, H, W, dtype));
+    std::unique_ptr<dmme_plan> owned(new dmme_plan());  // (a failed create frees the plan and, through their types, its tables)
+    dmme_plan* P = owned.get();
     P->cfg = *cfg;
     P->B = B;
     P->H = H;
     P->W = W;
-    P->dtype = dtype;
-    P->x3 = x3;
-    P->mix = mix;
+    P->x3 = dtype == DMME_BF16X3;   // fp32 storage
+    P->mix = dtype == DMME_F16R32;  // fp16 storage below the full-resolution level
+    P->dtype = P->x3 ? DMME_F32 : P->mix ? DMME_F16 : dtype;
     P->device = device;
-    int rc = build_plan(P);
-    if (rc != DMME_OK) {
-        delete P;
-        return rc;
-    }
-    if (P->mix) {  // every conv of the fp32 level must have its kernel: there is no fall-back to a 16-bit path that would read fp32 as halves
-        for (const Op& o : P->ops) {
-            if (o.kind != OP_CONV || !(o.mix || o.route_f32)) continue;
-            ConvArgs a{};
-            fill_conv(P, o, (const char*)4096, (const float*)4096, (float*)4096, (char*)4096, nullptr, 1, a);
-            const bool ok = o.mix == 3 ? conv_out_thin_supported(P->dtype, a) : o.mix == 4 ? conv1x1_pipe_supported(P->dtype, a) : o.mix ? conv_pipe_supported(P->dtype, a) : true;
-            if (!ok) {
-                set_error("plan_create: precision fp16r32 has no kernel for the %dx%d conv %d+%d -> %d channels on the %dx%d level (B = %d)", o.taps == 9 ? 3 : 1,
-                          o.taps == 9 ? 3 : 1, a.C1, a.C2, a.Cout, a.Hout, a.Wout, B);
-                delete P;
-                return DMME_ERR_UNSUPPORTED;
-            }
-        }
-    }
+    DMME_TRY(build_plan(P));
+    DMME_TRY(check_mix_kernels(P));
     assign_levels(P);
     if (!getenv("DMME_NO_FUSED_GN")) assign_stats(P);
     if (!getenv("DMME_NO_FUSED_GN") && !getenv("DMME_NO_GN_DIRECT")) assign_direct(P);
@@ -1375,310 +1425,14 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
     assign_rseg(P);
     assign_attn_proj(P);
     assign_lvl_nograd(P);
-    P->n_launches = 0;
-    for (const Op& o : P->ops) {
-        if (o.fused_away) continue;
-        if (o.lvl >= 0)
-            P->n_launches += o.lvl_first;
-        else if (o.kind == OP_GN)
-            P->n_launches += !(o.gn_direct || o.gn_in_consumer);
-        else
-            ++P->n_launches;
-    }
-    if (device >= 0) {
-        // ---- gradient buckets: cuts at ResBlock starts (a block's first op is the GroupNorm of its conv1), walked in backward order
-        std::vector<int> owner(P->params.size(), -1);  // op index that produces each parameter's gradient (-1: the time MLP, at the very end)
-        for (int oi = 0; oi < (int)P->ops.size(); ++oi) {
-            const Op& o = P->ops[oi];
-            if (o.kind == OP_CONV) {
-                owner[o.w] = oi;
-                owner[o.b] = oi;
-            } else if (o.kind == OP_GN) {
-                owner[o.gn_gamma] = oi;
-                owner[o.gn_beta] = oi;
-            }
-        }
-        std::vector<int> tcol_owner(P->tblocks.size(), -1);
-        for (size_t k = 0; k < P->tblocks.size(); ++k) {
-            const auto& tb = P->tblocks[k];
-            for (int oi = 0; oi < (int)P->ops.size(); ++oi) {
-                const Op& o = P->ops[oi];
-                if ((o.kind == OP_CONV && o.tproj_col == tb.col) || (o.kind == OP_GN && o.gn_mod_col == tb.col)) tcol_owner[k] = oi;
-            }
-            if (tcol_owner[k] >= 0) owner[tb.tw] = owner[tb.tb] = tcol_owner[k];
-        }
-        {
-            int64_t total = 0;
-            for (size_t pi = 0; pi < P->params.size(); ++pi)
-                if (!P->params[pi].is_buffer) total += P->params[pi].numel();
-            // block starts: a GroupNorm op whose consumer conv carries a time projection (DDPM) or that is followed by one (IDDPM conv1),
-            // i.e. the first op of a ResBlock; also bare down / up convs.  Simpler and sufficient: any OP_GN whose source is not produced by
-            // the op right before it inside the same block - approximated by "conv1's norm": the norm of a conv with tproj_col >= 0 (DDPM)
-            // or the norm two ops ahead of a modulated norm (IDDPM).
-            std::vector<char> is_start(P->ops.size(), 0);
-            for (int oi = 0; oi < (int)P->ops.size(); ++oi) {
-                const Op& o = P->ops[oi];
-                if (o.kind != OP_CONV || o.gn < 0) continue;
-                const bool conv1 = P->cfg.arch == DMME_ARCH_IDDPM ? (oi + 1 < (int)P->ops.size() && P->ops[oi + 1].kind == OP_GN && P->ops[oi + 1].gn_mod_col >= 0) : o.tproj_col >= 0;
-                if (conv1) is_start[o.gn] = 1;
-            }
-            const int n_target = debug_route("grad_buckets", 6);
-            // candidates: block starts with the fraction of the parameters backward has finished when the walk reaches them
-            std::vector<std::pair<int, double>> cand;
-            {
-                int64_t acc = 0;
-                for (int oi = (int)P->ops.size() - 1; oi > 0; --oi) {
-                    for (size_t pi = 0; pi < P->params.size(); ++pi)
-                        if (owner[pi] == oi && !P->params[pi].is_buffer) acc += P->params[pi].numel();
-                    if (is_start[oi]) cand.push_back({oi, (double)acc / (double)(total > 0 ? total : 1)});
-                }
-            }
-            std::vector<int> cuts{(int)P->ops.size()};
-            if (n_target > 1 && !cand.empty()) {
-                // the last cut first: what is left behind it (first down blocks, input conv, time MLP) is the one exchange no compute
-                // hides - as close to 12 % of the bytes as the block boundaries allow
-                int last = -1;
-                double best = 1e9;
-                for (int k = 0; k < (int)cand.size(); ++k) {
-                    const double rest = 1.0 - cand[k].second;
-                    if (rest < 0.04) continue;
-                    const double d = rest > 0.12 ? rest - 0.12 : 2.0 * (0.12 - rest);
-                    if (d < best) { best = d; last = k; }
-                }
-                if (last >= 0) {
-                    // the others: the block boundary nearest to each multiple of (what is in front of the last cut) / (n - 1)
-                    const double step = cand[last].second / (double)(n_target - 1);
-                    int prev_k = -1;
-                    for (int q = 1; q < n_target - 1; ++q) {
-                        int pick = -1;
-                        double bd = 1e9;
-                        for (int k = prev_k + 1; k < last; ++k) {
-                            const double d = cand[k].second > q * step ? cand[k].second - q * step : q * step - cand[k].second;
-                            if (d < bd) { bd = d; pick = k; }
-                        }
-                        if (pick < 0) break;
-                        cuts.push_back(cand[pick].first);
-                        prev_k = pick;
-                    }
-                    cuts.push_back(cand[last].first);
-                }
-            }
-            cuts.push_back(0);
-            bool clean = cuts.size() > 2 && !getenv("DMME_NO_GRAD_BUCKETS") && P->cfg.arch != DMME_ARCH_CLASSIFIER;  // (no buckets for the classifier)
-            if (clean) {
-                P->gb.resize(cuts.size() - 1);
-                for (size_t b = 0; b + 1 < cuts.size(); ++b) {
-                    dmme_plan::GradBucket& G = P->gb[b];
-                    G.op_hi = cuts[b];
-                    G.op_lo = cuts[b + 1];
-                    const bool last = b + 2 == cuts.size();
-                    std::vector<std::pair<int64_t, int64_t>> r;
-                    for (size_t pi = 0; pi < P->params.size(); ++pi) {
-                        const Param& pp = P->params[pi];  // (the sinusoid table, a buffer without gradient, rides in the last bucket: the
-                                                          // hand-overs then tile the whole flat buffer)
-                        const bool mine = owner[pi] < 0 ? last : (owner[pi] >= G.op_lo && owner[pi] < G.op_hi);
-                        if (!mine) continue;
-                        if (!r.empty() && r.back().first + r.back().second == pp.ref_off) r.back().second += pp.numel();
-                        else r.push_back({pp.ref_off, pp.numel()});
-                    }
-                    G.ranges = r;
-                    for (size_t k = 0; k < P->tblocks.size(); ++k) {
-                        if (tcol_owner[k] < G.op_lo || tcol_owner[k] >= G.op_hi) continue;
-                        const int c0 = P->tblocks[k].col, c1 = c0 + P->tblocks[k].cout;
-                        if (!G.tcols.empty() && G.tcols.back().second == c0) G.tcols.back().second = c1;
-                        else G.tcols.push_back({c0, c1});
-                    }
-                    // (the tiled time-projection gradient addresses 64-column tiles: it exists only when every block's width is a
-                    // multiple of 64, and then so is every range start)
-                }
-                for (size_t k = 0; k < P->tblocks.size(); ++k)
-                    if (tcol_owner[k] < 0) clean = false;
-            }
-            if (!clean) P->gb.clear();
-        }
-        for (auto& G : P->gb)  // before the "all" build: that one leaves the final Op::wg_layer values
-            for (int k = 0; k < 3; ++k) build_wgrad_group(P, G.wg[k], k, G.op_lo, G.op_hi);
-        for (int k = 0; k < 3; ++k) build_wgrad_group(P, P->wg[k], k);
-        std::vector<int> bias_job_op, col_job_op;  // op index each job belongs to (gradient buckets)
-        if (!debug_route("no_bias_group"))
-            for (Op& o : P->ops) {
-                if (o.kind != OP_CONV) continue;
-                const int o_index = (int)(&o - P->ops.data());
-                ConvArgs a{};
-                fill_conv(P, o, nullptr, nullptr, nullptr, nullptr, nullptr, 1, a);
-                if (o.gn >= 0 && o.b_gnrows >= 0) {
-                    // the norm in front of this conv: its backward leaves per-image dbeta / dgamma rows, summed over the batch by the same
-                    // grouped launch as the biases.  Bucket (gradient exchange overlap): by the NORM's op index, its jobs first.
-                    const Op& gop = P->ops[o.gn];
-                    const Tensor& t1 = P->tensors[gop.gn_src1];
-                    const int C1 = t1.C, C2 = gop.gn_src2 >= 0 ? P->tensors[gop.gn_src2].C : 0, C = C1 + C2;
-                    if (gn_bwd_fast_supported(P->dtype, t1.H * t1.W, C1, C2) &&
-                        gn_bwd_rows_supported(P->dtype, t1.H * t1.W, C1, C2, P->cfg.num_groups, gop.gn_mod_col >= 0)) {
-                        o.gn_rows_deferred = 1;
-                        for (int which = 0; which < 2; ++which)
-                            for (int cb = 0; cb < (C + 31) / 32; ++cb) {
-                                BiasJob j{};
-                                j.rowsum_off = o.b_gnrows + (int64_t)which * P->B * C * 4;
-                                j.dbias_off = P->params[which == 0 ? gop.gn_beta : gop.gn_gamma].ref_off;
-                                j.C = C;
-                                j.cblock = cb;
-                                j.tcol = -1;
-                                P->bias_jobs.push_back(j);
-                                bias_job_op.push_back(o.gn);
-                            }
-                    }
-                }
-                if (!colsum_fast_supported(P->dtype, a.Hout * a.Wout, a.Cout)) continue;
-                o.bias_deferred = 1;
-                if (!debug_route("no_colsum_group")) {
-                    ColJob cj{};
-                    const int nch = colsum_group_chunks(P->dtype, a.Hout * a.Wout, a.Cout, &cj.chunk_px, &cj.ppw);
-                    cj.dy_off = o.dst == -2 ? P->bws_dy : P->gt_off[o.dst];
-                    cj.rowsum_off = o.b_rowsum;
-                    cj.HW = a.Hout * a.Wout;
-                    cj.C = a.Cout;
-                    for (int ch = 0; ch < nch; ++ch) {
-                        cj.chunk = ch;
-                        P->col_jobs.push_back(cj);
-                        col_job_op.push_back(o_index);
-                    }
-                }
-                for (int cb = 0; cb < (a.Cout + 31) / 32; ++cb) {
-                    BiasJob j{};
-                    j.rowsum_off = o.b_rowsum;
-                    j.dbias_off = P->params[o.b].ref_off;
-                    j.C = a.Cout;
-                    j.cblock = cb;
-                    j.tcol = o.tproj_col;
-                    P->bias_jobs.push_back(j);
-                    bias_job_op.push_back(o_index);
-                }
-            }
-        for (auto& G : P->gb) {  // jobs were pushed in ascending op order: a bucket's jobs are one index range
-            auto range = [&](const std::vector<int>& ops_of, int& j0, int& j1) {
-                j0 = j1 = 0;
-                bool any = false, ok = true;
-                for (int j = 0; j < (int)ops_of.size(); ++j) {
-                    if (ops_of[j] < G.op_lo || ops_of[j] >= G.op_hi) continue;
-                    if (!any) { j0 = j; any = true; } else if (j != j1) ok = false;
-                    j1 = j + 1;
-                }
-                return ok;
-            };
-            if (!range(bias_job_op, G.bias0, G.bias1) || !range(col_job_op, G.col0, G.col1)) {
-                P->gb.clear();
-                break;
-            }
-        }
-    }
-    if (device >= 0) {
-        std::vector<PackItem> items;
-        build_pack_items(P, items);
-        P->n_items = (int)items.size();
-        hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = hipMalloc((void**)&P->items_dev, items.size() * sizeof(PackItem));
-        if (e == hipSuccess) e = hipMemcpy(P->items_dev, items.data(), items.size() * sizeof(PackItem), hipMemcpyHostToDevice);
-        std::vector<PackItem> bitems;
-        build_pack_items_bwd(P, bitems);
-        P->n_items_bwd = (int)bitems.size();
-        if (e == hipSuccess) e = hipMalloc((void**)&P->items_bwd_dev, bitems.size() * sizeof(PackItem));
-        if (e == hipSuccess) e = hipMemcpy(P->items_bwd_dev, bitems.data(), bitems.size() * sizeof(PackItem), hipMemcpyHostToDevice);
-        std::vector<PackItem> uitems;
-        build_unpack_items(P, uitems);
-        P->n_items_unpack = (int)uitems.size();
-        if (e == hipSuccess) e = hipMalloc((void**)&P->items_unpack_dev, uitems.size() * sizeof(PackItem));
-        if (e == hipSuccess) e = hipMemcpy(P->items_unpack_dev, uitems.data(), uitems.size() * sizeof(PackItem), hipMemcpyHostToDevice);
-        {
-            bool ok = !P->tblocks.empty() && P->tproj_cols % 64 == 0;
-            for (const auto& tb : P->tblocks) ok = ok && tb.cout % 64 == 0 && tb.col % 64 == 0;
-            if (ok) {
-                std::vector<int64_t> tiles(P->tproj_cols / 64 + P->tproj_cols / 32, -1);
-                const int n64 = P->tproj_cols / 64;
-                for (const auto& tb : P->tblocks) {
-                    for (int r = 0; r < tb.cout; r += 64) tiles[(tb.col + r) / 64] = P->params[tb.tw].ref_off + (int64_t)r * P->cfg.emb_dim;
-                    for (int r = 0; r < tb.cout; r += 32) tiles[n64 + (tb.col + r) / 32] = P->params[tb.tb].ref_off + r;
-                }
-                for (int64_t v : tiles) ok = ok && v >= 0;
-                if (ok) {
-                    if (e == hipSuccess) e = hipMalloc((void**)&P->tp_tiles_dev, tiles.size() * sizeof(int64_t));
-                    if (e == hipSuccess) e = hipMemcpy(P->tp_tiles_dev, tiles.data(), tiles.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-                    P->tp_n64 = n64;
-                }
-            }
-        }
-        if (!P->col_jobs.empty()) {
-            if (e == hipSuccess) e = hipMalloc((void**)&P->col_jobs_dev, P->col_jobs.size() * sizeof(ColJob));
-            if (e == hipSuccess) e = hipMemcpy(P->col_jobs_dev, P->col_jobs.data(), P->col_jobs.size() * sizeof(ColJob), hipMemcpyHostToDevice);
-        }
-        if (!P->bias_jobs.empty()) {
-            if (e == hipSuccess) e = hipMalloc((void**)&P->bias_jobs_dev, P->bias_jobs.size() * sizeof(BiasJob));
-            if (e == hipSuccess) e = hipMemcpy(P->bias_jobs_dev, P->bias_jobs.data(), P->bias_jobs.size() * sizeof(BiasJob), hipMemcpyHostToDevice);
-        }
-        std::vector<dmme_plan::WgGroup*> all_groups{&P->wg[0], &P->wg[1], &P->wg[2]};
-        for (auto& B_ : P->gb)
-            for (int k = 0; k < 3; ++k) all_groups.push_back(&B_.wg[k]);
-        for (dmme_plan::WgGroup* G : all_groups) {
-            if (G->jobs.empty()) continue;
-            if (e == hipSuccess) e = hipMalloc((void**)&G->layers_dev, G->layers.size() * sizeof(WgLayer));
-            if (e == hipSuccess) e = hipMemcpy(G->layers_dev, G->layers.data(), G->layers.size() * sizeof(WgLayer), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMalloc((void**)&G->jobs_dev, G->jobs.size() * sizeof(WgJob));
-            if (e == hipSuccess) e = hipMemcpy(G->jobs_dev, G->jobs.data(), G->jobs.size() * sizeof(WgJob), hipMemcpyHostToDevice);
-        }
-        // (every device plan: the backward reports a no-grad forward's workspace through this word too)
-        if (e == hipSuccess) e = hipHostMalloc((void**)&P->err_host, 64, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) memset(P->err_host, 0, 64);
-        for (LvlRun& R : P->lvl_runs) {
-            const size_t words = 16 + R.ops.size() * 2 * (size_t)R.NG * LVL_NS;
-            if (e == hipSuccess) e = hipMalloc((void**)&R.ops_dev, R.ops.size() * sizeof(LvlOp));
-            if (e == hipSuccess) e = hipMemcpy(R.ops_dev, R.ops.data(), R.ops.size() * sizeof(LvlOp), hipMemcpyHostToDevice);
-            if (e == hipSuccess && R.raw_skipped > 0) {
-                e = hipMalloc((void**)&R.ops_nograd_dev, R.ops_nograd.size() * sizeof(LvlOp));
-                if (e == hipSuccess) e = hipMemcpy(R.ops_nograd_dev, R.ops_nograd.data(), R.ops_nograd.size() * sizeof(LvlOp), hipMemcpyHostToDevice);
-            }
-            if (e == hipSuccess) e = hipMalloc((void**)&R.sync_dev, words * 4);
-            if (e == hipSuccess) e = hipMemset(R.sync_dev, 0, words * 4);
-        }
-        for (auto& G : P->gb)  // unpack items follow the parameter order: a bucket's items are the runs inside its flat ranges
-            for (int i = 0; i < (int)uitems.size(); ++i) {
-                bool mine = false;
-                for (auto& r : G.ranges) mine = mine || (uitems[i].src_off >= r.first && uitems[i].src_off < r.first + r.second);
-                if (!mine) continue;
-                if (!G.unpack.empty() && G.unpack.back().second == i) G.unpack.back().second = i + 1;
-                else G.unpack.push_back({i, i + 1});
-            }
-        if (e != hipSuccess) {
-            set_error("plan_create: device table setup failed: %s", hipGetErrorString(e));
-            delete P;
-            return DMME_ERR_HIP;
-        }
-    }
-    *out = P;
+    P->n_launches = count_launches(P);
+    plan_backward(P);
+    if (device >= 0) DMME_TRY(upload_tables(P));
+    *out = owned.release();
     return DMME_OK;
 }
 
-DMME_API void dmme_unet_plan_destroy(dmme_plan* plan) {
-    if (!plan) return;
-    if (plan->items_dev) (void)hipFree(plan->items_dev);
-    if (plan->items_bwd_dev) (void)hipFree(plan->items_bwd_dev);
-    if (plan->items_unpack_dev) (void)hipFree(plan->items_unpack_dev);
-    std::vector<dmme_plan::WgGroup*> all_groups{&plan->wg[0], &plan->wg[1], &plan->wg[2]};
-    for (auto& B_ : plan->gb)
-        for (int k = 0; k < 3; ++k) all_groups.push_back(&B_.wg[k]);
-    for (dmme_plan::WgGroup* G : all_groups) {
-        if (G->layers_dev) (void)hipFree(G->layers_dev);
-        if (G->jobs_dev) (void)hipFree(G->jobs_dev);
-    }
-    if (plan->tp_tiles_dev) (void)hipFree(plan->tp_tiles_dev);
-    if (plan->bias_jobs_dev) (void)hipFree(plan->bias_jobs_dev);
-    if (plan->col_jobs_dev) (void)hipFree(plan->col_jobs_dev);
-    if (plan->err_host) (void)hipHostFree(plan->err_host);
-    for (LvlRun& R : plan->lvl_runs) {
-        if (R.ops_dev) (void)hipFree(R.ops_dev);
-        if (R.ops_nograd_dev) (void)hipFree(R.ops_nograd_dev);
-        if (R.sync_dev) (void)hipFree(R.sync_dev);
-    }
-    delete plan;
-}
+DMME_API void dmme_unet_plan_destroy(dmme_plan* plan) { delete plan; }
 
 DMME_API int dmme_unet_plan_num_params(const dmme_plan* plan) { return plan ? (int)plan->params.size() : 0; }
 
@@ -1708,7 +1462,7 @@ DMME_API int dmme_unet_plan_num_launches(const dmme_plan* plan) { return plan ? 
 DMME_API int dmme_unet_pack_params(const dmme_plan* plan, const float* ref_flat, void* packed, void* stream) {
     DMME_REQUIRE(plan && ref_flat && packed, DMME_ERR_INVALID, "pack_params: null argument");
     DMME_REQUIRE(plan->items_dev, DMME_ERR_INVALID, "pack_params: plan was created without a device");
-    return launch_pack_table(plan->dtype, plan->items_dev, plan->n_items, ref_flat, packed, (hipStream_t)stream);
+    return launch_pack_table(plan->dtype, plan->items_dev.get(), plan->n_items, ref_flat, packed, (hipStream_t)stream);
 }
 
 static int unet_forward_impl(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len,

@@ -1,5 +1,6 @@
-// Backward side of the plan: the grouped weight-gradient tables, the reverse walk over the op list (data gradients through the
-// forward kernels, GroupNorm / attention / time-MLP backward), gradient buckets for the overlapped data-parallel exchange.
+// Backward side of the plan.  Planning (plan_backward, host arithmetic): gradient buckets for the overlapped data-parallel exchange,
+// the grouped weight-gradient tables, the deferred bias / column-sum jobs, the tiled time-projection gradient.  Execution: the reverse
+// walk over the op list (data gradients through the forward kernels, GroupNorm / attention / time-MLP backward).
 #include "plan.h"
 
 using namespace dmme;
@@ -8,7 +9,7 @@ namespace dmme {
 
 // Grouped weight gradients: every 3x3 stride-1 conv the all-taps MFMA kernel supports is taken out of the per-layer
 // sequence; its (cout tile, cin tile) pairs are cut into jobs of at most `q` consecutive 64-pixel tiles, longest first.
-void build_wgrad_group(dmme_plan* P, dmme_plan::WgGroup& G, int gi, int op_lo, int op_hi) {
+static void build_wgrad_group(dmme_plan* P, dmme_plan::WgGroup& G, int gi, int op_lo = 0, int op_hi = 1 << 30) {
     const int taps = gi == 1 ? 1 : 9, stride = gi == 2 ? 2 : 1;
     G.taps = taps;
     G.stride = stride;
@@ -112,6 +113,222 @@ void build_wgrad_group(dmme_plan* P, dmme_plan::WgGroup& G, int gi, int op_lo, i
         }
 }
 
+// Gradient buckets: the op list cut at ResBlock starts, walked in backward order (dmme_plan::GradBucket).  Leaves P->gb empty where
+// there is no clean cut.
+static void plan_grad_buckets(dmme_plan* P) {
+    if (getenv("DMME_NO_GRAD_BUCKETS") || P->cfg.arch == DMME_ARCH_CLASSIFIER) return;  // (the classifier's gradients are not exchanged)
+    const int nO = (int)P->ops.size();
+    std::vector<int> owner(P->params.size(), -1);  // op index that produces each parameter's gradient (-1: the time MLP, at the very end)
+    for (int oi = 0; oi < nO; ++oi) {
+        const Op& o = P->ops[oi];
+        if (o.kind == OP_CONV) {
+            owner[o.w] = oi;
+            owner[o.b] = oi;
+        } else if (o.kind == OP_GN) {
+            owner[o.gn_gamma] = oi;
+            owner[o.gn_beta] = oi;
+        }
+    }
+    std::vector<int> tcol_owner(P->tblocks.size(), -1);
+    for (size_t k = 0; k < P->tblocks.size(); ++k) {
+        const auto& tb = P->tblocks[k];
+        for (int oi = 0; oi < nO; ++oi) {
+            const Op& o = P->ops[oi];
+            if ((o.kind == OP_CONV && o.tproj_col == tb.col) || (o.kind == OP_GN && o.gn_mod_col == tb.col)) tcol_owner[k] = oi;
+        }
+        if (tcol_owner[k] < 0) return;  // a time projection nothing reads: no clean cut
+        owner[tb.tw] = owner[tb.tb] = tcol_owner[k];
+    }
+    int64_t total = 0;
+    for (const Param& p : P->params)
+        if (!p.is_buffer) total += p.numel();
+    // A block starts at the GroupNorm in front of its conv1.  DDPM: conv1 is the conv that carries the time projection.  IDDPM: conv1
+    // is the conv that the modulated (scale-shift) GroupNorm follows directly.
+    std::vector<char> is_start(nO, 0);
+    for (int oi = 0; oi < nO; ++oi) {
+        const Op& o = P->ops[oi];
+        if (o.kind != OP_CONV || o.gn < 0) continue;
+        const bool conv1 = P->cfg.arch == DMME_ARCH_IDDPM ? (oi + 1 < nO && P->ops[oi + 1].kind == OP_GN && P->ops[oi + 1].gn_mod_col >= 0) : o.tproj_col >= 0;
+        if (conv1) is_start[o.gn] = 1;
+    }
+    const int n_target = debug_route("grad_buckets", 6);
+    // candidates: block starts with the fraction of the parameters backward has finished when the walk reaches them
+    std::vector<std::pair<int, double>> cand;
+    int64_t acc = 0;
+    for (int oi = nO - 1; oi > 0; --oi) {
+        for (size_t pi = 0; pi < P->params.size(); ++pi)
+            if (owner[pi] == oi && !P->params[pi].is_buffer) acc += P->params[pi].numel();
+        if (is_start[oi]) cand.push_back({oi, (double)acc / (double)(total > 0 ? total : 1)});
+    }
+    std::vector<int> cuts{nO};
+    if (n_target > 1 && !cand.empty()) {
+        // the last cut first: what is left behind it (first down blocks, input conv, time MLP) is the one exchange no compute
+        // hides - as close to 12 % of the bytes as the block boundaries allow
+        int last = -1;
+        double best = 1e9;
+        for (int k = 0; k < (int)cand.size(); ++k) {
+            const double rest = 1.0 - cand[k].second;
+            if (rest < 0.04) continue;
+            const double d = rest > 0.12 ? rest - 0.12 : 2.0 * (0.12 - rest);
+            if (d < best) { best = d; last = k; }
+        }
+        if (last >= 0) {
+            // the others: the block boundary nearest to each multiple of (what is in front of the last cut) / (n - 1)
+            const double step = cand[last].second / (double)(n_target - 1);
+            int prev_k = -1;
+            for (int q = 1; q < n_target - 1; ++q) {
+                int pick = -1;
+                double bd = 1e9;
+                for (int k = prev_k + 1; k < last; ++k) {
+                    const double d = cand[k].second > q * step ? cand[k].second - q * step : q * step - cand[k].second;
+                    if (d < bd) { bd = d; pick = k; }
+                }
+                if (pick < 0) break;
+                cuts.push_back(cand[pick].first);
+                prev_k = pick;
+            }
+            cuts.push_back(cand[last].first);
+        }
+    }
+    cuts.push_back(0);
+    if (cuts.size() <= 2) return;
+    std::vector<PackItem> uitems;
+    build_unpack_items(P, uitems);
+    P->gb.resize(cuts.size() - 1);
+    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
+        dmme_plan::GradBucket& G = P->gb[b];
+        G.op_hi = cuts[b];
+        G.op_lo = cuts[b + 1];
+        const bool last = b + 2 == cuts.size();
+        for (size_t pi = 0; pi < P->params.size(); ++pi) {
+            const Param& pp = P->params[pi];  // (the sinusoid table, a buffer without gradient, rides in the last bucket: the
+                                              // hand-overs then tile the whole flat buffer)
+            const bool mine = owner[pi] < 0 ? last : (owner[pi] >= G.op_lo && owner[pi] < G.op_hi);
+            if (!mine) continue;
+            if (!G.ranges.empty() && G.ranges.back().first + G.ranges.back().second == pp.ref_off) G.ranges.back().second += pp.numel();
+            else G.ranges.push_back({pp.ref_off, pp.numel()});
+        }
+        // (the tiled time-projection gradient addresses 64-column tiles: it exists only when every block's width is a multiple of
+        // 64, and then so is every range start)
+        for (size_t k = 0; k < P->tblocks.size(); ++k) {
+            if (tcol_owner[k] < G.op_lo || tcol_owner[k] >= G.op_hi) continue;
+            const int c0 = P->tblocks[k].col, c1 = c0 + P->tblocks[k].cout;
+            if (!G.tcols.empty() && G.tcols.back().second == c0) G.tcols.back().second = c1;
+            else G.tcols.push_back({c0, c1});
+        }
+        // unpack items follow the parameter order: a bucket's items are the runs inside its flat ranges
+        for (int i = 0; i < (int)uitems.size(); ++i) {
+            bool mine = false;
+            for (auto& r : G.ranges) mine = mine || (uitems[i].src_off >= r.first && uitems[i].src_off < r.first + r.second);
+            if (!mine) continue;
+            if (!G.unpack.empty() && G.unpack.back().second == i) G.unpack.back().second = i + 1;
+            else G.unpack.push_back({i, i + 1});
+        }
+    }
+}
+
+// Deferred reductions (one grouped launch each per backward or per bucket): the bias / time-projection rows of every conv, the
+// per-image dbeta / dgamma rows of the GroupNorm in front of it, the column sums of dY; then every bucket's index range of each table.
+static void plan_deferred_reductions(dmme_plan* P) {
+    std::vector<int> bias_job_op, col_job_op;  // op index each job belongs to (gradient buckets)
+    if (!debug_route("no_bias_group"))
+        for (Op& o : P->ops) {
+            if (o.kind != OP_CONV) continue;
+            const int o_index = (int)(&o - P->ops.data());
+            ConvArgs a{};
+            fill_conv(P, o, nullptr, nullptr, nullptr, nullptr, nullptr, 1, a);
+            if (o.gn >= 0 && o.b_gnrows >= 0) {
+                // the norm in front of this conv: its backward leaves per-image dbeta / dgamma rows, summed over the batch by the same
+                // grouped launch as the biases.  Bucket (gradient exchange overlap): by the NORM's op index, its jobs first.
+                const Op& gop = P->ops[o.gn];
+                const Tensor& t1 = P->tensors[gop.gn_src1];
+                const int C1 = t1.C, C2 = gop.gn_src2 >= 0 ? P->tensors[gop.gn_src2].C : 0, C = C1 + C2;
+                if (gn_bwd_fast_supported(P->dtype, t1.H * t1.W, C1, C2) &&
+                    gn_bwd_rows_supported(P->dtype, t1.H * t1.W, C1, C2, P->cfg.num_groups, gop.gn_mod_col >= 0)) {
+                    o.gn_rows_deferred = 1;
+                    for (int which = 0; which < 2; ++which)
+                        for (int cb = 0; cb < (C + 31) / 32; ++cb) {
+                            BiasJob j{};
+                            j.rowsum_off = o.b_gnrows + (int64_t)which * P->B * C * 4;
+                            j.dbias_off = P->params[which == 0 ? gop.gn_beta : gop.gn_gamma].ref_off;
+                            j.C = C;
+                            j.cblock = cb;
+                            j.tcol = -1;
+                            P->bias_jobs.push_back(j);
+                            bias_job_op.push_back(o.gn);
+                        }
+                }
+            }
+            if (!colsum_fast_supported(P->dtype, a.Hout * a.Wout, a.Cout)) continue;
+            o.bias_deferred = 1;
+            if (!debug_route("no_colsum_group")) {
+                ColJob cj{};
+                const int nch = colsum_group_chunks(P->dtype, a.Hout * a.Wout, a.Cout, &cj.chunk_px, &cj.ppw);
+                cj.dy_off = o.dst == -2 ? P->bws_dy : P->gt_off[o.dst];
+                cj.rowsum_off = o.b_rowsum;
+                cj.HW = a.Hout * a.Wout;
+                cj.C = a.Cout;
+                for (int ch = 0; ch < nch; ++ch) {
+                    cj.chunk = ch;
+                    P->col_jobs.push_back(cj);
+                    col_job_op.push_back(o_index);
+                }
+            }
+            for (int cb = 0; cb < (a.Cout + 31) / 32; ++cb) {
+                BiasJob j{};
+                j.rowsum_off = o.b_rowsum;
+                j.dbias_off = P->params[o.b].ref_off;
+                j.C = a.Cout;
+                j.cblock = cb;
+                j.tcol = o.tproj_col;
+                P->bias_jobs.push_back(j);
+                bias_job_op.push_back(o_index);
+            }
+        }
+    for (auto& G : P->gb) {  // jobs were pushed in ascending op order: a bucket's jobs are one index range
+        auto range = [&](const std::vector<int>& ops_of, int& j0, int& j1) {
+            j0 = j1 = 0;
+            bool any = false, ok = true;
+            for (int j = 0; j < (int)ops_of.size(); ++j) {
+                if (ops_of[j] < G.op_lo || ops_of[j] >= G.op_hi) continue;
+                if (!any) { j0 = j; any = true; } else if (j != j1) ok = false;
+                j1 = j + 1;
+            }
+            return ok;
+        };
+        if (!range(bias_job_op, G.bias0, G.bias1) || !range(col_job_op, G.col0, G.col1)) {
+            P->gb.clear();
+            break;
+        }
+    }
+}
+
+// Batched time-projection gradients (dmme_plan::tp_tiles): where every block's width and column are multiples of 64.
+static void plan_time_proj_tiles(dmme_plan* P) {
+    bool ok = !P->tblocks.empty() && P->tproj_cols % 64 == 0;
+    for (const auto& tb : P->tblocks) ok = ok && tb.cout % 64 == 0 && tb.col % 64 == 0;
+    if (!ok) return;
+    const int n64 = P->tproj_cols / 64;
+    std::vector<int64_t> tiles(n64 + P->tproj_cols / 32, -1);
+    for (const auto& tb : P->tblocks) {
+        for (int r = 0; r < tb.cout; r += 64) tiles[(tb.col + r) / 64] = P->params[tb.tw].ref_off + (int64_t)r * P->cfg.emb_dim;
+        for (int r = 0; r < tb.cout; r += 32) tiles[n64 + (tb.col + r) / 32] = P->params[tb.tb].ref_off + r;
+    }
+    for (int64_t v : tiles)
+        if (v < 0) return;
+    P->tp_tiles = tiles;
+    P->tp_n64 = n64;
+}
+
+void plan_backward(dmme_plan* P) {
+    plan_grad_buckets(P);
+    for (auto& G : P->gb)  // before the "all" build: that one leaves the final Op::wg_layer values (and grows bws_bytes)
+        for (int k = 0; k < 3; ++k) build_wgrad_group(P, G.wg[k], k, G.op_lo, G.op_hi);
+    for (int k = 0; k < 3; ++k) build_wgrad_group(P, P->wg[k], k);
+    plan_deferred_reductions(P);
+    plan_time_proj_tiles(P);
+}
+
 }  // namespace dmme
 
 extern "C" {
@@ -122,7 +339,7 @@ DMME_API int64_t dmme_unet_plan_bwd_workspace_bytes(const dmme_plan* plan) { ret
 DMME_API int dmme_unet_pack_params_bwd(const dmme_plan* plan, const float* ref_flat, void* packed_bwd, void* stream) {
     DMME_REQUIRE(plan && ref_flat && packed_bwd, DMME_ERR_INVALID, "pack_params_bwd: null argument");
     DMME_REQUIRE(plan->items_bwd_dev, DMME_ERR_INVALID, "pack_params_bwd: plan was created without a device");
-    return launch_pack_table(plan->dtype, plan->items_bwd_dev, plan->n_items_bwd, ref_flat, packed_bwd, (hipStream_t)stream);
+    return launch_pack_table(plan->dtype, plan->items_bwd_dev.get(), plan->n_items_bwd, ref_flat, packed_bwd, (hipStream_t)stream);
 }
 
 static int backward_impl(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t, int t_len,
@@ -175,8 +392,8 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
     auto pgrad = [&](int param, int which) -> float* { return weights ? grad_flat + P->params[param].ref_off : sink + which * P->sink_half; };
     // (the first launch: it checks the device-side mark of the forward form, which a replayed no-grad graph sets without the host seeing it)
     // classifier: d_y is d logits (B, K) fp32 - copied as is (HW = 1, fp32) through the same mark check
-    int rc = P->head_src >= 0 ? launch_nchw_to_nhwc(DMME_F32, d_y, B, P->out_channels, 1, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host)
-                              : launch_nchw_to_nhwc(dt, d_y, B, P->out_channels, P->H * P->W, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host);
+    int rc = P->head_src >= 0 ? launch_nchw_to_nhwc(DMME_F32, d_y, B, P->out_channels, 1, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host.get())
+                              : launch_nchw_to_nhwc(dt, d_y, B, P->out_channels, P->H * P->W, bws + P->bws_dy, s, (const unsigned*)(ws + P->ws_mark), P->err_host.get());
     if (rc != DMME_OK) return rc;
     if (P->head_src >= 0) {  // the head: d logits -> d(top map), written whole; its parameters' gradients (weights form only)
         const Tensor& tt = P->tensors[P->head_src];
@@ -202,24 +419,24 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
         const dmme_plan::GradBucket* GBk = b >= 0 ? &P->gb[b] : nullptr;
         if (P->bias_jobs_dev && P->col_jobs_dev) {
             const int j0 = GBk ? GBk->col0 : 0, j1 = GBk ? GBk->col1 : (int)P->col_jobs.size();
-            if (j1 > j0) r = launch_colsum_group(dt, P->col_jobs_dev + j0, j1 - j0, bws, B, s);
+            if (j1 > j0) r = launch_colsum_group(dt, P->col_jobs_dev.get() + j0, j1 - j0, bws, B, s);
             if (r != DMME_OK) return r;
         }
         if (P->bias_jobs_dev) {
             const int j0 = GBk ? GBk->bias0 : 0, j1 = GBk ? GBk->bias1 : (int)P->bias_jobs.size();
-            if (j1 > j0) r = launch_bias_tproj_group(P->bias_jobs_dev + j0, j1 - j0, bws, grad_flat, dtproj, B, tc, nt, s);
+            if (j1 > j0) r = launch_bias_tproj_group(P->bias_jobs_dev.get() + j0, j1 - j0, bws, grad_flat, dtproj, B, tc, nt, s);
             if (r != DMME_OK) return r;
         }
         for (int k = 0; k < 3; ++k) {
             const dmme_plan::WgGroup& G = GBk ? GBk->wg[k] : P->wg[k];
             if (!G.jobs_dev) continue;
-            r = launch_wgrad_group(dt, G.taps, G.layers_dev, G.jobs_dev, (int)G.jobs.size(), ws, bws, drop_masks, wimage, s, G.dma, bws + P->bws_zpage);
+            r = launch_wgrad_group(dt, G.taps, G.layers_dev.get(), G.jobs_dev.get(), (int)G.jobs.size(), ws, bws, drop_masks, wimage, s, G.dma, bws + P->bws_zpage);
             if (r != DMME_OK) return r;
         }
         {
             std::vector<std::pair<int, int>> all_items{{0, P->n_items_unpack}};
             for (const auto& ir : (GBk ? GBk->unpack : all_items)) {
-                if (ir.second > ir.first) r = launch_wgrad_unpack(P->items_unpack_dev + ir.first, ir.second - ir.first, wimage, grad_flat, s);
+                if (ir.second > ir.first) r = launch_wgrad_unpack(P->items_unpack_dev.get() + ir.first, ir.second - ir.first, wimage, grad_flat, s);
                 if (r != DMME_OK) return r;
             }
         }
@@ -228,8 +445,8 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
             const int c0 = cr.first, c1 = cr.second;
             if (c1 <= c0) continue;
             if (P->tp_tiles_dev) {  // every block's dW / db in one launch each
-                r = launch_small_gemm_tn_tiled(dtproj + c0, tc, temb, emb, c1 - c0, emb, nt, grad_flat, emb, P->tp_tiles_dev + c0 / 64, s);
-                if (r == DMME_OK) r = launch_nsum_tiled(dtproj + c0, nt, c1 - c0, tc, 1, grad_flat, P->tp_tiles_dev + P->tp_n64 + c0 / 32, s);
+                r = launch_small_gemm_tn_tiled(dtproj + c0, tc, temb, emb, c1 - c0, emb, nt, grad_flat, emb, P->tp_tiles_dev.get() + c0 / 64, s);
+                if (r == DMME_OK) r = launch_nsum_tiled(dtproj + c0, nt, c1 - c0, tc, 1, grad_flat, P->tp_tiles_dev.get() + P->tp_n64 + c0 / 32, s);
                 if (r != DMME_OK) return r;
             } else {
                 for (const auto& tb : P->tblocks) {

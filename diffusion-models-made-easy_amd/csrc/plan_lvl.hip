@@ -331,7 +331,7 @@ void assign_levels(dmme_plan* P) {
                             P->ops[ci].use_act = 1;
                         }
                 }
-                P->lvl_runs.push_back(R);
+                P->lvl_runs.push_back(std::move(R));
             }
         }
         i = j;
@@ -396,7 +396,7 @@ static int g_lvl_stamp_run = -1, g_lvl_stamp_wg = 0;
 int run_level(const dmme_plan* P, const LvlRun& R, const char* pk, char* ws, int nt, const float* drop_masks, hipStream_t s, bool keep_ctx) {
     DMME_REQUIRE(R.ops_dev && R.sync_dev, DMME_ERR_INVALID, "level engine: the plan was created without a device");
     LvlArgs a{};
-    a.ops = (!keep_ctx && R.ops_nograd_dev) ? R.ops_nograd_dev : R.ops_dev;
+    a.ops = (!keep_ctx && R.ops_nograd_dev) ? R.ops_nograd_dev.get() : R.ops_dev.get();
     a.n_ops = (int)R.ops.size();
     a.ws = ws;
     a.packed = pk;
@@ -410,9 +410,9 @@ int run_level(const dmme_plan* P, const LvlRun& R, const char* pk, char* ws, int
     a.NGS = R.NGS;
     a.GB = R.GB;
     a.NJ = R.NJ;
-    a.ctl = R.sync_dev;
-    a.flags = R.sync_dev + 16;
-    a.err_sys = P->err_host;
+    a.ctl = R.sync_dev.get();
+    a.flags = R.sync_dev.get() + 16;
+    a.err_sys = P->err_host.get();
     a.run_tag = 1 + (int)(&R - P->lvl_runs.data());
     a.spin_limit = debug_route("lvl_spin", 0);
     a.withhold = debug_route("lvl_withhold", 0);
@@ -431,7 +431,7 @@ int run_level(const dmme_plan* P, const LvlRun& R, const char* pk, char* ws, int
 // replay a captured graph (no entry point runs then): no path hands results on with rc 0 once the word is set.
 int lvl_check(const dmme_plan* P, const char* where, hipStream_t stream, bool have_stream) {
     if (!P->err_host) return DMME_OK;
-    const unsigned v = __atomic_load_n(P->err_host, __ATOMIC_ACQUIRE);
+    const unsigned v = __atomic_load_n(P->err_host.get(), __ATOMIC_ACQUIRE);
     if (!v) return DMME_OK;
     // clear: the device-side sticky words (a set word makes every later wait of that run give up after 1024 polls) and the host word
     // - unless the caller's stream is being captured (synchronising calls would invalidate the capture; the word stays set and the
@@ -443,8 +443,8 @@ int lvl_check(const dmme_plan* P, const char* where, hipStream_t stream, bool ha
         const bool sw = hipGetDevice(&cur) == hipSuccess && cur != P->device && hipSetDevice(P->device) == hipSuccess;
         (void)hipDeviceSynchronize();
         for (const LvlRun& R : P->lvl_runs)
-            if (R.sync_dev) (void)hipMemset(R.sync_dev + 2, 0, 4);
-        __atomic_store_n(P->err_host, 0u, __ATOMIC_RELEASE);
+            if (R.sync_dev) (void)hipMemset(R.sync_dev.get() + 2, 0, 4);
+        __atomic_store_n(P->err_host.get(), 0u, __ATOMIC_RELEASE);
         if (sw) (void)hipSetDevice(cur);
     }
     if (v == kErrNogradBackward) {
@@ -479,7 +479,7 @@ DMME_API int dmme_unet_plan_level_info(const dmme_plan* plan, char* buf, int cap
     out = tmp;
     for (const LvlRun& R : plan->lvl_runs) {
         unsigned ctl[3] = {0, 0, 0};
-        if (R.sync_dev) DMME_CHECK_HIP(hipMemcpy(ctl, R.sync_dev, sizeof(ctl), hipMemcpyDeviceToHost));  // (synchronises with the device)
+        if (R.sync_dev) DMME_CHECK_HIP(hipMemcpy(ctl, R.sync_dev.get(), sizeof(ctl), hipMemcpyDeviceToHost));  // (synchronises with the device)
         snprintf(tmp, sizeof(tmp), " [map=%dx%d plan_ops=%d-%d engine_ops=%d groups=%d per_iteration=%d slice=%d workgroups=%d nograd_raw_skipped=%d epoch=%u err=%u]", 1 << R.sh, 1 << R.sh,
                  R.op_first, R.op_last, (int)R.ops.size(), R.NG, R.GB, 32 * R.NJ, R.NGS * (LVL_NS / R.NJ), R.raw_skipped, ctl[0], ctl[2]);
         out += tmp;

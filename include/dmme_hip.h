@@ -102,8 +102,11 @@ DMME_API int dmme_device_count(void);
 /* ---- UNet plan: replaces UNet.__init__ (models/ddpm.py:190-279) --------------------
  * Builds the layer graph (including the reference's always-false `if` at :242), the
  * parameter table, the packed-weight layout and the activation workspace layout for a
- * fixed (B, H, W, dtype).  Host-only; `device` selects which GPU owns the small
- * re-pack table (-1: do not touch any device, for CPU-side inspection of the table). */
+ * fixed (B, H, W, dtype).  Host-only arithmetic, the backward's tables included; `device` selects which GPU
+ * owns the plan's small device tables (-1: do not touch any device, for CPU-side inspection: such a plan
+ * reports the same gradient buckets, dmme_unet_plan_bwd_summary and backward workspace size as a device
+ * plan of the same arguments on a device that holds the default number of resident level-engine
+ * workgroups, and cannot launch). */
 DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W, int dtype, int device, dmme_plan** out);
 DMME_API void dmme_unet_plan_destroy(dmme_plan* plan);
 

@@ -139,3 +139,79 @@ def test_plan_fuses_residual_convs_into_conv2_where_the_persistent_kernel_runs_i
     assert fused(_plan_labels(1, _lib.BF16)[0]) == 0
     for dt in (_lib.F32, _lib.F16R32):
         assert fused(_plan_labels(128, dt)[0]) == 0
+
+
+def _host_plan_backward(batch, dtype, env=None, arch=None):
+    """(bucket table [(offset, numel, bucket)], ref_numel, bwd_summary) of a host-only plan of the default UNet"""
+    from dmme_amd import _lib
+
+    lib = _lib.lib()
+    cfg = _default_cfg()
+    if arch is not None:
+        cfg.arch, cfg.num_classes = arch, 10
+    saved = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        h = C.c_void_p()
+        assert lib.dmme_unet_plan_create(C.byref(cfg), batch, 32, 32, dtype, -1, C.byref(h)) == 0
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    off, num, bucket = (C.c_int64 * 64)(), (C.c_int64 * 64)(), (C.c_int * 64)()
+    n = lib.dmme_unet_plan_grad_buckets(h, off, num, bucket, 64)
+    assert 1 <= n <= 64
+    buf = C.create_string_buffer(4096)
+    assert lib.dmme_unet_plan_bwd_summary(h, buf, 4096) == 0
+    ref_numel = lib.dmme_unet_plan_ref_numel(h)
+    lib.dmme_unet_plan_destroy(h)
+    return [(off[i], num[i], bucket[i]) for i in range(n)], ref_numel, buf.value.decode()
+
+
+DEFAULT_BUCKETS = [(23908288, 5616000, 0), (32412992, 3715, 0), (19249856, 4658432, 1), (12557248, 6692608, 2), (10523072, 2034176, 3),
+                   (29524288, 2888704, 3), (4682944, 5840128, 4), (0, 4682944, 5)]
+
+
+def test_host_plan_cuts_the_default_unet_into_six_gradient_buckets():
+    """host logic of plan_grad_buckets (csrc/plan_bwd.hip), no GPU: a plan without a device announces the bucket table a device plan
+    hands over (tests/test_gpu_train.py asserts the same three balance conditions on the GPU) - 8 ranges in 6 buckets that tile the
+    flat gradient, whatever the batch and dtype."""
+    from dmme_amd import _lib
+
+    for batch, dtype in ((128, _lib.BF16), (32, _lib.F16), (1, _lib.BF16), (2, _lib.F32), (128, _lib.F16R32)):
+        table, n, _ = _host_plan_backward(batch, dtype)
+        assert table == DEFAULT_BUCKETS, (batch, dtype, table)
+        pos = 0
+        for o, m, _b in sorted(table):
+            assert o == pos, (o, pos)
+            pos = o + m
+        assert pos == n
+        nb = max(b for _, _, b in table) + 1
+        per_bucket = [sum(m for _, m, b in table if b == k) for k in range(nb)]
+        assert nb == 6 and [b for _, _, b in table] == sorted(b for _, _, b in table)
+        assert nb >= 4 and max(per_bucket) <= 0.26 * n and per_bucket[-1] <= 0.15 * n, per_bucket
+
+
+def test_host_plan_reports_the_deferred_backward_tables():
+    """host logic of build_wgrad_group / plan_deferred_reductions (csrc/plan_bwd.hip), no GPU: the grouped weight-gradient, column-sum
+    and bias tables of the benchmark plan; an fp32 plan has no grouped weight gradient and the column sums of every conv."""
+    from dmme_amd import _lib
+
+    _, _, s = _host_plan_backward(128, _lib.BF16)
+    assert s.startswith("wgrad_group3x3_layers=47 wgrad_group3x3_jobs=3840 wgrad_group1x1_layers=25 wgrad_group1x1_jobs=912 "
+                        "colsum_group_jobs=160 bias_group_jobs=1424"), s
+    _, _, s = _host_plan_backward(2, _lib.F32)
+    assert s.startswith("wgrad_group3x3_layers=0 wgrad_group3x3_jobs=0 wgrad_group1x1_layers=0 wgrad_group1x1_jobs=0 colsum_group_jobs=285 "), s
+
+
+def test_host_plan_without_buckets_is_one_piece():
+    """the one-piece answer include/dmme_hip.h documents: the classifier, DMME_NO_GRAD_BUCKETS; grad_buckets=3 cuts three"""
+    from dmme_amd import _lib
+
+    for kw in (dict(arch=_lib.ARCH_CLASSIFIER), dict(env={"DMME_NO_GRAD_BUCKETS": "1"})):
+        table, n, _ = _host_plan_backward(128, _lib.BF16, **kw)
+        assert table == [(0, n, 0)], (kw, table)
+    table, n, _ = _host_plan_backward(128, _lib.BF16, env={"DMME_DEBUG_ROUTE": "grad_buckets=3"})
+    assert len(table) == 5 and max(b for _, _, b in table) + 1 == 3 and sum(m for _, m, _b in table) == n, table
