@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 F16R32 = 4  # F16 below the full-resolution level; that level in fp32 tensors with three-pass split-fp16 products (within 1e-3 of fp32; inference)
 F32, BF16, BF16X3, F16 = 0, 1, 2, 3  # BF16X3: fp32 buffers, three-pass bf16 MFMA convolutions (the accurate mode); F16: IEEE half (inference)
-CHAIN_DDPM, CHAIN_DDIM, CHAIN_IDDPM, CHAIN_DDPM_GUIDED, CHAIN_DDIM_GUIDED = 0, 1, 2, 3, 4
+CHAIN_DDPM, CHAIN_DDIM, CHAIN_IDDPM, CHAIN_DDPM_GUIDED, CHAIN_DDIM_GUIDED, CHAIN_GDDIM = 0, 1, 2, 3, 4, 5
 ARCH_DDPM, ARCH_IDDPM, ARCH_CLASSIFIER = 0, 1, 2
 DTYPES = {"fp32": F32, "float32": F32, "32": F32, "bf16": BF16, "bfloat16": BF16, "16": BF16, "bf16-mixed": BF16, "16-mixed": BF16,
           "bf16x3": BF16X3, "fp16": F16, "float16": F16, "half": F16, "fp16r32": F16R32}
@@ -116,9 +116,12 @@ PROTOTYPES = {
     "dmme_q_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "dmme_ddpm_step": (_i, [_vp, _vp, _vp, _f, _f, _f, _i, _i64, _vp]),
     "dmme_ddim_step": (_i, [_vp, _vp, _f, _f, _i64, _vp]),
+    "dmme_gddim_step": (_i, [_vp, _vp, _vp, _f, _f, _f, _i64, _vp]),
+    "dmme_slerp": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "dmme_chain_set": (_i, [_vp, _i64, _vp, _u64, _u64, _vp]),
     "dmme_chain_update": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "dmme_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dmme_chain_update_gddim": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "dmme_log_softmax_grad": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "dmme_chain_update_guided": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "dmme_guided_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

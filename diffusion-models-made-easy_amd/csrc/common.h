@@ -369,6 +369,9 @@ int launch_q_sample(const float* x0, const float* z, const float* sqrt_abar, con
 int launch_ddpm_step(float* x, const float* eps, const float* z, float c1, float c2, float sigma, int add_noise,
                      int64_t numel, hipStream_t s);
 int launch_ddim_step(float* x, const float* eps, float s1, float s2, int64_t numel, hipStream_t s);
+int launch_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, hipStream_t s);
+int slerp_parts(int64_t chw);  // blocks per image of the first launch of launch_slerp: its scratch holds 3 * B * slerp_parts(chw) floats
+int launch_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, float* scratch, hipStream_t s);
 int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s);
 int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
                         hipStream_t s, const float* grad = nullptr, const float* noise = nullptr);

@@ -171,6 +171,40 @@ int launch_ddim_step(float* x, const float* eps, float s1, float s2, int64_t num
     return DMME_OK;
 }
 
+// Paper-form DDIM (Song et al. 2021, eq. 12) for every eta and both directions as one linear form: x' = (k0 x + k1 eps) + k2 z,
+// each product and sum rounded on its own (the host folds the square roots into k0..k2 in float64; dmme_hip.h: dmme_gddim_step).
+// z is read only where k2 != 0.
+__device__ __forceinline__ float gddim_update(float x, float e, float z, float k0, float k1, float k2) {
+    const float m = __fadd_rn(__fmul_rn(k0, x), __fmul_rn(k1, e));
+    return k2 != 0.0f ? __fadd_rn(m, __fmul_rn(k2, z)) : m;
+}
+__global__ void __launch_bounds__(256) gddim_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ z,
+                                                         float k0, float k1, float k2, int64_t n4, int64_t numel) {
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = q * 4;
+        if (b + 3 < numel) {
+            float4 xv = *reinterpret_cast<const float4*>(x + b);
+            const float4 ev = *reinterpret_cast<const float4*>(eps + b);
+            float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k2 != 0.0f) zv = *reinterpret_cast<const float4*>(z + b);
+            xv.x = gddim_update(xv.x, ev.x, zv.x, k0, k1, k2);
+            xv.y = gddim_update(xv.y, ev.y, zv.y, k0, k1, k2);
+            xv.z = gddim_update(xv.z, ev.z, zv.z, k0, k1, k2);
+            xv.w = gddim_update(xv.w, ev.w, zv.w, k0, k1, k2);
+            *reinterpret_cast<float4*>(x + b) = xv;
+        } else {
+            for (int64_t i = b; i < numel; ++i) x[i] = gddim_update(x[i], eps[i], k2 != 0.0f ? z[i] : 0.f, k0, k1, k2);
+        }
+    }
+}
+int launch_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, hipStream_t s) {
+    if (numel <= 0) return DMME_OK;
+    const int64_t n4 = (numel + 3) / 4;
+    hipLaunchKernelGGL(gddim_step_kernel, dim3(grid_for(n4)), dim3(256), 0, s, x, eps, z, k0, k1, k2, n4, numel);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
 // ------------------------------------------------------------------ MSE loss (+ gradient)
 __global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restrict__ eps, const float* __restrict__ target,
                                                           int64_t numel, float* __restrict__ d_eps, float gscale,
@@ -350,7 +384,8 @@ __global__ void chain_set_kernel(ChainState* st, long long i, const long long* _
 //      2: IDDPM (1/sqrt(alpha), beta/sqrt(1-abar), log beta, log max(beta~, 1e-12)); `out` has 2*chw values per image then
 //      3: classifier-guided DDPM (coef 0..2 as DDPM, coef[3] = s beta_t): x = mean + s beta_t g (+ sqrt(beta_t) z)
 //      4: classifier-guided DDIM (coef 0..1 as DDIM, coef[2] = s sqrt(1-abar_tau_i)): eps' = eps - s sqrt(1-abar_tau_i) g, then DDIM
-// g: d log p(y | x_t, t) / d x_t (guided kinds); zin (nullable, guided kinds): normals to use instead of the drawn ones (tests)
+//      5: paper-form DDIM, any eta, either direction (coef = k0, k1, k2): x = (k0 x + k1 eps) + k2 z; z drawn only where k2 != 0
+// g: d log p(y | x_t, t) / d x_t (guided kinds); zin (nullable, kinds 3 and 5): normals to use instead of the drawn ones (tests)
 template <int KIND>
 __global__ void __launch_bounds__(256) chain_update_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ coef,
                                                            const long long* __restrict__ t_table, ChainState* st, int64_t chw, int64_t n4,
@@ -378,6 +413,20 @@ __global__ void __launch_bounds__(256) chain_update_kernel(float* __restrict__ x
                 const float e = __fsub_rn(es[j], __fmul_rn(c2, gs[j]));
                 xs[j] = __fmul_rn(c1, __fdiv_rn(__fsub_rn(xs[j], __fmul_rn(c0, e)), c1));
             }
+        } else if (KIND == 5) {
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (c2 != 0.0f) {  // (the offset advances whether or not the draw is used, as at t == 1 of the DDPM kind)
+                if (zin) {
+                    const float4 zv = *reinterpret_cast<const float4*>(zin + b);
+                    z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+                } else {
+                    normal4(seed, off + (uint64_t)q, z);
+                }
+            }
+            const float4 ev = *reinterpret_cast<const float4*>(out + b);
+            const float* es = reinterpret_cast<const float*>(&ev);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xs[j] = gddim_update(xs[j], es[j], z[j], c0, c1, c2);
         } else if (KIND == 3) {
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (add_noise) {
@@ -442,8 +491,8 @@ int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t se
 
 int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
                         hipStream_t s, const float* grad, const float* noise) {
-    DMME_REQUIRE(kind >= 0 && kind <= 4, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
-    DMME_REQUIRE((kind >= 3) == (grad != nullptr), DMME_ERR_INVALID, "chain_update: the guided kinds (3, 4) and only they take a gradient");
+    DMME_REQUIRE(kind >= 0 && kind <= 5, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
+    DMME_REQUIRE((kind == 3 || kind == 4) == (grad != nullptr), DMME_ERR_INVALID, "chain_update: the guided kinds (3, 4) and only they take a gradient");
     DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "chain_update: image size %lld is not a multiple of 4", (long long)chw);
     const int64_t n4 = (int64_t)B * chw / 4;
     if (n4 <= 0) return DMME_OK;
@@ -458,8 +507,104 @@ int launch_chain_update(int kind, float* x, const float* out, const float* coef,
         hipLaunchKernelGGL(chain_update_kernel<2>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
     else if (kind == 3)
         hipLaunchKernelGGL(chain_update_kernel<3>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else
+    else if (kind == 4)
         hipLaunchKernelGGL(chain_update_kernel<4>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    else
+        hipLaunchKernelGGL(chain_update_kernel<5>, g, b, 0, s, x, out, coef, tt, st, chw, n4, (const float*)nullptr, noise);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// ------------------------------------------------------------------ spherical interpolation of latents (dmme_hip.h: dmme_slerp)
+// Two launches.  (1) per image pair, <xa, xb>, |xa|^2 and |xb|^2: `parts` blocks per image each leave three partial sums
+// (float4 loads, wave / block sums; stores, no atomics: the result does not depend on arrival order).  (2) every block of the
+// blend sums its image's partials, turns them and a tile of up to SLERP_TILE weights into the two coefficients per weight
+// (the handful of acos / sin per block runs in double), then streams its share of the image: xa and xb are loaded once per
+// weight tile and each weight's output is written from registers.
+constexpr int SLERP_TILE = 64;
+constexpr int SLERP_MAX_PARTS = 256;
+
+__global__ void __launch_bounds__(256) slerp_dots_kernel(const float* __restrict__ xa, const float* __restrict__ xb, int64_t chw4,
+                                                         float* __restrict__ partial) {
+    __shared__ float red[16];
+    const int64_t base = (int64_t)blockIdx.y * chw4 * 4;
+    float ab = 0.f, aa = 0.f, bb = 0.f;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < chw4; q += (int64_t)gridDim.x * blockDim.x) {
+        const float4 a = *reinterpret_cast<const float4*>(xa + base + q * 4);
+        const float4 b = *reinterpret_cast<const float4*>(xb + base + q * 4);
+        ab += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+        aa += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+        bb += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+    }
+    const float s0 = block_sum(ab, red);
+    const float s1 = block_sum(aa, red);
+    const float s2 = block_sum(bb, red);
+    if (threadIdx.x == 0) {
+        float* p = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+        p[0] = s0;
+        p[1] = s1;
+        p[2] = s2;
+    }
+}
+
+__global__ void __launch_bounds__(256) slerp_blend_kernel(const float* __restrict__ xa, const float* __restrict__ xb, const float* __restrict__ w,
+                                                          int n, int64_t chw4, const float* __restrict__ partial, int parts,
+                                                          float* __restrict__ out) {
+    __shared__ float red[16];
+    __shared__ float ca[SLERP_TILE], cb[SLERP_TILE];
+    const int B = gridDim.y;
+    const int64_t img = blockIdx.y, base = img * chw4 * 4;
+    float ab = 0.f, aa = 0.f, bb = 0.f;
+    for (int p = threadIdx.x; p < parts; p += blockDim.x) {
+        const float* v = partial + (img * parts + p) * 3;
+        ab += v[0];
+        aa += v[1];
+        bb += v[2];
+    }
+    const float dot = block_sum(ab, red);
+    const float na2 = block_sum(aa, red);
+    const float nb2 = block_sum(bb, red);
+    double cosv = (double)dot / (sqrt((double)na2) * sqrt((double)nb2));  // (a zero image: NaN, which takes the linear form below)
+    cosv = cosv > 1.0 ? 1.0 : (cosv < -1.0 ? -1.0 : cosv);
+    const double theta = acos(cosv), sn = sin(theta);
+    const bool linear = !(sn >= 1e-6);
+    for (int j0 = 0; j0 < n; j0 += SLERP_TILE) {
+        const int nt = n - j0 < SLERP_TILE ? n - j0 : SLERP_TILE;
+        __syncthreads();  // the previous tile's coefficients have been read
+        if ((int)threadIdx.x < nt) {
+            const double wj = (double)w[j0 + threadIdx.x];
+            ca[threadIdx.x] = (float)(linear ? 1.0 - wj : sin((1.0 - wj) * theta) / sn);
+            cb[threadIdx.x] = (float)(linear ? wj : sin(wj * theta) / sn);
+        }
+        __syncthreads();
+        for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < chw4; q += (int64_t)gridDim.x * blockDim.x) {
+            const float4 a = *reinterpret_cast<const float4*>(xa + base + q * 4);
+            const float4 b = *reinterpret_cast<const float4*>(xb + base + q * 4);
+            for (int j = 0; j < nt; ++j) {
+                const float fa = ca[j], fb = cb[j];
+                float4 o;
+                o.x = fa * a.x + fb * b.x;
+                o.y = fa * a.y + fb * b.y;
+                o.z = fa * a.z + fb * b.z;
+                o.w = fa * a.w + fb * b.w;
+                *reinterpret_cast<float4*>(out + ((int64_t)(j0 + j) * B + img) * chw4 * 4 + q * 4) = o;
+            }
+        }
+    }
+}
+
+int slerp_parts(int64_t chw) {
+    const int64_t p = (chw / 4 + 255) / 256;
+    return (int)(p > SLERP_MAX_PARTS ? SLERP_MAX_PARTS : (p < 1 ? 1 : p));
+}
+
+int launch_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, float* scratch, hipStream_t s) {
+    DMME_REQUIRE(n > 0 && B > 0 && B <= 65535 && chw > 0, DMME_ERR_INVALID, "slerp: n = %d weights, B = %d images of %lld values", n, B, (long long)chw);
+    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_INVALID, "slerp: image size %lld is not a multiple of 4", (long long)chw);
+    const int parts = slerp_parts(chw);
+    hipLaunchKernelGGL(slerp_dots_kernel, dim3(parts, B), dim3(256), 0, s, xa, xb, chw / 4, scratch);
+    DMME_CHECK_LAUNCH();
+    hipLaunchKernelGGL(slerp_blend_kernel, dim3(parts, B), dim3(256), 0, s, xa, xb, w, n, chw / 4, (const float*)scratch, parts, out);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

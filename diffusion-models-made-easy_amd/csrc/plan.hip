@@ -2,6 +2,9 @@
 // packed-weight layout, workspace layout, launch sequence) and the extern "C" API.
 #include "plan.h"
 
+#include <map>
+#include <mutex>
+
 namespace dmme {
 
 static thread_local char g_err[512] = "";
@@ -1395,7 +1398,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 107; }  // 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 108; }  // 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1656,6 +1659,11 @@ DMME_API int dmme_ddim_step(float* x, const float* eps, float sqrt_one_minus_aba
     return launch_ddim_step(x, eps, sqrt_one_minus_abar, sqrt_abar_prev, numel, (hipStream_t)stream);
 }
 
+DMME_API int dmme_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, void* stream) {
+    DMME_REQUIRE(x && eps && (z || k2 == 0.0f) && numel >= 0, DMME_ERR_INVALID, "gddim_step: null argument (z is needed where k2 != 0)");
+    return launch_gddim_step(x, eps, z, k0, k1, k2, numel, (hipStream_t)stream);
+}
+
 DMME_API int dmme_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t philox_seed, uint64_t philox_offset, void* stream) {
     DMME_REQUIRE(state && t_table && i >= 0, DMME_ERR_INVALID, "chain_set: bad argument");
     return launch_chain_set(state, i, t_table, philox_seed, philox_offset, (hipStream_t)stream);
@@ -1667,11 +1675,17 @@ DMME_API int dmme_chain_update(int kind, float* x, const float* model_out, const
     return launch_chain_update(kind, x, model_out, step_coef, t_table, state, B, chw, (hipStream_t)stream);
 }
 
+DMME_API int dmme_chain_update_gddim(float* x, const float* model_out, const float* noise, const float* step_coef, const int64_t* t_table,
+                                     void* state, int B, int64_t chw, void* stream) {
+    DMME_REQUIRE(x && model_out && step_coef && t_table && state && B > 0 && chw > 0, DMME_ERR_INVALID, "chain_update_gddim: bad argument");
+    return launch_chain_update(DMME_CHAIN_GDDIM, x, model_out, step_coef, t_table, state, B, chw, (hipStream_t)stream, nullptr, noise);
+}
+
 DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
                              const float* step_coef, const int64_t* t_table, void* state, void* stream) {
     DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state, DMME_ERR_INVALID, "chain_step: null argument");
     if (int rc0 = lvl_check(plan, "chain_step", (hipStream_t)stream, true)) return rc0;
-    DMME_REQUIRE(kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_IDDPM && plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+    DMME_REQUIRE(((kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_IDDPM) || kind == DMME_CHAIN_GDDIM) && plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
                  "chain_step: sampler kind %d / architecture %d (guided kinds: dmme_guided_chain_step)", kind, plan->cfg.arch);
     DMME_REQUIRE((kind == DMME_CHAIN_IDDPM) == (plan->out_channels == 2 * plan->cfg.in_channels), DMME_ERR_INVALID,
                  "chain_step: sampler kind %d does not fit a network with %d output channels", kind, plan->out_channels);
@@ -1681,6 +1695,33 @@ DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x
     if (rc != DMME_OK) return rc;
     return launch_chain_update(kind, x, model_out, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
                                (hipStream_t)stream);
+}
+
+// The two launches of dmme_slerp hand three partial sums per (image, block) from one to the other.  The entry point takes no scratch
+// argument, so the library keeps one buffer per device, grown on demand (hipFree waits for the device: no launch still reads the old one).
+DMME_API int dmme_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, void* stream) {
+    DMME_REQUIRE(xa && xb && w && out, DMME_ERR_INVALID, "slerp: null argument");
+    DMME_REQUIRE(n > 0 && B > 0 && B <= 65535 && chw > 0, DMME_ERR_INVALID, "slerp: n = %d weights, B = %d images of %lld values", n, B, (long long)chw);
+    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_INVALID, "slerp: image size %lld is not a multiple of 4", (long long)chw);
+    static std::mutex mu;
+    static std::map<int, std::pair<float*, size_t>> scratch;  // device -> (buffer, floats)
+    const size_t need = (size_t)3 * B * slerp_parts(chw);
+    float* buf = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        int dev = 0;
+        DMME_CHECK_HIP(hipGetDevice(&dev));
+        auto& e = scratch[dev];
+        if (e.second < need) {
+            if (e.first) DMME_CHECK_HIP(hipFree(e.first));
+            e = {nullptr, 0};
+            const size_t cap = need < 4096 ? 4096 : need;
+            DMME_CHECK_HIP(hipMalloc((void**)&e.first, cap * sizeof(float)));
+            e.second = cap;
+        }
+        buf = e.first;
+    }
+    return launch_slerp(xa, xb, w, n, B, chw, out, buf, (hipStream_t)stream);
 }
 
 DMME_API int dmme_log_softmax_grad(const float* logits, const int64_t* y, int B, int K, int mode, float scale, float* loss, float* d_logits,

@@ -26,15 +26,18 @@ class ChainRunner:
     changes between steps, nothing is copied host-to-device, nothing synchronises.  `x` is updated in place.  Falls back to
     issuing the same launches eagerly when graph capture is unavailable (same results either way)."""
 
-    def __init__(self, process, x: Tensor, use_graph: bool = True):
+    def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
+        """`spec`: an explicit (kind, (n, rows, t_table)) in place of the process's own `_chain_kind` / `_chain_tables()` - a process
+        with more than one chain over the same network (GeneralizedDDIM: the reversed tables of its encoding direction)"""
         model = process.model
         if not (isinstance(x, Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4):
             raise ValueError("ChainRunner needs a contiguous fp32 GPU image batch")
         B, _, H, W = x.shape
         self.process, self.model, self.x = process, model, x
         self.plan = model._plan_for(B, H, W, x.device)
-        self.kind = process._chain_kind
-        n, rows, ttab = process._chain_tables()
+        self.kind, (n, rows, ttab) = spec if spec is not None else (process._chain_kind, process._chain_tables())
+        # does the update consume normals?  (the shipped DDIM kinds never do; the paper-form kind only with a non-zero k2 somewhere)
+        self.draws = self.kind not in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED) and (self.kind != _lib.CHAIN_GDDIM or any(r[2] != 0.0 for r in rows))
         self.n_steps = n
         self.coef = torch.tensor(rows, dtype=torch.float32).reshape(-1).to(x.device)
         self.ttab = torch.tensor(ttab, dtype=torch.int64).to(x.device)
@@ -104,7 +107,7 @@ class ChainRunner:
 
     def run(self, first: int, count: int):
         """`count` steps from loop index `first` downwards, drawing from torch's CUDA generator like the eager loop"""
-        if self.kind in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED):  # the DDIM update draws nothing: torch's generator stays where the eager loop leaves it
+        if not self.draws:  # a chain that draws nothing: torch's generator stays where the eager loop leaves it
             seed, off = 0, 0
         else:
             seed, off = philox_reserve(self.x.device, self.x.numel() * count)
@@ -161,7 +164,7 @@ class DDPM(nn.Module):
             self._all_t = torch.arange(0, n, device=device).unsqueeze(1)
         return self._all_t[t]
 
-    def chain_runner(self, x: Tensor, use_graph: bool = True, slot: str = "_runner") -> Optional[ChainRunner]:
+    def chain_runner(self, x: Tensor, use_graph: bool = True, slot: str = "_runner", spec=None) -> Optional[ChainRunner]:
         """runner bound to the image buffer `x` (cached per buffer / shape); None when the replayable step does not apply
         (a model that is not a dmme_amd UNet, train mode, an image size that is not a multiple of 4)"""
         model = self.model
@@ -170,7 +173,7 @@ class DDPM(nn.Module):
         r = getattr(self, slot, None)
         key = (x.data_ptr(), tuple(x.shape), model._dtype, use_graph)
         if r is None or r._key != key or r.model is not model:
-            r = ChainRunner(self, x, use_graph)
+            r = ChainRunner(self, x, use_graph, spec() if spec is not None else None)  # (spec: a callable, evaluated only when a runner is built)
             r._key = key
             setattr(self, slot, r)
         return r
@@ -195,7 +198,8 @@ class DDPM(nn.Module):
         if runner is None:
             return None
         buf.copy_(x_t)
-        seed, off = philox_reserve(x_t.device, x_t.numel())
+        # (the paper-form DDIM kind at eta = 0 reserves nothing, like its eager step; every other kind keeps reserving one span per call)
+        seed, off = (0, 0) if runner.kind == _lib.CHAIN_GDDIM and not runner.draws else philox_reserve(x_t.device, x_t.numel())
         runner.set(index, seed, off)
         with torch.no_grad():
             runner.step()

@@ -16,7 +16,7 @@ checkpoint callbacks, ...):
   seed_everything
 
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml [--max-steps N] [--batch-size B]
-  python -m dmme_amd.trainer sample --config configs/ddim/cifar10.yaml [--num-images N] [--steps K]
+  python -m dmme_amd.trainer sample --config configs/ddim/cifar10.yaml [--num-images N] [--steps K] [--sampler ddim-paper --eta E]
 """
 
 from __future__ import annotations
@@ -210,6 +210,9 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper"],
+                    help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table")
+    ap.add_argument("--eta", type=float, default=0.0, help="sample --sampler ddim-paper: 0 deterministic ... 1 DDPM's posterior variance")
     args = ap.parse_args(argv)
 
     from . import _lib
@@ -237,6 +240,13 @@ def main(argv=None):
             from .checkpoint import load_checkpoint
 
             load_checkpoint(ckpt_path, module, strict=False)
+        if args.sampler == "ddim-paper":
+            from .diffusion_models import DDIM, GeneralizedDDIM
+
+            old = module.diffusion_model
+            if not isinstance(old, DDIM):
+                raise SystemExit("--sampler ddim-paper needs a DDIM config (sub_timesteps and a tau schedule)")
+            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta).cuda()
         module.eval()
         dm = module.diffusion_model
         t0 = time.perf_counter()
@@ -248,8 +258,9 @@ def main(argv=None):
             import dmme_amd
 
             imgs = dmme_amd.gaussian(shape, device="cuda")
+            first = dm.sub_timesteps if args.sampler == "ddim-paper" else dm.timesteps  # (the paper sampler's loop index counts sub-steps)
             for k in range(args.steps):
-                imgs = module(imgs, dm.timesteps - k)
+                imgs = module(imgs, first - k)
         torch.cuda.synchronize()
         print(json.dumps({"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3),
                           "finite": bool(torch.isfinite(imgs).all())}))

@@ -330,6 +330,27 @@ DMME_API int dmme_ddpm_step(float* x, const float* eps, const float* z, float in
 DMME_API int dmme_ddim_step(float* x, const float* eps, float sqrt_one_minus_abar, float sqrt_abar_prev, int64_t numel,
                    void* stream);
 
+/* one paper-form DDIM update (Song et al. 2021, eq. 12), in place on x; the eager twin of DMME_CHAIN_GDDIM (below), bit-identical to it:
+ *   x = (k0 * x + k1 * eps) + k2 * z      every product and sum rounded to fp32 on its own (no fma)
+ * The host folds the schedule into the three scalars in float64 and rounds them to fp32.  With a = abar[tau_i]:
+ *   reverse step to p = abar[tau_{i-1}]:  sigma = eta sqrt((1-p)/(1-a)) sqrt(1 - a/p)  (0 where p == 1 or a == 1),
+ *                                         k0 = sqrt(p/a), k1 = sqrt(max(1 - p - sigma^2, 0)) - k0 sqrt(1-a), k2 = sigma
+ *   encode step to n = abar[tau_{i+1}]:   k0 = sqrt(n/a), k1 = sqrt(1-n) - k0 sqrt(1-a), k2 = 0
+ * z is read only where k2 != 0 and may be NULL otherwise.  The DDIM update dmme_ddim_step computes is the reference's collapsed one
+ * (x - sqrt(1-abar_tau_i) eps: the term sqrt(1-abar_prev) eps that points back to x_t is missing) and stays as it is. */
+DMME_API int dmme_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, void* stream);
+
+/* spherical interpolation between B pairs of images (latents) at n weights, xa / xb: (B, chw), w: n device floats, out: (n, B, chw):
+ *   theta_b = acos(clamp(<xa_b, xb_b> / (|xa_b| |xb_b|), -1, 1))
+ *   out[j][b] = sin((1 - w_j) theta_b) / sin(theta_b) * xa_b + sin(w_j theta_b) / sin(theta_b) * xb_b
+ * and out[j][b] = (1 - w_j) xa_b + w_j xb_b where sin(theta_b) < 1e-6 (parallel images, or one of them zero).
+ * Two launches: the three sums per image (several blocks per image, partial sums through a per-device buffer the library owns:
+ * calls on one device must be ordered, on one stream or by events), then one pass that reads xa and xb once per tile of 64 weights
+ * and writes every weight's output.  The buffer is allocated at the first call and whenever it has to grow, which a stream capture
+ * does not allow: make one call of the shape outside a capture first.  chw must be a multiple of 4; n > 0; 0 < B <= 65535; out must
+ * not alias xa or xb. */
+DMME_API int dmme_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, void* stream);
+
 /* simple_loss (equations/ddpm/losses.py:13): loss[0] = mean((target-eps)^2); optional
  * d_eps = 2 (eps - target) / numel * grad_scale.  `scratch` needs 1024 floats. */
 DMME_API int dmme_mse_loss(const float* eps, const float* target, int64_t numel, float* loss, float* d_eps,
@@ -359,17 +380,24 @@ DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64
  *             DMME_CHAIN_DDPM  {1/sqrt(alpha_t), beta_t/sqrt(1-abar_t), sqrt(beta_t), -}     (equations/ddpm/ddpm.py:65-71)
  *             DMME_CHAIN_DDIM  {sqrt(1-abar_tau_i), sqrt(abar_tau_{i-1}), -, -}              (equations/ddim/ddim.py:52-57)
  *             DMME_CHAIN_IDDPM {1/sqrt(alpha_t), beta_t/sqrt(1-abar_t), log beta_t, log max(beta~_t, 1e-12)}
+ *             DMME_CHAIN_GDDIM {k0, k1, k2, -} of dmme_gddim_step: the paper-form DDIM step at loop index i, for any eta.  The index
+ *                              only ever runs downwards, so a chain that ENCODES (x_0 -> x_T) gets reversed tables: row and timestep
+ *                              at loop index j describe the step tau_{S-j} -> tau_{S-j+1}
  * dmme_chain_update = the sampler update alone (noise drawn in the kernel from Philox(state.seed, state.offset + quad index): the values
  * dmme_randn would produce at the same offset, so a chain equals the eager loop bit for bit); no noise is added at t == 1 but
  * the offset advances all the same (the reference draws and discards, diffusion_models/ddpm.py:107-110).  After the update the
  * state moves on: i -= 1, t = t_table[i], offset += B*chw/4.  dmme_chain_step = dmme_unet_forward at t = state.t followed by
- * dmme_chain_update; x is updated in place, model_out receives the network output.  chw must be a multiple of 4. */
-enum { DMME_CHAIN_DDPM = 0, DMME_CHAIN_DDIM = 1, DMME_CHAIN_IDDPM = 2, DMME_CHAIN_DDPM_GUIDED = 3, DMME_CHAIN_DDIM_GUIDED = 4 };
+ * dmme_chain_update; x is updated in place, model_out receives the network output.  chw must be a multiple of 4.
+ * DMME_CHAIN_GDDIM draws its normals only at loop indices whose k2 != 0; the offset advances at every step all the same.
+ * dmme_chain_update_gddim = dmme_chain_update(DMME_CHAIN_GDDIM, ...) with `noise` (nullable) used in place of the drawn normals (tests). */
+enum { DMME_CHAIN_DDPM = 0, DMME_CHAIN_DDIM = 1, DMME_CHAIN_IDDPM = 2, DMME_CHAIN_DDPM_GUIDED = 3, DMME_CHAIN_DDIM_GUIDED = 4, DMME_CHAIN_GDDIM = 5 };
 DMME_API int dmme_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t philox_seed, uint64_t philox_offset, void* stream);
 DMME_API int dmme_chain_update(int kind, float* x, const float* model_out, const float* step_coef, const int64_t* t_table, void* state,
                       int B, int64_t chw, void* stream);
 DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
                     const float* step_coef, const int64_t* t_table, void* state, void* stream);
+DMME_API int dmme_chain_update_gddim(float* x, const float* model_out, const float* noise, const float* step_coef, const int64_t* t_table,
+                            void* state, int B, int64_t chw, void* stream);
 
 /* ---- classifier guidance (Dhariwal & Nichol 2021, Algorithms 1 and 2; the reference's src/dmme/guidance/classifier.py sketch) ----
  * dmme_log_softmax_grad: row-wise log-softmax of logits (B, K) fp32 against int64 labels y[B].
