@@ -87,3 +87,43 @@ class _IDDPMLossFunction(torch.autograd.Function):
 def iddpm_loss_apply(model_out: Tensor, x_t: Tensor, x_0: Tensor, target: Tensor, t: Tensor, coef: Tensor, w_simple: float, w_vlb: float) -> Tensor:
     """w_simple * L_simple + w_vlb * L_vlb (reference: diffusion_models/iddpm.py:92-116, equations/iddpm/losses.py:40-98)."""
     return _IDDPMLossFunction.apply(model_out, x_t, x_0, target, t, coef.to(device=model_out.device, dtype=torch.float32).contiguous(), w_simple, w_vlb)
+
+
+class _IDDPMLossRowsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model_out: Tensor, x_t: Tensor, x_0: Tensor, target: Tensor, t: Tensor, coef: Tensor, timesteps: int, weight, w_simple: float,
+                w_vlb: float, status):
+        o = model_out.detach().to(torch.float32).contiguous()
+        B = o.size(0)
+        loss = torch.empty(3, dtype=torch.float32, device=o.device)
+        rows = torch.empty((3, B), dtype=torch.float32, device=o.device)
+        scratch = torch.empty(64 * B, dtype=torch.float32, device=o.device)
+        d_out = torch.empty_like(o) if model_out.requires_grad else None
+        _lib.check(
+            _lib.lib().dmme_iddpm_loss_rows(_lib.ptr(o), _lib.ptr(x_t), _lib.ptr(x_0), _lib.ptr(target), _lib.ptr(t), _lib.ptr(coef), int(timesteps),
+                                            _lib.ptr(weight), B, x_t[0].numel(), w_simple, w_vlb, _lib.ptr(loss), _lib.ptr(rows), _lib.ptr(d_out), 1.0,
+                                            _lib.ptr(status), _lib.ptr(scratch), _lib.stream_ptr()),
+            "dmme_iddpm_loss_rows",
+        )
+        ctx.d_out = d_out
+        ctx.parts = loss
+        ctx.mark_non_differentiable(rows)
+        return loss[0], rows
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor, _grad_rows):
+        d = ctx.d_out
+        ctx.d_out = None
+        return (d * grad_out if d is not None else None), None, None, None, None, None, None, None, None, None, None
+
+
+def iddpm_loss_rows_apply(model_out: Tensor, x_t: Tensor, x_0: Tensor, target: Tensor, t: Tensor, coef: Tensor, timesteps: int, weight,
+                          w_simple: float, w_vlb: float, status=None):
+    """(importance-weighted loss, rows (3, B)): dmme_iddpm_loss_rows.  loss = mean_b weight_b rows[2][b]; rows = per-image L_simple, L_vlb and
+    w_simple L_simple + w_vlb L_vlb, unweighted and outside the autograd graph; the gradient carries weight_b.  `status`: device int32[1]
+    the kernel sets when a t lies outside [1, timesteps]."""
+    dev = model_out.device
+    if weight is not None:
+        weight = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return _IDDPMLossRowsFunction.apply(model_out, x_t, x_0, target, t, coef.to(device=dev, dtype=torch.float32).contiguous(), timesteps, weight,
+                                        w_simple, w_vlb, status)

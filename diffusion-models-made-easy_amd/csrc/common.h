@@ -390,6 +390,13 @@ int launch_iddpm_step(float* x, const float* out, const float* z, float c1, floa
                       int B, int64_t chw, hipStream_t s);
 int launch_iddpm_loss(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int B,
                       int64_t chw, float w_simple, float w_vlb, float* loss, float* d_out, float gscale, float* scratch, hipStream_t s);
+int launch_iddpm_loss_rows(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int T,
+                           const float* weight, int B, int64_t chw, float w_simple, float w_vlb, float* loss, float* rows, float* d_out,
+                           float gscale, int* status, float* scratch, hipStream_t s);
+int launch_iddpm_prior_rows(const float* x_0, int B, int64_t chw, float alpha_bar_T, float* prior, hipStream_t s);
+int launch_tsampler_draw(const float* hist, const int* count, int T, int H, float uniform_prob, uint64_t seed, uint64_t offset, int B, int64_t* t,
+                         float* weight, float* p, hipStream_t s);
+int launch_tsampler_update(float* hist, int* count, int T, int H, const int64_t* t, const float* L, int B, int* status, hipStream_t s);
 int launch_mse(const float* eps, const float* target, int64_t numel, float* loss, float* d_eps, float gscale,
                float* scratch, hipStream_t s);
 

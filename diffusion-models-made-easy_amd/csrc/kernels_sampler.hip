@@ -275,6 +275,32 @@ int launch_iddpm_step(float* x, const float* out, const float* z, float c1, floa
 //   [0] 1/sqrt(alpha_t)  [1] beta_t/sqrt(1-abar_t)  [2] log beta_t  [3] log max(beta~_t, 1e-12)
 //   [4] sqrt(abar_{t-1}) beta_t/(1-abar_t)  [5] sqrt(alpha_t)(1-abar_{t-1})/(1-abar_t)  [6] sqrt(beta~_t)  [7] unused
 // L_vlb uses the predicted noise with a stop-gradient, so d/d(eps) comes from L_simple only and d/d(v) from L_vlb only.
+// one element of the loss: d = target - eps (L_simple's residual), the VLB term and d(VLB term)/dv.  Shared by iddpm_loss_kernel and
+// iddpm_loss_rows_kernel, so the two evaluate the same expressions in the same order.
+__device__ __forceinline__ void iddpm_loss_elem(const float* __restrict__ c, bool t_is_one, float e, float v, float xt, float x0, float tgt,
+                                                float& d, float& vlb, float& dv) {
+    d = tgt - e;
+    const float mean = c[0] * (xt - c[1] * e);
+    const float sd = iddpm_std(v, c[2], c[3]);
+    const float hl = 0.5f * (c[2] - c[3]);  // d(sd)/dv = sd * hl
+    if (t_is_one) {  // discrete NLL of x_0 in bins of +-1/255 (losses.py:9-20)
+        const float ap = (x0 + 1.0f / 255.0f - mean) / sd, am = (x0 - 1.0f / 255.0f - mean) / sd;
+        const bool up = x0 < 1.0f, lo = x0 > -1.0f;
+        const float Fp = up ? 0.5f * (1.0f + erff(ap * 0.70710678118654752f)) : 1.0f;
+        const float Fm = lo ? 0.5f * (1.0f + erff(am * 0.70710678118654752f)) : 0.0f;
+        const float prob = Fp - Fm;
+        vlb = -logf(fmaxf(prob, 1e-12f));
+        const float pp = up ? 0.3989422804014327f * expf(-0.5f * ap * ap) * ap : 0.f;
+        const float pm = lo ? 0.3989422804014327f * expf(-0.5f * am * am) * am : 0.f;
+        dv = prob >= 1e-12f ? hl * (pp - pm) / prob : 0.f;  // -(1/prob) d(prob)/d(sd) * sd * hl, d Phi(a)/d sd = -phi(a) a / sd
+    } else {  // KL(q(x_{t-1} | x_t, x_0) || p_theta) (losses.py:23-31, torch kl_normal_normal)
+        const float qm = c[4] * x0 + c[5] * xt;
+        const float q = c[6] / sd, ratio = q * q;
+        const float u = (qm - mean) / sd, t1 = u * u;
+        vlb = 0.5f * (ratio + t1 - 1.0f - logf(ratio));
+        dv = hl * (1.0f - ratio - t1);
+    }
+}
 __global__ void __launch_bounds__(256) iddpm_loss_kernel(const float* __restrict__ out, const float* __restrict__ x_t, const float* __restrict__ x_0,
                                                          const float* __restrict__ target, const int64_t* __restrict__ t,
                                                          const float* __restrict__ coef, int64_t chw, int64_t total, float w_simple, float w_vlb,
@@ -284,32 +310,9 @@ __global__ void __launch_bounds__(256) iddpm_loss_kernel(const float* __restrict
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = i / chw, r = i - b * chw;
         const int64_t tt = t[b];
-        const float* c = coef + tt * 8;
-        const float e = out[b * 2 * chw + r], v = out[b * 2 * chw + chw + r];
-        const float xt = x_t[i], x0 = x_0[i];
-        const float d = target[i] - e;
+        float d, vlb, dv;
+        iddpm_loss_elem(coef + tt * 8, tt == 1, out[b * 2 * chw + r], out[b * 2 * chw + chw + r], x_t[i], x_0[i], target[i], d, vlb, dv);
         acc_s += d * d;
-        const float mean = c[0] * (xt - c[1] * e);
-        const float sd = iddpm_std(v, c[2], c[3]);
-        const float hl = 0.5f * (c[2] - c[3]);  // d(sd)/dv = sd * hl
-        float vlb, dv;
-        if (tt == 1) {  // discrete NLL of x_0 in bins of +-1/255 (losses.py:9-20)
-            const float ap = (x0 + 1.0f / 255.0f - mean) / sd, am = (x0 - 1.0f / 255.0f - mean) / sd;
-            const bool up = x0 < 1.0f, lo = x0 > -1.0f;
-            const float Fp = up ? 0.5f * (1.0f + erff(ap * 0.70710678118654752f)) : 1.0f;
-            const float Fm = lo ? 0.5f * (1.0f + erff(am * 0.70710678118654752f)) : 0.0f;
-            const float prob = Fp - Fm;
-            vlb = -logf(fmaxf(prob, 1e-12f));
-            const float pp = up ? 0.3989422804014327f * expf(-0.5f * ap * ap) * ap : 0.f;
-            const float pm = lo ? 0.3989422804014327f * expf(-0.5f * am * am) * am : 0.f;
-            dv = prob >= 1e-12f ? hl * (pp - pm) / prob : 0.f;  // -(1/prob) d(prob)/d(sd) * sd * hl, d Phi(a)/d sd = -phi(a) a / sd
-        } else {  // KL(q(x_{t-1} | x_t, x_0) || p_theta) (losses.py:23-31, torch kl_normal_normal)
-            const float qm = c[4] * x0 + c[5] * xt;
-            const float q = c[6] / sd, ratio = q * q;
-            const float u = (qm - mean) / sd, t1 = u * u;
-            vlb = 0.5f * (ratio + t1 - 1.0f - logf(ratio));
-            dv = hl * (1.0f - ratio - t1);
-        }
         acc_v += vlb;
         if (d_out) {
             d_out[b * 2 * chw + r] = (-2.0f * d) * (w_simple * gscale);
@@ -351,6 +354,267 @@ int launch_iddpm_loss(const float* out, const float* x_t, const float* x_0, cons
                        gscale / (float)total, d_out, scratch);
     DMME_CHECK_LAUNCH();
     hipLaunchKernelGGL(iddpm_loss_final_kernel, dim3(1), dim3(256), 0, s, scratch, (int)g, 1.0f / (float)total, w_simple, w_vlb, loss);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// ------------------------------------------------------------------ Improved DDPM as published: per-image loss rows, prior, timestep resampler
+// (dmme_hip.h: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update).  No kernel here uses a value read
+// from device memory as an index before it has checked it against the table it indexes.
+
+constexpr int ROWS_MAX_PARTS = 32;  // workgroups per image of iddpm_loss_rows_kernel: `scratch` holds 2 * B * ROWS_MAX_PARTS floats at most
+static inline int rows_parts(int64_t chw) {
+    const int64_t p = (chw + 1023) / 1024;
+    return (int)(p > ROWS_MAX_PARTS ? ROWS_MAX_PARTS : (p < 1 ? 1 : p));
+}
+
+// workgroup (b, part) sums its share of image b: partial[(b * parts + part) * 2 + {0, 1}] = sum (target - eps)^2, sum VLB term (plain stores,
+// one owner each).  An image whose t is outside [1, T] reads no table row: its gradient rows become NaN and the final pass flags it.
+__global__ void __launch_bounds__(256) iddpm_loss_rows_kernel(const float* __restrict__ out, const float* __restrict__ x_t, const float* __restrict__ x_0,
+                                                              const float* __restrict__ target, const int64_t* __restrict__ t,
+                                                              const float* __restrict__ coef, int T, const float* __restrict__ weight, int parts,
+                                                              int64_t chw, float w_simple, float w_vlb, float gscale, float* __restrict__ d_out,
+                                                              float* __restrict__ partial) {
+    __shared__ float red[16];
+    const int64_t b = blockIdx.x / parts;
+    const int part = (int)(blockIdx.x - b * parts);
+    const int64_t tt = t[b];
+    const bool valid = tt >= 1 && tt <= (int64_t)T;
+    const float* ob = out + b * 2 * chw;
+    float* db = d_out ? d_out + b * 2 * chw : nullptr;
+    float acc_s = 0.f, acc_v = 0.f;
+    if (valid) {
+        const float* c = coef + tt * 8;
+        const bool weighted = weight != nullptr;
+        const float wb = weighted ? weight[b] : 1.0f;
+        for (int64_t r = (int64_t)part * blockDim.x + threadIdx.x; r < chw; r += (int64_t)parts * blockDim.x) {
+            const int64_t i = b * chw + r;
+            float d, vlb, dv;
+            iddpm_loss_elem(c, tt == 1, ob[r], ob[chw + r], x_t[i], x_0[i], target[i], d, vlb, dv);
+            acc_s += d * d;
+            acc_v += vlb;
+            if (db) {
+                const float ge = (-2.0f * d) * (w_simple * gscale), gv = dv * (w_vlb * gscale);
+                db[r] = weighted ? ge * wb : ge;
+                db[chw + r] = weighted ? gv * wb : gv;
+            }
+        }
+    } else if (db) {
+        const float nan = __int_as_float(0x7fc00000);
+        for (int64_t r = (int64_t)part * blockDim.x + threadIdx.x; r < chw; r += (int64_t)parts * blockDim.x) {
+            db[r] = nan;
+            db[chw + r] = nan;
+        }
+    }
+    const float ts = block_sum(acc_s, red);
+    __syncthreads();
+    const float tv = block_sum(acc_v, red);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = ts;
+        partial[2 * blockIdx.x + 1] = tv;
+    }
+}
+// one workgroup: thread b adds image b's partials in index order, then fixed-order block sums over the images
+__global__ void __launch_bounds__(256) iddpm_loss_rows_final_kernel(const float* __restrict__ partial, int parts, const int64_t* __restrict__ t, int T,
+                                                                    const float* __restrict__ weight, int B, float inv_chw, float w_simple,
+                                                                    float w_vlb, float* __restrict__ loss, float* __restrict__ rows,
+                                                                    int* __restrict__ status) {
+    __shared__ float red[16];
+    const float nan = __int_as_float(0x7fc00000);
+    float a_s = 0.f, a_v = 0.f, a_w = 0.f;
+    bool bad = false;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const int64_t tt = t[b];
+        float S = 0.f, V = 0.f;
+        for (int p = 0; p < parts; ++p) {
+            S += partial[2 * ((int64_t)b * parts + p)];
+            V += partial[2 * ((int64_t)b * parts + p) + 1];
+        }
+        S *= inv_chw;
+        V *= inv_chw;
+        if (tt < 1 || tt > (int64_t)T) {
+            S = nan;
+            V = nan;
+            bad = true;
+        }
+        const float row = w_simple * S + w_vlb * V;
+        rows[b] = S;
+        rows[B + b] = V;
+        rows[2 * B + b] = row;
+        a_s += S;
+        a_v += V;
+        a_w += weight ? weight[b] * row : row;
+    }
+    if (bad && status) *status = 1;
+    const float ts = block_sum(a_s, red);
+    const float tv = block_sum(a_v, red);
+    const float tw = block_sum(a_w, red);
+    if (threadIdx.x == 0) {
+        const float inv_b = 1.0f / (float)B;
+        loss[0] = tw * inv_b;
+        loss[1] = ts * inv_b;
+        loss[2] = tv * inv_b;
+    }
+}
+int launch_iddpm_loss_rows(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int T,
+                           const float* weight, int B, int64_t chw, float w_simple, float w_vlb, float* loss, float* rows, float* d_out,
+                           float gscale, int* status, float* scratch, hipStream_t s) {
+    DMME_REQUIRE(out && x_t && x_0 && target && t && coef && loss && rows && scratch, DMME_ERR_INVALID, "iddpm_loss_rows: null argument");
+    DMME_REQUIRE(B > 0 && chw > 0 && T >= 1, DMME_ERR_INVALID, "iddpm_loss_rows: B = %d images of %lld values, T = %d", B, (long long)chw, T);
+    const int parts = rows_parts(chw);
+    DMME_REQUIRE((int64_t)B * parts <= 0x7fffffff, DMME_ERR_INVALID, "iddpm_loss_rows: B = %d is too large", B);
+    const int64_t total = (int64_t)B * chw;
+    hipLaunchKernelGGL(iddpm_loss_rows_kernel, dim3((unsigned)(B * parts)), dim3(256), 0, s, out, x_t, x_0, target, t, coef, T, weight, parts, chw,
+                       w_simple, w_vlb, gscale / (float)total, d_out, scratch);
+    DMME_CHECK_LAUNCH();
+    hipLaunchKernelGGL(iddpm_loss_rows_final_kernel, dim3(1), dim3(256), 0, s, (const float*)scratch, parts, t, T, weight, B, 1.0f / (float)chw,
+                       w_simple, w_vlb, loss, rows, status);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// prior[b] = 0.5 (k + abar_T mean(x_0^2)), k = -log(1 - abar_T) - abar_T: one workgroup per image.  k is evaluated on the host in double
+// (log1p: the three constant terms of the KL cancel to ~abar_T^2 / 2, far below fp32 next to 1).
+__global__ void __launch_bounds__(256) iddpm_prior_rows_kernel(const float* __restrict__ x_0, int64_t chw, double k, double abar,
+                                                               float* __restrict__ prior) {
+    __shared__ float red[16];
+    const float* xb = x_0 + (int64_t)blockIdx.x * chw;
+    float acc = 0.f;
+    for (int64_t r = threadIdx.x; r < chw; r += blockDim.x) acc += xb[r] * xb[r];
+    const float tot = block_sum(acc, red);
+    if (threadIdx.x == 0) prior[blockIdx.x] = (float)(0.5 * (k + abar * ((double)tot / (double)chw)));
+}
+int launch_iddpm_prior_rows(const float* x_0, int B, int64_t chw, float alpha_bar_T, float* prior, hipStream_t s) {
+    DMME_REQUIRE(x_0 && prior, DMME_ERR_INVALID, "iddpm_prior_rows: null argument");
+    DMME_REQUIRE(B > 0 && chw > 0, DMME_ERR_INVALID, "iddpm_prior_rows: B = %d images of %lld values", B, (long long)chw);
+    DMME_REQUIRE(alpha_bar_T >= 0.0f && alpha_bar_T < 1.0f, DMME_ERR_INVALID, "iddpm_prior_rows: alpha_bar_T = %g is outside [0, 1)", (double)alpha_bar_T);
+    const double ab = (double)alpha_bar_T;
+    hipLaunchKernelGGL(iddpm_prior_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, x_0, chw, -log1p(-ab) - ab, ab, prior);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// Loss-second-moment timestep resampler (Nichol & Dhariwal 2021, section 3.3).  One workgroup: (1) warm iff every count[1..T] == H;
+// (2) s_t = sqrt(mean_k hist[t][k]^2), p_t = (1 - u0) s_t / sum(s) + u0 / T, or 1 / T while not warm (or where sum(s) is not a positive
+// finite number); (3) inclusive fp32 prefix sum of p in LDS: every thread owns a contiguous chunk, sums it from zero, one thread scans
+// the chunk sums, and cdf = chunk offset + running chunk sum, which is non-decreasing across chunk borders too; (4) draw b takes
+// u = uniform b of the Philox span (seed, offset) and t_b = 1 + #{t : cdf_t <= u cdf_T} by bisection, clamped to [1, T].
+constexpr int TSAMPLER_MAX_T = 12288;  // the cdf lives in LDS: 48 KiB
+__global__ void __launch_bounds__(256) tsampler_draw_kernel(const float* __restrict__ hist, const int* __restrict__ count, int T, int H, float u0,
+                                                            uint64_t seed, uint64_t offset, int B, int64_t* __restrict__ t_out,
+                                                            float* __restrict__ w_out, float* __restrict__ p_out) {
+    extern __shared__ float cdf[];  // [T + 1]: s_t, then p_t, then the prefix sums; entry 0 stays 0
+    __shared__ float red[16];
+    __shared__ float chunk_off[257];
+    __shared__ int cold;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    if (tid == 0) {
+        cold = 0;
+        cdf[0] = 0.f;
+    }
+    __syncthreads();
+    bool mine_cold = false;
+    for (int t = 1 + tid; t <= T; t += nt) mine_cold |= count[t] != H;
+    if (mine_cold) cold = 1;  // (every writer stores the same value)
+    __syncthreads();
+    bool warm = cold == 0;
+    float acc = 0.f;
+    if (warm) {
+        for (int t = 1 + tid; t <= T; t += nt) {
+            const float* row = hist + (int64_t)t * H;
+            float q = 0.f;
+            for (int k = 0; k < H; ++k) q += row[k] * row[k];
+            const float s = sqrtf(q / (float)H);
+            cdf[t] = s;
+            acc += s;
+        }
+    }
+    const float sum_s = block_sum(acc, red);
+    warm = warm && sum_s > 0.f && sum_s <= 3.0e38f;  // (false for NaN)
+    const float uni = 1.0f / (float)T;
+    for (int t = 1 + tid; t <= T; t += nt) {
+        const float p = warm ? (1.0f - u0) * cdf[t] / sum_s + u0 / (float)T : uni;
+        cdf[t] = p;
+        p_out[t] = p;
+    }
+    if (tid == 0) p_out[0] = 0.f;
+    __threadfence_block();
+    __syncthreads();
+    const int per = (T + nt - 1) / nt, lo = 1 + tid * per, hi = min(T, lo + per - 1);
+    float run = 0.f;
+    for (int t = lo; t <= hi; ++t) run += cdf[t];
+    chunk_off[tid + 1] = run;
+    __syncthreads();
+    if (tid == 0) {
+        chunk_off[0] = 0.f;
+        for (int k = 1; k <= nt; ++k) chunk_off[k] = chunk_off[k - 1] + chunk_off[k];
+    }
+    __syncthreads();
+    const float base = chunk_off[tid];
+    run = 0.f;
+    for (int t = lo; t <= hi; ++t) {
+        run += cdf[t];
+        cdf[t] = base + run;
+    }
+    __syncthreads();
+    const float top = cdf[T];
+    for (int b = tid; b < B; b += nt) {
+        uint32_t r[4];
+        philox4x32_10(seed, offset + (uint64_t)(b >> 2), r);
+        const float x = u01(r[b & 3]) * top;
+        int a = 1, e = T + 1;  // first t in [1, T + 1) with cdf[t] > x; T + 1 when there is none
+        while (a < e) {
+            const int m = (a + e) >> 1;
+            if (cdf[m] <= x) a = m + 1; else e = m;
+        }
+        const int tb = a > T ? T : a;  // 1 + #{t : cdf_t <= x}, kept inside the table
+        t_out[b] = tb;
+        w_out[b] = warm ? 1.0f / ((float)T * p_out[tb]) : 1.0f;
+    }
+}
+int launch_tsampler_draw(const float* hist, const int* count, int T, int H, float uniform_prob, uint64_t seed, uint64_t offset, int B, int64_t* t,
+                         float* weight, float* p, hipStream_t s) {
+    DMME_REQUIRE(hist && count && t && weight && p, DMME_ERR_INVALID, "tsampler_draw: null argument");
+    DMME_REQUIRE(B > 0 && T >= 1 && H >= 1, DMME_ERR_INVALID, "tsampler_draw: B = %d, T = %d, H = %d", B, T, H);
+    DMME_REQUIRE(uniform_prob >= 0.0f && uniform_prob <= 1.0f, DMME_ERR_INVALID, "tsampler_draw: uniform_prob = %g is outside [0, 1]", (double)uniform_prob);
+    DMME_REQUIRE(T <= TSAMPLER_MAX_T, DMME_ERR_UNSUPPORTED, "tsampler_draw: T = %d is above %d", T, TSAMPLER_MAX_T);
+    hipLaunchKernelGGL(tsampler_draw_kernel, dim3(1), dim3(256), (size_t)(T + 1) * sizeof(float), s, hist, count, T, H, uniform_prob, seed, offset, B,
+                       t, weight, p);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// push (t_b, L_b), b = 0 .. B-1, in index order: the thread that owns timestep t walks the batch and is the only writer of row t and
+// count[t].  count[t] is clamped to [0, H] before it positions a store.  The owner of t = 1 also flags the entries nobody takes.
+__global__ void __launch_bounds__(256) tsampler_update_kernel(float* __restrict__ hist, int* __restrict__ count, int T, int H,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ L, int B,
+                                                              int* __restrict__ status) {
+    const int own = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (own > T) return;
+    float* row = hist + (int64_t)own * H;
+    int c = count[own];
+    c = c < 0 ? 0 : (c > H ? H : c);
+    bool bad = false;
+    for (int b = 0; b < B; ++b) {
+        const int64_t tb = t[b];
+        const float v = L[b];
+        const bool finite = fabsf(v) <= 3.4028234e38f;  // (false for NaN)
+        if (own == 1 && (tb < 1 || tb > (int64_t)T || !finite)) bad = true;
+        if (tb != (int64_t)own || !finite) continue;
+        if (c < H) {
+            row[c++] = v;
+        } else {
+            for (int k = 0; k + 1 < H; ++k) row[k] = row[k + 1];
+            row[H - 1] = v;
+        }
+    }
+    count[own] = c;
+    if (bad && status) *status = 1;
+}
+int launch_tsampler_update(float* hist, int* count, int T, int H, const int64_t* t, const float* L, int B, int* status, hipStream_t s) {
+    DMME_REQUIRE(hist && count && t && L, DMME_ERR_INVALID, "tsampler_update: null argument");
+    DMME_REQUIRE(B > 0 && T >= 1 && H >= 1, DMME_ERR_INVALID, "tsampler_update: B = %d, T = %d, H = %d", B, T, H);
+    hipLaunchKernelGGL(tsampler_update_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, hist, count, T, H, t, L, B, status);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

@@ -1398,7 +1398,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 108; }  // 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 109; }  // 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1779,6 +1779,26 @@ DMME_API int dmme_iddpm_loss(const float* model_out, const float* x_t, const flo
                  "iddpm_loss: bad argument");
     return launch_iddpm_loss(model_out, x_t, x_0, target, t, coef, B, chw, w_simple, w_vlb, loss, d_out, grad_scale, scratch,
                              (hipStream_t)stream);
+}
+
+DMME_API int dmme_iddpm_loss_rows(const float* model_out, const float* x_t, const float* x_0, const float* target, const int64_t* t,
+                                  const float* coef, int T, const float* weight, int B, int64_t chw, float w_simple, float w_vlb, float* loss,
+                                  float* rows, float* d_out, float grad_scale, int* status, float* scratch, void* stream) {
+    return launch_iddpm_loss_rows(model_out, x_t, x_0, target, t, coef, T, weight, B, chw, w_simple, w_vlb, loss, rows, d_out, grad_scale, status,
+                                  scratch, (hipStream_t)stream);
+}
+
+DMME_API int dmme_iddpm_prior_rows(const float* x_0, int B, int64_t chw, float alpha_bar_T, float* prior, void* stream) {
+    return launch_iddpm_prior_rows(x_0, B, chw, alpha_bar_T, prior, (hipStream_t)stream);
+}
+
+DMME_API int dmme_tsampler_draw(const float* hist, const int* count, int T, int H, float uniform_prob, uint64_t philox_seed,
+                                uint64_t philox_offset, int B, int64_t* t, float* weight, float* p, void* stream) {
+    return launch_tsampler_draw(hist, count, T, H, uniform_prob, philox_seed, philox_offset, B, t, weight, p, (hipStream_t)stream);
+}
+
+DMME_API int dmme_tsampler_update(float* hist, int* count, int T, int H, const int64_t* t, const float* L, int B, int* status, void* stream) {
+    return launch_tsampler_update(hist, count, T, H, t, L, B, status, (hipStream_t)stream);
 }
 
 DMME_API int dmme_mse_loss(const float* eps, const float* target, int64_t numel, float* loss, float* d_eps, float grad_scale,

@@ -4,7 +4,9 @@ as the reference; the per-pixel math runs in the HIP kernels dmme_iddpm_step / d
 from __future__ import annotations
 
 import math
+from typing import List, Sequence
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -45,3 +47,33 @@ def process_coefficients(beta: Tensor, alpha: Tensor, alpha_bar: Tensor) -> Tens
     tab[1:, 5] = torch.sqrt(at) * (1 - abp) / (1 - abt)
     tab[1:, 6] = torch.sqrt(beta_tilde)
     return tab
+
+
+def space_timesteps(timesteps: int, sample_steps: int) -> List[int]:
+    r"""the K timesteps of a strided sampling chain (Nichol & Dhariwal 2021, section 4), evenly spaced over 1..T with both ends kept:
+    s_k = 1 + round((k - 1)(T - 1)/(K - 1)), k = 1..K, with Python's round (half to even, as in the paper's code).  s_1 = 1, s_K = T."""
+    T, K = int(timesteps), int(sample_steps)
+    if not 2 <= K <= T:
+        raise ValueError(f"sample_steps = {sample_steps} must lie in [2, timesteps = {timesteps}]")
+    return [1 + round((k - 1) * (T - 1) / (K - 1)) for k in range(1, K + 1)]
+
+
+def respaced_coefficients(alpha_bar: Tensor, steps: Sequence[int]) -> Tensor:
+    r"""(K+1, 4) fp32 rows of the DMME_CHAIN_IDDPM update for the chain that visits only `steps` = s_1 < ... < s_K; row k is the step
+    s_k -> s_{k-1} (s_0 = 0, abar_{s_0} = 1) and row 0 is zero (never stepped from).  In float64 from the registered alpha_bar:
+      beta'_k = min(1 - abar_{s_k}/abar_{s_{k-1}}, 0.999)   (the constructor's clip)
+      beta~'_k = beta'_k (1 - abar_{s_{k-1}})/(1 - abar_{s_k})
+      row k = {1/sqrt(1 - beta'_k), beta'_k/sqrt(1 - abar_{s_k}), log beta'_k, log max(beta~'_k, 1e-12)}, each rounded once to fp32."""
+    ab = alpha_bar.detach().reshape(-1).to(torch.float64).cpu().numpy()
+    s = [int(v) for v in steps]
+    if not s or s[0] < 1 or s[-1] >= ab.size or any(b <= a for a, b in zip(s, s[1:])):
+        raise ValueError("steps must be strictly increasing timesteps inside 1..T")
+    cur, prev = ab[s], np.concatenate([[1.0], ab[s[:-1]]])
+    beta = np.minimum(1.0 - cur / prev, 0.999)
+    beta_tilde = beta * (1.0 - prev) / (1.0 - cur)
+    rows = np.zeros((len(s) + 1, 4), dtype=np.float64)
+    rows[1:, 0] = 1.0 / np.sqrt(1.0 - beta)
+    rows[1:, 1] = beta / np.sqrt(1.0 - cur)
+    rows[1:, 2] = np.log(beta)
+    rows[1:, 3] = np.log(np.maximum(beta_tilde, 1e-12))
+    return torch.from_numpy(rows.astype(np.float32))

@@ -26,9 +26,14 @@ class LitIDDPM(LitDDPM):
         offset: float = 0.008,
         start: float = 0.0001,
         end: float = 0.02,
+        t_sampler: str = "uniform",
     ):
         if diffusion_model is None:
             if model is None:
                 model = UNet()
-            diffusion_model = IDDPM(model, timesteps, loss_type, gamma, schedule, offset, start, end)
+            diffusion_model = IDDPM(model, timesteps, loss_type, gamma, schedule, offset, start, end, t_sampler)
         super().__init__(lr, warmup, decay, diffusion_model)
+
+    def generate(self, img_size, sample_steps: Optional[int] = None):
+        """`sample_steps` = K: the strided K-step chain with the learned variance (IDDPM.generate)"""
+        return self.diffusion_model.generate(img_size=img_size, sample_steps=sample_steps)

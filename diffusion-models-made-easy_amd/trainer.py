@@ -17,6 +17,7 @@ checkpoint callbacks, ...):
 
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml [--max-steps N] [--batch-size B]
   python -m dmme_amd.trainer sample --config configs/ddim/cifar10.yaml [--num-images N] [--steps K] [--sampler ddim-paper --eta E]
+  python -m dmme_amd.trainer sample --config configs/iddpm/cifar10.yaml --sample-steps K    (Improved DDPM: K << T strided steps)
 """
 
 from __future__ import annotations
@@ -213,12 +214,22 @@ def main(argv=None):
     ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table")
     ap.add_argument("--eta", type=float, default=0.0, help="sample --sampler ddim-paper: 0 deterministic ... 1 DDPM's posterior variance")
+    ap.add_argument("--sample-steps", type=int, default=None,
+                    help="sample, Improved DDPM configs: a strided chain over this many of the T timesteps, with the learned variance")
     args = ap.parse_args(argv)
 
     from . import _lib
     from . import distributed as D
 
     conf = parse_config(args.config)
+    if args.sample_steps is not None:
+        from .lit_modules import LitIDDPM
+
+        cls = _resolve(conf["model_spec"]["class_path"])
+        if not (isinstance(cls, type) and issubclass(cls, LitIDDPM)):
+            raise SystemExit("--sample-steps needs an Improved DDPM config (LitIDDPM: the strided chain uses the learned variance)")
+        if args.command != "sample" or args.steps is not None or args.sampler != "config":
+            raise SystemExit("--sample-steps belongs to `sample` and replaces --steps / --sampler")
     if args.precision:
         conf["precision"] = conf["sample_precision"] = args.precision
     if args.command == "sample":
@@ -252,7 +263,9 @@ def main(argv=None):
         t0 = time.perf_counter()
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)
-        if args.steps is None:
+        if args.sample_steps is not None:
+            imgs = module.generate(shape, sample_steps=args.sample_steps)
+        elif args.steps is None:
             imgs = module.generate(shape)
         else:
             import dmme_amd

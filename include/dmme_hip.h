@@ -448,6 +448,47 @@ DMME_API int dmme_iddpm_loss(const float* model_out, const float* x_t, const flo
                     const float* coef, int B, int64_t chw, float w_simple, float w_vlb, float* loss, float* d_out,
                     float grad_scale, float* scratch, void* stream);
 
+/* ---- Improved DDPM as published (Nichol & Dhariwal 2021): per-image loss rows for importance-weighted L_vlb and for bits/dim, the prior
+ * term of the bound, and the loss-second-moment timestep resampler (section 3.3).  These entry points take T and never use a device-side
+ * value as an index before checking it against the table it indexes. */
+
+/* dmme_iddpm_loss with per-image rows, optional importance weights and a checked t.  Per element the arithmetic is dmme_iddpm_loss's.
+ *   rows[0][b] = S_b = mean over image b of (target - eps)^2
+ *   rows[1][b] = V_b = mean over image b of the VLB term (discrete NLL where t[b] == 1, KL elsewhere), in nats/dim
+ *   rows[2][b] = w_simple S_b + w_vlb V_b                                   (rows: 3 x B floats)
+ *   loss[1] = mean_b S_b, loss[2] = mean_b V_b (both unweighted), loss[0] = (1/B) sum_b weight[b] rows[2][b]   (3 floats)
+ *   d_out (optional, B x 2C x H x W) = what dmme_iddpm_loss writes, times weight[b].  weight == NULL stands for all ones and skips the
+ *   multiply: d_out is then bit-identical to dmme_iddpm_loss's.
+ * A t[b] outside [1, T] reads no row of coef: rows[.][b], loss[0..2] and image b of d_out become NaN and *status (nullable, device int) is
+ * set to 1, as by dmme_log_softmax_grad.  Two launches, no atomics: up to 32 workgroups per image leave partial sums in `scratch`
+ * (64 * B floats), one workgroup adds them in index order, so equal inputs give equal bits.  chw is free (no multiple of 4 needed). */
+DMME_API int dmme_iddpm_loss_rows(const float* model_out, const float* x_t, const float* x_0, const float* target, const int64_t* t,
+                                  const float* coef, int T, const float* weight, int B, int64_t chw, float w_simple, float w_vlb, float* loss,
+                                  float* rows, float* d_out, float grad_scale, int* status, float* scratch, void* stream);
+
+/* prior term of the variational bound, KL(q(x_T | x_0) || N(0, I)) per image in nats/dim:
+ *   prior[b] = mean over image b of 0.5 (-log(1 - abar_T) - 1 + (1 - abar_T) + abar_T x_0^2),   0 <= alpha_bar_T < 1.
+ * The three constant terms are folded on the host in double (they cancel to about abar_T^2 / 2). */
+DMME_API int dmme_iddpm_prior_rows(const float* x_0, int B, int64_t chw, float alpha_bar_T, float* prior, void* stream);
+
+/* draw t[B] and weight[B] from the loss history.  Caller-owned device state: hist float[T+1][H] (row 0 unused), count int32[T+1].
+ *   warm  iff count[t] == H for every t in 1..T
+ *   p[t]  = 1/T while not warm; else (1 - uniform_prob) s_t / sum(s) + uniform_prob / T with s_t = sqrt(mean_k hist[t][k]^2)
+ *           (also 1/T where sum(s) is not a positive finite number).  p: float[T+1] output, p[0] = 0.
+ *   u_b   = uniform b of the Philox span (philox_seed, philox_offset in quads): word b % 4 of quad b / 4, ((x >> 8) + 1) / 2^24
+ *   t[b]  = 1 + #{t : cdf_t <= u_b cdf_T}, cdf the inclusive fp32 prefix sum of p, clamped to [1, T]: 1..T inclusive - T is reachable,
+ *           unlike under the reference's uniform_int(1, T), or a history would never fill
+ *   weight[b] = 1 / (T p[t[b]]); exactly 1.0f while not warm.
+ * One workgroup (scan, then bisection); the prefix sums live in LDS: T <= 12288, DMME_ERR_UNSUPPORTED above. */
+DMME_API int dmme_tsampler_draw(const float* hist, const int* count, int T, int H, float uniform_prob, uint64_t philox_seed,
+                                uint64_t philox_offset, int B, int64_t* t, float* weight, float* p, void* stream);
+
+/* push (t[b], L[b]), b = 0..B-1, into the history, with the result of doing so in index order: count[t] < H: hist[t][count[t]++] = L;
+ * otherwise row t moves left by one and hist[t][H-1] = L.  Values are copied, never recomputed.  One thread owns each timestep and walks
+ * the batch, so a timestep that occurs many times (more than H times too) needs no atomics.  An entry whose t[b] is outside [1, T] or
+ * whose L[b] is not finite is skipped (a NaN in the history would poison p for good) and sets *status (nullable, device int) to 1. */
+DMME_API int dmme_tsampler_update(float* hist, int* count, int T, int H, const int64_t* t, const float* L, int B, int* status, void* stream);
+
 /* ---- single-op entry points used by the unit parity tests ---------------------------
  * Activations here are NHWC in the compute dtype; weights in the packed layout
  * [Cout][taps][Cin]; they exercise exactly the kernels the plan launches.
