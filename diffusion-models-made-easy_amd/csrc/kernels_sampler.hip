@@ -122,87 +122,94 @@ int launch_q_sample(const float* x0, const float* z, const float* sqrt_abar, con
 }
 
 // ------------------------------------------------------------------ reverse updates
-// explicitly rounded ops (never contracted into fma): same rounding sequence as the
-// reference's separate torch ops
-__device__ __forceinline__ float ddpm_update(float x, float e, float z, float c1, float c2, float sigma, int add_noise) {
-    const float m = __fmul_rn(c1, __fsub_rn(x, __fmul_rn(c2, e)));
-    return add_noise ? __fadd_rn(m, __fmul_rn(sigma, z)) : m;
+// One element function per sampler kind (DMME_CHAIN_*, dmme_hip.h), used by the eager kernel (host scalars, z from memory) and by the
+// chain kernel (scalars from device tables, z drawn in the kernel): the two agree bit for bit because they run the same code.  Every
+// operation is explicitly rounded (never contracted into fma): the rounding sequence of the reference's separate torch ops.
+//   c0..c3: DDPM  1/sqrt(alpha_t), beta_t/sqrt(1-abar_t), sqrt(beta_t), -      IDDPM  as DDPM, then log beta_t, log max(beta~_t, 1e-12)
+//           DDIM  sqrt(1-abar_tau_i), sqrt(abar_tau_{i-1}), -, -               GDDIM  k0, k1, k2, - (dmme_hip.h: dmme_gddim_step)
+//           DDPM_GUIDED  as DDPM, then s beta_t                                DDIM_GUIDED  as DDIM, then s sqrt(1-abar_tau_i)
+__device__ __forceinline__ float ddpm_mean(float x, float e, float c0, float c1) { return __fmul_rn(c0, __fsub_rn(x, __fmul_rn(c1, e))); }
+// the DDIM update as the reference ships it: sqrt(abar_prev) * x0_hat, x0_hat = (x - sqrt(1-abar) eps) / sqrt(abar_prev)
+__device__ __forceinline__ float ddim_collapse(float x, float e, float c0, float c1) {
+    return __fmul_rn(c1, __fdiv_rn(__fsub_rn(x, __fmul_rn(c0, e)), c1));
 }
-__global__ void __launch_bounds__(256) ddpm_step_kernel(float* __restrict__ x, const float* __restrict__ eps,
-                                                        const float* __restrict__ z, float c1, float c2, float sigma,
-                                                        int add_noise, int64_t n4, int64_t numel) {
+// Sigma = exp(v log beta_t + (1 - v) log max(beta~_t, 1e-12)) (equations/iddpm/losses.py:34-37)
+__device__ __forceinline__ float iddpm_std(float v, float log_beta, float log_beta_tilde) {
+    return sqrtf(expf(__fadd_rn(__fmul_rn(v, log_beta), __fmul_rn(__fsub_rn(1.0f, v), log_beta_tilde))));
+}
+// e: predicted noise, v: learned-variance output (IDDPM), g: d log p(y | x_t, t) / d x_t (guided kinds), z: a normal, read where add_noise
+template <int KIND>
+__device__ __forceinline__ float sampler_update(float x, float e, float v, float g, float z, float c0, float c1, float c2, float c3, int add_noise) {
+    if (KIND == DMME_CHAIN_DDIM) return ddim_collapse(x, e, c0, c1);
+    if (KIND == DMME_CHAIN_DDIM_GUIDED) return ddim_collapse(x, __fsub_rn(e, __fmul_rn(c2, g)), c0, c1);
+    float m;
+    if (KIND == DMME_CHAIN_GDDIM) {  // paper form (Song et al. 2021, eq. 12), any eta, either direction: (k0 x + k1 eps) + k2 z
+        m = __fadd_rn(__fmul_rn(c0, x), __fmul_rn(c1, e));
+    } else {
+        m = ddpm_mean(x, e, c0, c1);
+        if (KIND == DMME_CHAIN_DDPM_GUIDED) m = __fadd_rn(m, __fmul_rn(c3, g));  // (the shift stays at t == 1)
+    }
+    return add_noise ? __fadd_rn(m, __fmul_rn(KIND == DMME_CHAIN_IDDPM ? iddpm_std(v, c2, c3) : c2, z)) : m;
+}
+// where element i's predicted noise lies in the network output: IDDPM's is [B][2][chw] (eps plane, then the v plane chw further on),
+// every other kind's has x's own layout
+template <int KIND>
+__device__ __forceinline__ int64_t eps_at(int64_t i, int64_t chw) {
+    return KIND == DMME_CHAIN_IDDPM ? i + (i / chw) * chw : i;
+}
+__device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// The eager update, in place on x: one thread per quad, 16-byte accesses where the quad is whole and (IDDPM) lies inside one image, which
+// it does, aligned in both planes, exactly when chw % 4 == 0; element by element otherwise.  z is read only where add_noise.
+template <int KIND>
+__global__ void __launch_bounds__(256) eager_update_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ z, float c0,
+                                                           float c1, float c2, float c3, int add_noise, int64_t chw, int64_t n4, int64_t numel) {
+    constexpr bool LEARNED = KIND == DMME_CHAIN_IDDPM;
+    const bool quads_fit = !LEARNED || chw % 4 == 0;
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = q * 4;
-        if (b + 3 < numel) {
-            float4 xv = *reinterpret_cast<const float4*>(x + b);
-            const float4 ev = *reinterpret_cast<const float4*>(eps + b);
-            float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (add_noise) zv = *reinterpret_cast<const float4*>(z + b);
-            xv.x = ddpm_update(xv.x, ev.x, zv.x, c1, c2, sigma, add_noise);
-            xv.y = ddpm_update(xv.y, ev.y, zv.y, c1, c2, sigma, add_noise);
-            xv.z = ddpm_update(xv.z, ev.z, zv.z, c1, c2, sigma, add_noise);
-            xv.w = ddpm_update(xv.w, ev.w, zv.w, c1, c2, sigma, add_noise);
+        if (b + 3 < numel && quads_fit) {
+            const int64_t eo = eps_at<KIND>(b, chw);
+            float4 xv = load4(x + b), vv = make_float4(0.f, 0.f, 0.f, 0.f), zv = vv;
+            const float4 ev = load4(out + eo);
+            if (add_noise) zv = load4(z + b);
+            if (LEARNED && add_noise) vv = load4(out + eo + chw);
+            xv.x = sampler_update<KIND>(xv.x, ev.x, vv.x, 0.f, zv.x, c0, c1, c2, c3, add_noise);
+            xv.y = sampler_update<KIND>(xv.y, ev.y, vv.y, 0.f, zv.y, c0, c1, c2, c3, add_noise);
+            xv.z = sampler_update<KIND>(xv.z, ev.z, vv.z, 0.f, zv.z, c0, c1, c2, c3, add_noise);
+            xv.w = sampler_update<KIND>(xv.w, ev.w, vv.w, 0.f, zv.w, c0, c1, c2, c3, add_noise);
             *reinterpret_cast<float4*>(x + b) = xv;
         } else {
-            for (int64_t i = b; i < numel; ++i) x[i] = ddpm_update(x[i], eps[i], add_noise ? z[i] : 0.f, c1, c2, sigma, add_noise);
+            for (int64_t i = b; i < b + 4 && i < numel; ++i) {
+                const int64_t eo = eps_at<KIND>(i, chw);
+                x[i] = sampler_update<KIND>(x[i], out[eo], LEARNED && add_noise ? out[eo + chw] : 0.f, 0.f, add_noise ? z[i] : 0.f, c0, c1, c2, c3,
+                                            add_noise);
+            }
         }
     }
 }
-int launch_ddpm_step(float* x, const float* eps, const float* z, float c1, float c2, float sigma, int add_noise,
-                     int64_t numel, hipStream_t s) {
+template <int KIND>
+static int launch_eager_update(float* x, const float* out, const float* z, float c0, float c1, float c2, float c3, int add_noise, int64_t chw,
+                               int64_t numel, hipStream_t s) {
     if (numel <= 0) return DMME_OK;
     const int64_t n4 = (numel + 3) / 4;
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(n4)), dim3(256), 0, s, x, eps, z, c1, c2, sigma, add_noise, n4, numel);
+    hipLaunchKernelGGL(eager_update_kernel<KIND>, dim3(grid_for(n4)), dim3(256), 0, s, x, out, z, c0, c1, c2, c3, add_noise, chw, n4, numel);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
-
-__global__ void __launch_bounds__(256) ddim_step_kernel(float* __restrict__ x, const float* __restrict__ eps, float s1,
-                                                        float s2, int64_t numel) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x0_hat = __fdiv_rn(__fsub_rn(x[i], __fmul_rn(s1, eps[i])), s2);
-        x[i] = __fmul_rn(s2, x0_hat);
-    }
+int launch_ddpm_step(float* x, const float* eps, const float* z, float c1, float c2, float sigma, int add_noise, int64_t numel, hipStream_t s) {
+    return launch_eager_update<DMME_CHAIN_DDPM>(x, eps, z, c1, c2, sigma, 0.f, add_noise, 0, numel, s);
 }
 int launch_ddim_step(float* x, const float* eps, float s1, float s2, int64_t numel, hipStream_t s) {
-    if (numel <= 0) return DMME_OK;
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(numel)), dim3(256), 0, s, x, eps, s1, s2, numel);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-
-// Paper-form DDIM (Song et al. 2021, eq. 12) for every eta and both directions as one linear form: x' = (k0 x + k1 eps) + k2 z,
-// each product and sum rounded on its own (the host folds the square roots into k0..k2 in float64; dmme_hip.h: dmme_gddim_step).
-// z is read only where k2 != 0.
-__device__ __forceinline__ float gddim_update(float x, float e, float z, float k0, float k1, float k2) {
-    const float m = __fadd_rn(__fmul_rn(k0, x), __fmul_rn(k1, e));
-    return k2 != 0.0f ? __fadd_rn(m, __fmul_rn(k2, z)) : m;
-}
-__global__ void __launch_bounds__(256) gddim_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ z,
-                                                         float k0, float k1, float k2, int64_t n4, int64_t numel) {
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = q * 4;
-        if (b + 3 < numel) {
-            float4 xv = *reinterpret_cast<const float4*>(x + b);
-            const float4 ev = *reinterpret_cast<const float4*>(eps + b);
-            float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (k2 != 0.0f) zv = *reinterpret_cast<const float4*>(z + b);
-            xv.x = gddim_update(xv.x, ev.x, zv.x, k0, k1, k2);
-            xv.y = gddim_update(xv.y, ev.y, zv.y, k0, k1, k2);
-            xv.z = gddim_update(xv.z, ev.z, zv.z, k0, k1, k2);
-            xv.w = gddim_update(xv.w, ev.w, zv.w, k0, k1, k2);
-            *reinterpret_cast<float4*>(x + b) = xv;
-        } else {
-            for (int64_t i = b; i < numel; ++i) x[i] = gddim_update(x[i], eps[i], k2 != 0.0f ? z[i] : 0.f, k0, k1, k2);
-        }
-    }
+    return launch_eager_update<DMME_CHAIN_DDIM>(x, eps, nullptr, s1, s2, 0.f, 0.f, 0, 0, numel, s);
 }
 int launch_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, hipStream_t s) {
-    if (numel <= 0) return DMME_OK;
-    const int64_t n4 = (numel + 3) / 4;
-    hipLaunchKernelGGL(gddim_step_kernel, dim3(grid_for(n4)), dim3(256), 0, s, x, eps, z, k0, k1, k2, n4, numel);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
+    return launch_eager_update<DMME_CHAIN_GDDIM>(x, eps, z, k0, k1, k2, 0.f, k2 != 0.0f, 0, numel, s);  // z is read only where k2 != 0
+}
+// network output (B, 2C, H, W): channels [0, C) = eps, [C, 2C) = v (diffusion_models/iddpm.py:159)
+int launch_iddpm_step(float* x, const float* out, const float* z, float c1, float c2, float log_beta, float log_beta_tilde, int add_noise, int B,
+                      int64_t chw, hipStream_t s) {
+    return launch_eager_update<DMME_CHAIN_IDDPM>(x, out, z, c1, c2, log_beta, log_beta_tilde, add_noise, chw, (int64_t)B * chw, s);
 }
 
 // ------------------------------------------------------------------ MSE loss (+ gradient)
@@ -240,36 +247,6 @@ int launch_mse(const float* eps, const float* target, int64_t numel, float* loss
 }
 
 // ------------------------------------------------------------------ Improved DDPM (learned variance)
-// network output (B, 2C, H, W): channels [0, C) = eps, [C, 2C) = v (diffusion_models/iddpm.py:159).
-// Sigma = exp(v log beta_t + (1 - v) log max(beta~_t, 1e-12)) (equations/iddpm/losses.py:34-37).
-__device__ __forceinline__ float iddpm_std(float v, float log_beta, float log_beta_tilde) {
-    return sqrtf(expf(__fadd_rn(__fmul_rn(v, log_beta), __fmul_rn(__fsub_rn(1.0f, v), log_beta_tilde))));
-}
-__global__ void __launch_bounds__(256) iddpm_step_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ z,
-                                                         float c1, float c2, float log_beta, float log_beta_tilde, int add_noise,
-                                                         int64_t chw, int64_t total) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = i / chw, r = i - b * chw;
-        const float e = out[b * 2 * chw + r];
-        const float m = __fmul_rn(c1, __fsub_rn(x[i], __fmul_rn(c2, e)));
-        if (add_noise) {
-            const float sd = iddpm_std(out[b * 2 * chw + chw + r], log_beta, log_beta_tilde);
-            x[i] = __fadd_rn(m, __fmul_rn(sd, z[i]));
-        } else {
-            x[i] = m;
-        }
-    }
-}
-int launch_iddpm_step(float* x, const float* out, const float* z, float c1, float c2, float log_beta, float log_beta_tilde,
-                      int add_noise, int B, int64_t chw, hipStream_t s) {
-    const int64_t total = (int64_t)B * chw;
-    if (total <= 0) return DMME_OK;
-    hipLaunchKernelGGL(iddpm_step_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, out, z, c1, c2, log_beta, log_beta_tilde, add_noise, chw,
-                       total);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-
 // Hybrid / VLB loss and its gradient w.r.t. the raw network output, one pass (diffusion_models/iddpm.py:62-116,
 // equations/iddpm/losses.py:9-98).  coef: per-timestep fp32 table, 8 floats per t:
 //   [0] 1/sqrt(alpha_t)  [1] beta_t/sqrt(1-abar_t)  [2] log beta_t  [3] log max(beta~_t, 1e-12)
@@ -644,93 +621,40 @@ __global__ void chain_set_kernel(ChainState* st, long long i, const long long* _
     st->pad = 0u;
 }
 
-// KIND 0: DDPM (coef = 1/sqrt(alpha), beta/sqrt(1-abar), sqrt(beta)), 1: DDIM (sqrt(1-abar_tau_i), sqrt(abar_tau_{i-1})),
-//      2: IDDPM (1/sqrt(alpha), beta/sqrt(1-abar), log beta, log max(beta~, 1e-12)); `out` has 2*chw values per image then
-//      3: classifier-guided DDPM (coef 0..2 as DDPM, coef[3] = s beta_t): x = mean + s beta_t g (+ sqrt(beta_t) z)
-//      4: classifier-guided DDIM (coef 0..1 as DDIM, coef[2] = s sqrt(1-abar_tau_i)): eps' = eps - s sqrt(1-abar_tau_i) g, then DDIM
-//      5: paper-form DDIM, any eta, either direction (coef = k0, k1, k2): x = (k0 x + k1 eps) + k2 z; z drawn only where k2 != 0
-// g: d log p(y | x_t, t) / d x_t (guided kinds); zin (nullable, kinds 3 and 5): normals to use instead of the drawn ones (tests)
+// KIND: a DMME_CHAIN_* constant; coef[i][0..3] are c0..c3 of sampler_update<KIND> at loop index i.  The kinds with a DDPM mean add noise
+// where t != 1, the paper-form DDIM kind where k2 != 0, the shipped DDIM kinds never; the offset advances by n4 at every step all the same
+// (the reference draws and discards at t == 1).  IDDPM: `out` has 2*chw values per image.
+// g: d log p(y | x_t, t) / d x_t (guided kinds); zin (nullable; DDPM_GUIDED and GDDIM): normals to use instead of the drawn ones (tests)
 template <int KIND>
 __global__ void __launch_bounds__(256) chain_update_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ coef,
                                                            const long long* __restrict__ t_table, ChainState* st, int64_t chw, int64_t n4,
-                                                           const float* __restrict__ g = nullptr, const float* __restrict__ zin = nullptr) {
+                                                           const float* __restrict__ g, const float* __restrict__ zin) {
+    constexpr bool DRAWS = KIND != DMME_CHAIN_DDIM && KIND != DMME_CHAIN_DDIM_GUIDED;
+    constexpr bool TAKES_ZIN = KIND == DMME_CHAIN_DDPM_GUIDED || KIND == DMME_CHAIN_GDDIM;
     const long long i = st->i, t = st->t;
     const unsigned long long off = st->offset, seed = st->seed;
     const float c0 = coef[4 * i], c1 = coef[4 * i + 1], c2 = coef[4 * i + 2], c3 = coef[4 * i + 3];
-    const int add_noise = t != 1;
+    const int add_noise = KIND == DMME_CHAIN_GDDIM ? c2 != 0.0f : t != 1;
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = q * 4;
-        float4 xv = *reinterpret_cast<const float4*>(x + b);
-        float* xs = reinterpret_cast<float*>(&xv);
-        if (KIND == 1) {
-            const float4 ev = *reinterpret_cast<const float4*>(out + b);
-            const float* es = reinterpret_cast<const float*>(&ev);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xs[j] = __fmul_rn(c1, __fdiv_rn(__fsub_rn(xs[j], __fmul_rn(c0, es[j])), c1));
-        } else if (KIND == 4) {
-            const float4 ev = *reinterpret_cast<const float4*>(out + b);
-            const float4 gv = *reinterpret_cast<const float4*>(g + b);
-            const float* es = reinterpret_cast<const float*>(&ev);
-            const float* gs = reinterpret_cast<const float*>(&gv);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float e = __fsub_rn(es[j], __fmul_rn(c2, gs[j]));
-                xs[j] = __fmul_rn(c1, __fdiv_rn(__fsub_rn(xs[j], __fmul_rn(c0, e)), c1));
-            }
-        } else if (KIND == 5) {
-            float z[4] = {0.f, 0.f, 0.f, 0.f};
-            if (c2 != 0.0f) {  // (the offset advances whether or not the draw is used, as at t == 1 of the DDPM kind)
-                if (zin) {
-                    const float4 zv = *reinterpret_cast<const float4*>(zin + b);
-                    z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-                } else {
-                    normal4(seed, off + (uint64_t)q, z);
-                }
-            }
-            const float4 ev = *reinterpret_cast<const float4*>(out + b);
-            const float* es = reinterpret_cast<const float*>(&ev);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xs[j] = gddim_update(xs[j], es[j], z[j], c0, c1, c2);
-        } else if (KIND == 3) {
-            float z[4] = {0.f, 0.f, 0.f, 0.f};
-            if (add_noise) {
-                if (zin) {
-                    const float4 zv = *reinterpret_cast<const float4*>(zin + b);
-                    z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-                } else {
-                    normal4(seed, off + (uint64_t)q, z);
-                }
-            }
-            const float4 ev = *reinterpret_cast<const float4*>(out + b);
-            const float4 gv = *reinterpret_cast<const float4*>(g + b);
-            const float* es = reinterpret_cast<const float*>(&ev);
-            const float* gs = reinterpret_cast<const float*>(&gv);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float m = __fadd_rn(__fmul_rn(c0, __fsub_rn(xs[j], __fmul_rn(c1, es[j]))), __fmul_rn(c3, gs[j]));  // (the shift stays at t == 1)
-                xs[j] = add_noise ? __fadd_rn(m, __fmul_rn(c2, z[j])) : m;
-            }
-        } else {
-            float z[4] = {0.f, 0.f, 0.f, 0.f};
-            if (add_noise) normal4(seed, off + (uint64_t)q, z);  // the reference draws and discards at t == 1: the offset still advances
-            if (KIND == 0) {
-                const float4 ev = *reinterpret_cast<const float4*>(out + b);
-                const float* es = reinterpret_cast<const float*>(&ev);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xs[j] = ddpm_update(xs[j], es[j], z[j], c0, c1, c2, add_noise);
+        float4 xv = load4(x + b), vv = make_float4(0.f, 0.f, 0.f, 0.f), gv = vv;
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (DRAWS && add_noise) {
+            if (TAKES_ZIN && zin) {
+                const float4 zv = load4(zin + b);
+                z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
             } else {
-                const int64_t img = b / chw, r = b - img * chw;  // chw % 4 == 0: a quad never straddles two images
-                const float4 ev = *reinterpret_cast<const float4*>(out + img * 2 * chw + r);
-                const float4 vv = *reinterpret_cast<const float4*>(out + img * 2 * chw + chw + r);
-                const float* es = reinterpret_cast<const float*>(&ev);
-                const float* vs = reinterpret_cast<const float*>(&vv);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float m = __fmul_rn(c0, __fsub_rn(xs[j], __fmul_rn(c1, es[j])));
-                    xs[j] = add_noise ? __fadd_rn(m, __fmul_rn(iddpm_std(vs[j], c2, c3), z[j])) : m;
-                }
+                normal4(seed, off + (uint64_t)q, z);
             }
         }
+        const int64_t eo = eps_at<KIND>(b, chw);  // chw % 4 == 0: a quad never straddles two images (loaded after the draw: not live across it)
+        const float4 ev = load4(out + eo);
+        if (KIND == DMME_CHAIN_IDDPM) vv = load4(out + eo + chw);
+        if (KIND == DMME_CHAIN_DDPM_GUIDED || KIND == DMME_CHAIN_DDIM_GUIDED) gv = load4(g + b);
+        float* xs = reinterpret_cast<float*>(&xv);
+        const float *es = reinterpret_cast<const float*>(&ev), *vs = reinterpret_cast<const float*>(&vv), *gs = reinterpret_cast<const float*>(&gv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xs[j] = sampler_update<KIND>(xs[j], es[j], vs[j], gs[j], z[j], c0, c1, c2, c3, add_noise);
         *reinterpret_cast<float4*>(x + b) = xv;
     }
     __syncthreads();  // every thread of this block has read the state (and is past its loads of it)
@@ -755,26 +679,27 @@ int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t se
 
 int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
                         hipStream_t s, const float* grad, const float* noise) {
-    DMME_REQUIRE(kind >= 0 && kind <= 5, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
-    DMME_REQUIRE((kind == 3 || kind == 4) == (grad != nullptr), DMME_ERR_INVALID, "chain_update: the guided kinds (3, 4) and only they take a gradient");
+    const bool guided = kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED;
+    DMME_REQUIRE(kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_GDDIM, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
+    DMME_REQUIRE(guided == (grad != nullptr), DMME_ERR_INVALID, "chain_update: the guided kinds (3, 4) and only they take a gradient");
     DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "chain_update: image size %lld is not a multiple of 4", (long long)chw);
     const int64_t n4 = (int64_t)B * chw / 4;
     if (n4 <= 0) return DMME_OK;
     const dim3 g(grid_for(n4)), b(256);
     ChainState* st = (ChainState*)state;
     const long long* tt = (const long long*)t_table;
-    if (kind == 0)
-        hipLaunchKernelGGL(chain_update_kernel<0>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
-    else if (kind == 1)
-        hipLaunchKernelGGL(chain_update_kernel<1>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
-    else if (kind == 2)
-        hipLaunchKernelGGL(chain_update_kernel<2>, g, b, 0, s, x, out, coef, tt, st, chw, n4);
-    else if (kind == 3)
-        hipLaunchKernelGGL(chain_update_kernel<3>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else if (kind == 4)
-        hipLaunchKernelGGL(chain_update_kernel<4>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    if (kind == DMME_CHAIN_DDPM)
+        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    else if (kind == DMME_CHAIN_DDIM)
+        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDIM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    else if (kind == DMME_CHAIN_IDDPM)
+        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_IDDPM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    else if (kind == DMME_CHAIN_DDPM_GUIDED)
+        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDPM_GUIDED>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
+    else if (kind == DMME_CHAIN_DDIM_GUIDED)
+        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDIM_GUIDED>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
     else
-        hipLaunchKernelGGL(chain_update_kernel<5>, g, b, 0, s, x, out, coef, tt, st, chw, n4, (const float*)nullptr, noise);
+        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

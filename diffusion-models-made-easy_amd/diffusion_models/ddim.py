@@ -16,7 +16,7 @@ from torch import Tensor, nn
 from .. import _lib
 from ..common.noise import gaussian, gaussian_like
 from ..equations.ddim import linear_tau, quadratic_tau
-from .ddpm import DDPM, ChainRunner
+from .ddpm import DDPM, ChainRunner, _scalar_index
 
 
 class DDIM(DDPM):
@@ -47,9 +47,7 @@ class DDIM(DDPM):
 
     def sampling_step(self, x_tau_i: Tensor, i: Tensor) -> Tensor:
         r"""x_{tau_{i-1}} from x_{tau_i} (reference: diffusion_models/ddim.py:55-77); i has shape (1,)."""
-        if i.numel() != 1:
-            raise RuntimeError(f"sampling_step expects an index tensor of shape (1,), got {tuple(i.shape)}")
-        idx = int(i.reshape(-1)[0].item())
+        idx = _scalar_index(i, "an index")
         eps = self.model(x_tau_i, self.tau[idx].reshape(1))
         x = x_tau_i.detach().to(torch.float32).clone()
         return self._ddim_update(x, eps, idx)
@@ -78,16 +76,12 @@ class DDIM(DDPM):
     @torch.no_grad()
     def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
         """S-step strided chain (reference: diffusion_models/ddim.py:79-99)"""
-        dev = self.beta.device
-        x = gaussian(img_size, device=dev)
-        runner = self._generate_runner(img_size, dev) if len(img_size) == 4 and not self.model.training else None
-        if runner is not None:
-            runner.x.copy_(x)
-            return runner.run(self.sub_timesteps, self.sub_timesteps).clone()
-        for i in range(self.sub_timesteps, 0, -1):
-            eps = self.model(x, self.tau_tensor(i, dev))
-            self._ddim_update(x, eps, i)
-        return x
+        return self._decode_chain(gaussian(img_size, device=self.beta.device), self.sub_timesteps)
+
+    def _decode_chain(self, x: Tensor, start: int) -> Tensor:
+        """`start` reverse steps from loop index `start`, in place on x or through the captured step"""
+        runner = self._buffered_runner("_runner", x.shape, x.device)
+        return self._run_chain(runner, x, start, start, lambda i: self._ddim_update(x, self.model(x, self.tau_tensor(i, x.device)), i))
 
 
 class GeneralizedDDIM(DDIM):
@@ -157,9 +151,7 @@ class GeneralizedDDIM(DDIM):
 
     def sampling_step(self, x_tau_i: Tensor, i: Tensor, noise: Optional[Tensor] = None) -> Tensor:
         r"""x_{tau_{i-1}} from x_{tau_i}; i has shape (1,) as in `DDIM.sampling_step`; `noise` replaces the drawn normals"""
-        if i.numel() != 1:
-            raise RuntimeError(f"sampling_step expects an index tensor of shape (1,), got {tuple(i.shape)}")
-        idx = self._index(i.reshape(-1)[0].item(), "sampling_step")
+        idx = self._index(_scalar_index(i, "an index"), "sampling_step")
         eps = self.model(x_tau_i, self.tau[idx].reshape(1))
         x = x_tau_i.detach().to(torch.float32).clone()
         return self._gddim_update(x, eps, self._rev_rows[idx], noise, self._draws)
@@ -173,11 +165,8 @@ class GeneralizedDDIM(DDIM):
         return self._enc_t_dev[j]
 
     def _encode_runner(self, shape, dev) -> Optional[ChainRunner]:
-        """the encoding direction's runner: one per shape, on a buffer of its own (`_generate_runner` is the decoding direction's)"""
-        buf = getattr(self, "_enc_buf", None)
-        if buf is None or tuple(buf.shape) != tuple(shape) or buf.device != torch.device(dev):
-            buf = self._enc_buf = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
-        return self.chain_runner(buf, slot="_enc_runner", spec=lambda: (_lib.CHAIN_GDDIM, self._encode_tables()))
+        """the encoding direction's runner: one per shape, on a buffer of its own (slot `_runner` is the decoding direction's)"""
+        return self._buffered_runner("_enc_runner", shape, dev, spec=lambda: (_lib.CHAIN_GDDIM, self._encode_tables()), buf="_enc_buf")
 
     @torch.no_grad()
     def decode(self, x: Tensor, start: Optional[int] = None) -> Tensor:
@@ -187,15 +176,7 @@ class GeneralizedDDIM(DDIM):
         if not 0 <= start <= S:
             raise ValueError(f"decode: start {start} outside 0..{S}")
         x = x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
-        if start == 0:
-            return x
-        runner = self._generate_runner(tuple(x.shape), x.device) if x.dim() == 4 and not self.model.training else None
-        if runner is not None:
-            runner.x.copy_(x)
-            return runner.run(start, start).clone()
-        for i in range(start, 0, -1):
-            self._ddim_update(x, self.model(x, self.tau_tensor(i, x.device)), i)
-        return x
+        return x if start == 0 else self._decode_chain(x, start)
 
     @torch.no_grad()
     def encode(self, x0: Tensor, upto: Optional[int] = None) -> Tensor:
@@ -207,13 +188,8 @@ class GeneralizedDDIM(DDIM):
         x = x0.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
         if upto == 0:
             return x
-        runner = self._encode_runner(tuple(x.shape), x.device) if x.dim() == 4 and not self.model.training else None
-        if runner is not None:
-            runner.x.copy_(x)
-            return runner.run(S, upto).clone()
-        for j in range(S, S - upto, -1):
-            self._gddim_update(x, self.model(x, self._enc_t_tensor(j, x.device)), self._enc_rows[j])
-        return x
+        step = lambda j: self._gddim_update(x, self.model(x, self._enc_t_tensor(j, x.device)), self._enc_rows[j])
+        return self._run_chain(self._encode_runner(x.shape, x.device), x, S, upto, step)
 
     @torch.no_grad()
     def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:

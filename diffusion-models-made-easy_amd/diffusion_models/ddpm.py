@@ -18,7 +18,29 @@ from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..equations.ddpm import linear_schedule, sampling_coefficients
 
 
-class ChainRunner:
+def _scalar_index(t: Tensor, what: str) -> int:
+    """the host integer of `sampling_step`'s index argument.  As in the reference only a tensor of shape (1,) is valid (the
+    reference's `torch.where(t == 1, ...)` broadcasts t against the last image dimension)."""
+    if t.numel() != 1:
+        raise RuntimeError(f"sampling_step expects {what} tensor of shape (1,), got {tuple(t.shape)}")
+    return int(t.reshape(-1)[0].item())
+
+
+class ChainTables:
+    """the device side of a chain (include/dmme_hip.h: dmme_chain_*): the per-index scalars of the update `coef` [n+1][4], the
+    timestep at each loop index `ttab`, and the 64-byte loop `state` {i, t, Philox offset, seed, ticket}"""
+
+    def __init__(self, rows, ttab, device):
+        self.coef = torch.tensor(rows, dtype=torch.float32).reshape(-1).to(device)
+        self.ttab = torch.tensor(ttab, dtype=torch.int64).to(device)
+        self.state = torch.zeros(8, dtype=torch.int64, device=device)
+
+    def set(self, i: int, seed: int = 0, offset: int = 0):
+        """place the loop at index i (DDPM: t = i) with the Philox stream at (seed, offset in quads)"""
+        _lib.check(_lib.lib().dmme_chain_set(_lib.ptr(self.state), int(i), _lib.ptr(self.ttab), seed & 0xFFFFFFFFFFFFFFFF, int(offset), _lib.stream_ptr()), "dmme_chain_set")
+
+
+class ChainRunner(ChainTables):
     """One replayable denoising step on a fixed image buffer (include/dmme_hip.h: dmme_chain_*).
 
     The loop state (index i, timestep t, Philox seed / offset) and the per-index scalars of the update live on the device;
@@ -39,9 +61,7 @@ class ChainRunner:
         # does the update consume normals?  (the shipped DDIM kinds never do; the paper-form kind only with a non-zero k2 somewhere)
         self.draws = self.kind not in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED) and (self.kind != _lib.CHAIN_GDDIM or any(r[2] != 0.0 for r in rows))
         self.n_steps = n
-        self.coef = torch.tensor(rows, dtype=torch.float32).reshape(-1).to(x.device)
-        self.ttab = torch.tensor(ttab, dtype=torch.int64).to(x.device)
-        self.state = torch.zeros(8, dtype=torch.int64, device=x.device)
+        super().__init__(rows, ttab, x.device)
         self.out = torch.empty((B, model.out_channels, H, W), dtype=torch.float32, device=x.device)
         self.quads = x.numel() // 4
         self.use_graph = use_graph
@@ -49,17 +69,13 @@ class ChainRunner:
         self.capture_error = None  # why this runner launches eagerly although a graph was asked for (None: it does not)
         self._wkey = None
 
-    def set(self, i: int, seed: int = 0, offset: int = 0):
-        """place the loop at index i (DDPM: t = i) with the Philox stream at (seed, offset in quads)"""
-        _lib.check(_lib.lib().dmme_chain_set(_lib.ptr(self.state), int(i), _lib.ptr(self.ttab), seed & 0xFFFFFFFFFFFFFFFF, int(offset), _lib.stream_ptr()), "dmme_chain_set")
-
     def _launch(self, packed):
         _lib.check(
             _lib.lib().dmme_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace), self.kind,
                                        _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
             "dmme_chain_step",
         )
-        self.plan.fwd_gen = getattr(self.plan, "fwd_gen", 0) + 1  # the workspace was overwritten (pending backwards must refuse)
+        self.plan.overwritten()
 
     def _weights_key(self):
         """identifies the packed weights the captured graph reads"""
@@ -102,7 +118,7 @@ class ChainRunner:
         # earlier replayed step raises here, one step late at most, for callers that never reach `run`'s final check)
         self.plan.check()
         self.graph.replay()
-        self.plan.fwd_gen = getattr(self.plan, "fwd_gen", 0) + 1
+        self.plan.overwritten()
         return self.x
 
     def run(self, first: int, count: int):
@@ -167,48 +183,78 @@ class DDPM(nn.Module):
     def chain_runner(self, x: Tensor, use_graph: bool = True, slot: str = "_runner", spec=None) -> Optional[ChainRunner]:
         """runner bound to the image buffer `x` (cached per buffer / shape); None when the replayable step does not apply
         (a model that is not a dmme_amd UNet, train mode, an image size that is not a multiple of 4)"""
-        model = self.model
-        if not hasattr(model, "_plan_for") or model.training or not x.is_cuda or x[0].numel() % 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        if not self._replayable(x):
             return None
         r = getattr(self, slot, None)
-        key = (x.data_ptr(), tuple(x.shape), model._dtype, use_graph)
-        if r is None or r._key != key or r.model is not model:
-            r = ChainRunner(self, x, use_graph, spec() if spec is not None else None)  # (spec: a callable, evaluated only when a runner is built)
+        key = self._runner_key(x, use_graph)
+        if r is None or r._key != key:
+            r = self._runner_class(self, x, use_graph, spec() if spec is not None else None)  # (spec: a callable, evaluated only when a runner is built)
             r._key = key
             setattr(self, slot, r)
         return r
 
-    def _generate_runner(self, img_size, dev) -> Optional["ChainRunner"]:
-        """the runner `generate` uses: ONE per (shape, dtype), bound to an internal image buffer that outlives the call - a second
-        `generate` of the same shape re-uses the captured graph, the coefficient tables and the buffers instead of building them again"""
-        buf = getattr(self, "_gen_buf", None)
-        if buf is None or tuple(buf.shape) != tuple(img_size) or buf.device != torch.device(dev):
-            buf = self._gen_buf = torch.empty(tuple(img_size), dtype=torch.float32, device=dev)
-        return self.chain_runner(buf, slot="_runner")
+    _runner_class = ChainRunner
+
+    def _replayable(self, x: Tensor) -> bool:
+        model = self.model
+        return hasattr(model, "_plan_for") and not model.training and x.is_cuda and x.dim() == 4 and x[0].numel() % 4 == 0 and x.dtype == torch.float32 and x.is_contiguous()
+
+    def _runner_key(self, x: Tensor, use_graph: bool):
+        """what a cached runner is good for: this buffer, this network (by identity) in this precision"""
+        return (x.data_ptr(), tuple(x.shape), self.model, self.model._dtype, use_graph)
+
+    def _buffered_runner(self, slot: str, shape, device, spec=None, buf: str = "_gen_buf") -> Optional[ChainRunner]:
+        """the runner in `slot`, bound to an internal image buffer (attribute `buf`) of this shape on this device; both outlive the call:
+        a second chain of the same shape re-uses the captured graph, the device tables and the buffers.  None where `chain_runner` is."""
+        b = getattr(self, buf, None)
+        if b is None or tuple(b.shape) != tuple(shape) or b.device != torch.device(device):
+            b = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+            setattr(self, buf, b)
+        return self.chain_runner(b, slot=slot, spec=spec)
+
+    def _run_chain(self, runner: Optional[ChainRunner], x: Tensor, first: int, count: int, step) -> Tensor:
+        """`count` steps from loop index `first` downwards: x into the runner's buffer, one captured step (UNet + noise + update +
+        state advance) replayed, a clone of the result; without a runner the eager `step(index)`, in place on x, index by index"""
+        if runner is not None:
+            runner.x.copy_(x)
+            return runner.run(first, count).clone()
+        for i in range(first, first - count, -1):
+            step(i)
+        return x
 
     def _once_via_runner(self, x_t: Tensor, index: int) -> Optional[Tensor]:
         """single step at loop index `index` through the captured graph, for callers that loop on the host one step at a time
         (LitDDPM.forward <- callbacks/generate.py:82): small batches are bound by the ~160 dependent launches of an eager step"""
         if self.model.training or not x_t.is_cuda or x_t.shape[0] > 64 or torch.is_grad_enabled() and x_t.requires_grad:
             return None
-        buf = getattr(self, "_once_buf", None)
-        if buf is None or buf.shape != x_t.shape or buf.device != x_t.device:
-            buf = self._once_buf = torch.empty(tuple(x_t.shape), dtype=torch.float32, device=x_t.device)
-        runner = self.chain_runner(buf, slot="_runner_once")
+        runner = self._buffered_runner("_runner_once", x_t.shape, x_t.device, buf="_once_buf")
         if runner is None:
             return None
-        buf.copy_(x_t)
+        runner.x.copy_(x_t)
         # (the paper-form DDIM kind at eta = 0 reserves nothing, like its eager step; every other kind keeps reserving one span per call)
         seed, off = (0, 0) if runner.kind == _lib.CHAIN_GDDIM and not runner.draws else philox_reserve(x_t.device, x_t.numel())
         runner.set(index, seed, off)
         with torch.no_grad():
             runner.step()
-        out = buf.clone()
         # (per-step callers: `runner.step()` reads the engine's status word in front of every replay without synchronising - a
         # hand-off timeout raises one step late at most - and `model.check_engine()` is the synchronising check at the end of a loop)
-        return out
+        return runner.x.clone()
 
     # ------------------------------------------------------------------ training
+    def _noised(self, x_0: Tensor, t: Tensor, noise: Tensor, target: bool = True):
+        """forward noising for every loss here: (x0, t, x_t, target) = fp32 x_0, int64 t, x_t ~ q(x_t | x_0) built from `noise`, and the
+        noise as the loss re-derives it from x_t (None with target=False).  The caller draws `t` and `noise`."""
+        x0 = x_0.detach().to(torch.float32).contiguous()
+        z = noise.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        t = t.to(device=x0.device, dtype=torch.int64).contiguous()
+        x_t = torch.empty_like(x0)
+        tgt = torch.empty_like(x0) if target else None
+        _lib.check(
+            _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), x0.size(0), x0[0].numel(), _lib.ptr(x_t), _lib.ptr(tgt), _lib.stream_ptr()),
+            "dmme_q_sample",
+        )
+        return x0, t, x_t, tgt
+
     def training_step(self, x_0: Tensor, t: Optional[Tensor] = None, noise: Optional[Tensor] = None) -> Tensor:
         r"""L_simple for one batch (reference: diffusion_models/ddpm.py:53-81).
 
@@ -216,22 +262,12 @@ class DDPM(nn.Module):
         (never T itself, as in the reference) and noise ~ N(0, I)."""
         from ..autograd import mse_loss_apply
 
-        B = x_0.size(0)
         if t is None:
-            t = uniform_int(1, self.timesteps, B, device=x_0.device)
+            t = uniform_int(1, self.timesteps, x_0.size(0), device=x_0.device)
         if noise is None:
             noise = gaussian_like(x_0)
-        x0 = x_0.detach().to(torch.float32).contiguous()
-        z = noise.detach().to(torch.float32).contiguous()
-        t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
-        x_t = torch.empty_like(x0)
-        target = torch.empty_like(x0)
-        _lib.check(
-            _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), B, x0[0].numel(), _lib.ptr(x_t), _lib.ptr(target), _lib.stream_ptr()),
-            "dmme_q_sample",
-        )
-        noise_in_x_t = self.model(x_t, t)
-        return mse_loss_apply(noise_in_x_t, target)
+        _, t, x_t, target = self._noised(x_0, t, noise)
+        return mse_loss_apply(self.model(x_t, t), target)
 
     # ------------------------------------------------------------------ sampling
     def _reverse_update(self, x_t: Tensor, eps: Tensor, t: int, noise: Optional[Tensor]) -> Tensor:
@@ -244,13 +280,8 @@ class DDPM(nn.Module):
         return x_t
 
     def sampling_step(self, x_t: Tensor, t: Tensor, noise: Optional[Tensor] = None) -> Tensor:
-        r"""one draw from p_theta(x_{t-1} | x_t) (reference: diffusion_models/ddpm.py:83-111).
-
-        As in the reference only a timestep tensor of shape (1,) is valid (the reference's
-        `torch.where(t == 1, ...)` broadcasts t against the last image dimension)."""
-        if t.numel() != 1:
-            raise RuntimeError(f"sampling_step expects a timestep tensor of shape (1,), got {tuple(t.shape)}")
-        step = int(t.reshape(-1)[0].item())
+        r"""one draw from p_theta(x_{t-1} | x_t) (reference: diffusion_models/ddpm.py:83-111); t has shape (1,)"""
+        step = _scalar_index(t, "a timestep")
         eps = self.model(x_t, t.reshape(1))
         x = x_t.detach().to(torch.float32).clone()
         return self._reverse_update(x, eps, step, noise)
@@ -271,14 +302,8 @@ class DDPM(nn.Module):
         """run the full T-step chain from pure noise (reference: diffusion_models/ddpm.py:113-133)"""
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
-        runner = self._generate_runner(img_size, dev) if len(img_size) == 4 and not self.model.training else None
-        if runner is not None:  # one captured step (UNet + noise + update + t -> t-1) replayed T times
-            runner.x.copy_(x_t)
-            return runner.run(self.timesteps, self.timesteps).clone()
-        for t in range(self.timesteps, 0, -1):
-            eps = self.model(x_t, self.timestep_tensor(t, dev))
-            self._reverse_update(x_t, eps, t, None)
-        return x_t
+        runner, T = self._buffered_runner("_runner", img_size, dev), self.timesteps
+        return self._run_chain(runner, x_t, T, T, lambda t: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(t, dev)), t, None))
 
     def forward(self, x: Tensor, t: Tensor) -> Tensor:
         return self.model(x, t)

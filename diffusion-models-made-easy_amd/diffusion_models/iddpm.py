@@ -117,15 +117,7 @@ class IDDPM(DDPM):
             weight = drawn if weight is None else weight
         if noise is None:
             noise = gaussian_like(x_0)
-        x0 = x_0.detach().to(torch.float32).contiguous()
-        z = noise.detach().to(torch.float32).contiguous()
-        t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
-        x_t = torch.empty_like(x0)
-        target = torch.empty_like(x0)
-        _lib.check(
-            _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), B, x0[0].numel(), _lib.ptr(x_t), _lib.ptr(target), _lib.stream_ptr()),
-            "dmme_q_sample",
-        )
+        x0, t, x_t, target = self._noised(x_0, t, noise)
         model_output = self.model(x_t, t)
         w_simple, w_vlb = (0.0, 1.0) if self.loss_type == "vlb" else (1.0, float(self.gamma))
         loss, rows = iddpm_loss_rows_apply(model_output, x_t, x0, target, t, self._coef, self.timesteps, weight, w_simple, w_vlb, self._ts_status)
@@ -149,20 +141,11 @@ class IDDPM(DDPM):
             return self._training_step_resampled(x_0, t, noise, weight)
         if weight is not None:
             raise ValueError('per-image weights need t_sampler="loss-second-moment"')
-        B = x_0.size(0)
         if t is None:
-            t = uniform_int(1, self.timesteps, B, device=x_0.device)
+            t = uniform_int(1, self.timesteps, x_0.size(0), device=x_0.device)
         if noise is None:
             noise = gaussian_like(x_0)
-        x0 = x_0.detach().to(torch.float32).contiguous()
-        z = noise.detach().to(torch.float32).contiguous()
-        t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
-        x_t = torch.empty_like(x0)
-        target = torch.empty_like(x0)
-        _lib.check(
-            _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), B, x0[0].numel(), _lib.ptr(x_t), _lib.ptr(target), _lib.stream_ptr()),
-            "dmme_q_sample",
-        )
+        x0, t, x_t, target = self._noised(x_0, t, noise)
         model_output = self.model(x_t, t)
         if self.loss_type == "vlb":
             return iddpm_loss_apply(model_output, x_t, x0, target, t, self._coef, 0.0, 1.0)
@@ -200,25 +183,8 @@ class IDDPM(DDPM):
         K, rows, ttab = self._respaced_tables(int(sample_steps))
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
-        runner = None
-        if len(img_size) == 4 and not self.model.training:
-            buf = getattr(self, "_gen_buf", None)
-            if buf is None or tuple(buf.shape) != tuple(img_size) or buf.device != torch.device(dev):
-                buf = self._gen_buf = torch.empty(tuple(img_size), dtype=torch.float32, device=dev)
-            runner = self.respaced_runner(buf, K)
-        if runner is not None:
-            runner.x.copy_(x_t)
-            return runner.run(K, K).clone()
-        B, chw = x_t.size(0), x_t[0].numel()
-        for k in range(K, 0, -1):
-            out = self.model(x_t, self.timestep_tensor(ttab[k], dev))
-            noise = gaussian_like(x_t)
-            c = rows[k]
-            _lib.check(
-                _lib.lib().dmme_iddpm_step(_lib.ptr(x_t), _lib.ptr(out), _lib.ptr(noise), c[0], c[1], c[2], c[3], int(ttab[k] != 1), B, chw, _lib.stream_ptr()),
-                "dmme_iddpm_step",
-            )
-        return x_t
+        runner = self._buffered_runner(f"_runner_k{K}", img_size, dev, spec=lambda: (_lib.CHAIN_IDDPM, (K, rows, ttab)))  # (on the full chain's buffer)
+        return self._run_chain(runner, x_t, K, K, lambda k: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(ttab[k], dev)), ttab[k], None, rows[k]))
 
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()
@@ -232,7 +198,6 @@ class IDDPM(DDPM):
         x0 = x_0.detach().to(torch.float32).contiguous()
         dev, chw = x0.device, x0[0].numel()
         lib = _lib.lib()
-        x_t, target = torch.empty_like(x0), torch.empty_like(x0)
         loss = torch.empty(3, dtype=torch.float32, device=dev)
         rows = torch.empty((3, B), dtype=torch.float32, device=dev)
         scratch = torch.empty(64 * B, dtype=torch.float32, device=dev)
@@ -242,11 +207,7 @@ class IDDPM(DDPM):
         coef = self._coef.to(device=dev, dtype=torch.float32).contiguous()
         for step in range(T, 0, -1):
             t = torch.full((B,), step, dtype=torch.int64, device=dev)
-            z = gaussian_like(x0) if noise is None else noise[step - 1].detach().to(device=dev, dtype=torch.float32).contiguous()
-            _lib.check(
-                lib.dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), B, chw, _lib.ptr(x_t), _lib.ptr(target), _lib.stream_ptr()),
-                "dmme_q_sample",
-            )
+            _, _, x_t, target = self._noised(x0, t, gaussian_like(x0) if noise is None else noise[step - 1])
             out = self.model(x_t, t).detach().to(torch.float32).contiguous()
             _lib.check(
                 lib.dmme_iddpm_loss_rows(_lib.ptr(out), _lib.ptr(x_t), _lib.ptr(x0), _lib.ptr(target), _lib.ptr(t), _lib.ptr(coef), T, None, B, chw, 0.0, 1.0,
@@ -261,13 +222,13 @@ class IDDPM(DDPM):
         terms = terms.t().contiguous()
         return BitsPerDim(prior + terms.sum(dim=1), prior, terms)
 
-    def _reverse_update(self, x_t: Tensor, model_output: Tensor, t: int, noise: Optional[Tensor]) -> Tensor:
+    def _reverse_update(self, x_t: Tensor, model_output: Tensor, t: int, noise: Optional[Tensor], row=None) -> Tensor:
+        """`row`: the scalars of a strided chain's step in place of the full chain's at t"""
         if noise is None:
             noise = gaussian_like(x_t)  # drawn even when t == 1, then unused (reference :144-149)
-        c = self._coef_host[t]
-        B = x_t.size(0)
+        c = self._coef_host[t] if row is None else row
         _lib.check(
-            _lib.lib().dmme_iddpm_step(_lib.ptr(x_t), _lib.ptr(model_output), _lib.ptr(noise), c[0], c[1], c[2], c[3], int(t != 1), B, x_t[0].numel(), _lib.stream_ptr()),
+            _lib.lib().dmme_iddpm_step(_lib.ptr(x_t), _lib.ptr(model_output), _lib.ptr(noise), c[0], c[1], c[2], c[3], int(t != 1), x_t.size(0), x_t[0].numel(), _lib.stream_ptr()),
             "dmme_iddpm_step",
         )
         return x_t

@@ -28,7 +28,7 @@ from torch import Tensor, nn
 from .. import _lib
 from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..diffusion_models.ddim import DDIM
-from ..diffusion_models.ddpm import DDPM, ChainRunner
+from ..diffusion_models.ddpm import DDPM, ChainRunner, ChainTables, _scalar_index
 from ..models.ddpm import UNet
 
 __all__ = ["EncoderClassifier", "ClassifierGuidedDDPM", "ClassifierGuidedDDIM", "GuidedChainRunner", "classifier_loss", "cross_entropy_apply"]
@@ -134,20 +134,11 @@ def classifier_loss(classifier: EncoderClassifier, diffusion: DDPM, x_0: Tensor,
     """Cross-entropy of the noise-aware classifier on x_t = q_sample(x_0, t, noise), t ~ uniform_int(1, T) per image by default
     (as DDPM.training_step draws it); `t` / `noise` may be injected.  The backward runs through HIP into the classifier's flat
     gradient buffer (works with optim.FusedAdam)."""
-    B = x_0.size(0)
     if t is None:
-        t = uniform_int(1, diffusion.timesteps, B, device=x_0.device)
+        t = uniform_int(1, diffusion.timesteps, x_0.size(0), device=x_0.device)
     if noise is None:
         noise = gaussian_like(x_0)
-    x0 = x_0.detach().to(torch.float32).contiguous()
-    z = noise.detach().to(torch.float32).contiguous()
-    t = t.to(device=x_0.device, dtype=torch.int64).contiguous()
-    x_t = torch.empty_like(x0)
-    _lib.check(
-        _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(diffusion._sqrt_alpha_bar), _lib.ptr(diffusion._sqrt_one_minus_alpha_bar), _lib.ptr(t), B,
-                                 x0[0].numel(), _lib.ptr(x_t), None, _lib.stream_ptr()),
-        "dmme_q_sample",
-    )
+    _, t, x_t, _ = diffusion._noised(x_0, t, noise, target=False)
     return cross_entropy_apply(classifier(x_t, t), y)
 
 
@@ -155,9 +146,11 @@ class GuidedChainRunner(ChainRunner):
     """ChainRunner whose captured step is dmme_guided_chain_step: UNet forward, classifier forward, log-softmax gradient,
     input-only backward and the guided update, with the labels in a static device buffer (`y`)."""
 
-    def __init__(self, process, x: Tensor, use_graph: bool = True):
-        super().__init__(process, x, use_graph)
+    def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         cls = process.classifier
+        if process.model.training or cls.training:
+            raise RuntimeError("guided sampling runs the UNet and the classifier in eval mode")
+        super().__init__(process, x, use_graph, spec)
         B, _, H, W = x.shape
         self.cls = cls
         self.cls_plan = cls._plan_for(B, H, W, x.device)
@@ -183,8 +176,8 @@ class GuidedChainRunner(ChainRunner):
                                               _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
             "dmme_guided_chain_step",
         )
-        self.plan.fwd_gen = getattr(self.plan, "fwd_gen", 0) + 1
-        cp.fwd_gen = getattr(cp, "fwd_gen", 0) + 1
+        self.plan.overwritten()
+        cp.overwritten()
 
     def step(self):
         self.cls._bwd_buffers(self.cls_plan)  # (re-packs outside any capture when the classifier's parameters changed)
@@ -197,37 +190,32 @@ class _Guided:
     classifier: EncoderClassifier
     guidance_scale: float
 
+    _runner_class = GuidedChainRunner
+
+    def _replayable(self, x: Tensor) -> bool:
+        return True  # (there is no eager chain to fall back to: what the step cannot run on is refused where the runner is built)
+
+    def _runner_key(self, x: Tensor, use_graph: bool):
+        return super()._runner_key(x, use_graph) + (self.classifier, self.classifier._dtype, self.guidance_scale)
+
     def _guided_runner(self, img_size, dev) -> GuidedChainRunner:
-        buf = getattr(self, "_gbuf", None)
-        if buf is None or tuple(buf.shape) != tuple(img_size) or buf.device != torch.device(dev):
-            buf = self._gbuf = torch.empty(tuple(img_size), dtype=torch.float32, device=dev)
-        r = getattr(self, "_grunner", None)
-        key = (buf.data_ptr(), tuple(buf.shape), self.model._dtype, self.classifier._dtype, self.guidance_scale)
-        if r is None or r._key != key or r.model is not self.model or r.cls is not self.classifier:
-            if self.model.training or self.classifier.training:
-                raise RuntimeError("guided sampling runs the UNet and the classifier in eval mode")
-            r = GuidedChainRunner(self, buf)
-            r._key = key
-            self._grunner = r
-        return r
+        return self._buffered_runner("_grunner", img_size, dev, buf="_gbuf")
 
     def _eager_update(self, x: Tensor, eps: Tensor, g: Tensor, index: int, noise: Optional[Tensor]) -> Tensor:
         dev = x.device
         tabs = getattr(self, "_gtabs", None)
-        if tabs is None or tabs[0] != (dev, self.guidance_scale):
-            n, rows, ttab = self._chain_tables()
-            tabs = self._gtabs = ((dev, self.guidance_scale), torch.tensor(rows, dtype=torch.float32).reshape(-1).to(dev),
-                                  torch.tensor(ttab, dtype=torch.int64).to(dev), torch.zeros(8, dtype=torch.int64, device=dev))
-        _, coef, ttab, state = tabs
+        if tabs is None or tabs.key != (dev, self.guidance_scale):
+            _, rows, ttab = self._chain_tables()
+            tabs = self._gtabs = ChainTables(rows, ttab, dev)
+            tabs.key = (dev, self.guidance_scale)
         if self._chain_kind == _lib.CHAIN_DDIM_GUIDED or noise is not None:
             seed, off = 0, 0
         else:
             seed, off = philox_reserve(dev, x.numel())  # (drawn even at t == 1, then unused: the reference's order)
         z = None if noise is None else noise.detach().to(device=dev, dtype=torch.float32).contiguous()
-        _lib.check(_lib.lib().dmme_chain_set(_lib.ptr(state), int(index), _lib.ptr(ttab), seed & 0xFFFFFFFFFFFFFFFF, int(off), _lib.stream_ptr()),
-                   "dmme_chain_set")
-        _lib.check(_lib.lib().dmme_chain_update_guided(self._chain_kind, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(g), _lib.ptr(z), _lib.ptr(coef), _lib.ptr(ttab),
-                                                       _lib.ptr(state), x.shape[0], x[0].numel(), _lib.stream_ptr()), "dmme_chain_update_guided")
+        tabs.set(index, seed, off)
+        _lib.check(_lib.lib().dmme_chain_update_guided(self._chain_kind, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(g), _lib.ptr(z), _lib.ptr(tabs.coef), _lib.ptr(tabs.ttab),
+                                                       _lib.ptr(tabs.state), x.shape[0], x[0].numel(), _lib.stream_ptr()), "dmme_chain_update_guided")
         return x
 
     def _guided_step(self, x_t: Tensor, index: int, t_dev: Tensor, y, noise: Optional[Tensor]) -> Tensor:
@@ -269,9 +257,7 @@ class ClassifierGuidedDDPM(_Guided, DDPM):
 
     def sampling_step(self, x_t: Tensor, t: Tensor, y, noise: Optional[Tensor] = None) -> Tensor:
         """one guided draw from p(x_{t-1} | x_t, y); t has shape (1,)"""
-        if t.numel() != 1:
-            raise RuntimeError(f"sampling_step expects a timestep tensor of shape (1,), got {tuple(t.shape)}")
-        step = int(t.reshape(-1)[0].item())
+        step = _scalar_index(t, "a timestep")
         return self._guided_step(x_t, step, self.timestep_tensor(step, x_t.device), y, noise)
 
     @torch.no_grad()
@@ -299,9 +285,7 @@ class ClassifierGuidedDDIM(_Guided, DDIM):
 
     def sampling_step(self, x_tau_i: Tensor, i: Tensor, y) -> Tensor:
         """x_{tau_{i-1}} from x_{tau_i} with guidance; i has shape (1,)"""
-        if i.numel() != 1:
-            raise RuntimeError(f"sampling_step expects an index tensor of shape (1,), got {tuple(i.shape)}")
-        idx = int(i.reshape(-1)[0].item())
+        idx = _scalar_index(i, "an index")
         return self._guided_step(x_tau_i, idx, self.tau_tensor(idx, x_tau_i.device), y, None)
 
     @torch.no_grad()

@@ -53,6 +53,11 @@ class _Plan:
         self.workspace = None
         self.packed = None
         self.packed_version = None
+        self.fwd_gen = 0
+
+    def overwritten(self):
+        """a launch overwrote the workspace (activations, drawn masks): a backward still pending on an earlier forward must refuse"""
+        self.fwd_gen += 1
 
     def param_table(self):
         n = self.lib.dmme_unet_plan_num_params(self.h)
@@ -495,7 +500,7 @@ class UNet(nn.Module):
         self._last_plan = plan
         # every forward of this (B, H, W, dtype) overwrites the activations (plan.workspace) and the drawn masks a pending
         # backward would read: the generation stamp lets that backward refuse instead of producing wrong gradients
-        plan.fwd_gen = getattr(plan, "fwd_gen", 0) + 1
+        plan.overwritten()
         if want_ctx:
             return y, (plan, xin, t, masks, plan.fwd_gen)
         return y
@@ -541,7 +546,7 @@ class UNet(nn.Module):
         # at most one step late instead of never; callers that read the result on the host use check_engine()
         plan.check()
         g[1].replay()
-        plan.fwd_gen = getattr(plan, "fwd_gen", 0) + 1
+        plan.overwritten()
         return g[2]
 
     def check_engine(self):

@@ -81,6 +81,52 @@ def test_chain_update_bit_exact_vs_eager_kernels_and_state_advance(kind):
             assert ttab[i] == 1  # the next update runs the t == 1 branch
 
 
+# ------------------------------------------------------------------------------------------ the eager kernels' ragged tail
+GUARD = 1.0e30  # what lies behind x's last element, before and after the call
+
+
+def _eager_step(kind, x, out, z, B, chw):
+    """one eager update in place on the first B * chw floats of the flat buffer `x` (a null z where z is None)"""
+    from dmme_amd import _lib
+
+    lib, c = _lib.lib(), (1.0101525783538818, 0.1414213627576828, 0.30000001192092896)
+    if kind.startswith("ddpm"):
+        rc = lib.dmme_ddpm_step(_lib.ptr(x), _lib.ptr(out), _lib.ptr(z), c[0], c[1], c[2], int(kind == "ddpm-noise"), B * chw, _lib.stream_ptr())
+    elif kind == "ddim":
+        rc = lib.dmme_ddim_step(_lib.ptr(x), _lib.ptr(out), c[1], 0.9899494647979736, B * chw, _lib.stream_ptr())
+    elif kind.startswith("gddim"):
+        rc = lib.dmme_gddim_step(_lib.ptr(x), _lib.ptr(out), _lib.ptr(z), c[0], -c[1], c[2] if kind == "gddim-noise" else 0.0, B * chw, _lib.stream_ptr())
+    else:  # log beta_t, log beta~_t of a mid-chain step
+        rc = lib.dmme_iddpm_step(_lib.ptr(x), _lib.ptr(out), _lib.ptr(z), c[0], c[1], -3.9, -4.6, int(kind == "iddpm-noise"), B, chw, _lib.stream_ptr())
+    _lib.check(rc, kind)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("kind", ["ddpm-noise", "ddpm-mean", "ddim", "gddim-noise", "gddim-det", "iddpm-noise", "iddpm-mean"])
+def test_eager_step_ragged_tail_equals_the_padded_problem(kind):
+    """dmme_{ddpm,ddim,gddim,iddpm}_step on sizes that are no multiple of 4 (IDDPM: images of chw values with `out` laid out
+    [B][2][chw], so quads straddle image borders and the v plane starts unaligned) against the same kernel on the same values
+    embedded in a problem padded to whole quads: the update is elementwise and both runs execute the same device code, so the
+    two agree bit for bit (expf / sqrtf of the IDDPM kind included).  A null z is accepted where the update reads no noise, and
+    nothing behind x's last element is written."""
+    iddpm = kind.startswith("iddpm")
+    reads_z = kind.endswith("-noise")
+    planes = 2 if iddpm else 1
+    for B, chw in ([(1, 1), (3, 75), (2, 4099)] if iddpm else [(1, n) for n in (1, 2, 3, 5, 4099)]):
+        pad = -chw % 4
+        x = synth.normal(chw, (B, chw))
+        out = synth.normal(chw + 1, (B, planes, chw))
+        z = synth.normal(chw + 2, (B, chw))
+        xr = torch.cat([x.reshape(-1), torch.full((7,), GUARD)]).cuda()
+        _eager_step(kind, xr, out.cuda(), z.cuda() if reads_z else None, B, chw)
+        grow = lambda v, fill: torch.cat([v, torch.full(v.shape[:-1] + (pad,), fill)], dim=-1).contiguous().cuda()  # finite padding
+        xp = grow(x, 0.25)
+        _eager_step(kind, xp, grow(out, -0.5), grow(z, 0.75) if reads_z else None, B, chw + pad)
+        assert torch.equal(xr[: B * chw].reshape(B, chw), xp[:, :chw]), f"{kind}: B = {B}, chw = {chw}"
+        assert not torch.equal(xr[: B * chw].cpu(), x.reshape(-1)), f"{kind}: nothing was updated"
+        assert bool((xr[B * chw :] == GUARD).all()), f"{kind}: B = {B}, chw = {chw}: wrote behind x"
+
+
 # ------------------------------------------------------------------------------------------ whole chains
 def test_generate_through_the_captured_step_equals_the_eager_loop():
     """DDPM / DDIM / IDDPM `generate` (one hipGraph of UNet + noise + update + state advance, replayed) against the eager host loop
