@@ -240,49 +240,97 @@ struct ConvArgs {
 };
 
 // ---- kernel launchers (defined in the .hip files) ------------------------------------
-int launch_conv_generic(int dtype, const ConvArgs& a, hipStream_t s);
 int launch_mfma_valu(int mode, int iters, int blocks, float* sink, hipStream_t s);
 int launch_issue_probe(int kind, int n_inner, int iters, int flags, int blocks, long long* sink, const void* src, hipStream_t s);
 int launch_l2_stream(const void* buf, int64_t bytes, int iters, int mode, int depth, int blocks, unsigned* sink, hipStream_t s);
-const char* conv_generic_kernel_name(const ConvArgs& a);
-bool conv_in_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px);
-// returns DMME_ERR_UNSUPPORTED (without setting the error) when the shape is outside
-// the MFMA kernel's domain, so callers can fall back to the generic kernel.
+
+// ---- which kernel runs a convolution (conv_route.hip) --------------------------------
+struct ConvTile {  // host-computed geometry, passed by value
+    int TW, TH, TN;       // output tile: TN images x TH x TW pixels (product = BM)
+    int HH, HWd;          // halo extent in (virtual) input space
+    int tiles_x, tiles_y; // tiles per image
+    int tiles_m, tiles_n;
+    int a_rows;           // TN*HH*HWd
+    unsigned magic_px, magic_w;  // ceil(2^32 / (HH*HWd)), ceil(2^32 / HWd): exact x/d by __umulhi for x*d < 2^32
+};
+enum ConvFamily {
+    CONV_GENERIC = 0,  // kernels_generic.hip: the input conv's kernels and the any-shape kernel
+    CONV_MFMA,         // first-generation MFMA kernel (conv_mfma.hip)
+    CONV_THIN,         // the 3- / 6-channel output conv as one 27- / 54-column GEMM + a 9-term gather (conv_thin.hip)
+    CONV1X1_SPLIT,     // ConvArgs::mix 4 (conv1x1_pipe.hip)
+    CONV1X1_AS,        // activation-stationary, K <= 256 (conv1x1_as.hip)
+    CONV1X1_TILED,     // software-pipelined tiles (conv1x1_pipe.hip)
+    CONV3X3_SPLIT,     // ConvArgs::mix 1 / 2: the wave-specialised kernel's split-pass form (conv_pipe.hip)
+    CONV3X3_WS,        // wave-specialised, persistent: 256- or 128-pixel tiles (BM)
+    CONV3X3_KW,        // K split over the four waves, layers with few output pixels (conv_kw.hip)
+    CONV3X3_PIPE,      // four-wave software pipeline
+};
+// What conv_route() decided for one (dtype, ConvArgs): every consumer - the launch, the kernel label, the plan-time queries - reads
+// this value instead of deciding again.
+struct ConvRoute {
+    int family;        // ConvFamily
+    ConvTile tile;     // the tiled 3x3 families and CONV_MFMA
+    int BM, BN;        // output tile: pixels x couts
+    int cand;          // CONV_MFMA / CONV1X1_TILED / CONV3X3_PIPE: index into the family's candidate table
+    int GT, UA;        // CONV3X3_PIPE: taps staged per barrier interval, halo units a thread may own
+    int NI, ring;      // CONV3X3_KW: the instance
+    int ksplit;        // CONV3X3_PIPE: K slices over workgroups (1: none)
+    int rseg;          // CONV3X3_WS: ConvArgs::r_w is set and the segment's shape is in the kernel's domain
+    // fused GroupNorm statistics of the output, where the kernel can emit them (stat_tiles 0: it cannot - a tile spans images):
+    int vec;           // channels per output vector: a group is whole vectors (or half of an 8-channel one)
+    int stat_bn;       // couts one statistics block spans: whole groups
+    int stat_px;       // pixels per partial
+    int stat_tiles;    // partials per image
+};
+// a route of `family` on BM x BN output tiles; statistics by default one partial per tile, groups inside its BN couts
+inline ConvRoute make_route(int family, int BM = 0, int BN = 0, int vec = 0) {
+    ConvRoute r{};
+    r.family = family;
+    r.BM = r.stat_px = BM;
+    r.BN = r.stat_bn = BN;
+    r.vec = vec;
+    return r;
+}
+ConvRoute conv_route(int dtype, const ConvArgs& a);
+// the families' shape rules: each fills r and returns true when its kernel takes the conv.  conv_route() alone orders them.
+bool conv_thin_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv1x1_split_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv1x1_domain(int dtype, const ConvArgs& a);  // what both the activation-stationary and the tiled 1x1 kernel need
+bool conv1x1_as_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv1x1_tiled_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv3x3_split_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv3x3_pipe_route(int dtype, const ConvArgs& a, ConvRoute& r);  // the two below apply only where this one does, and replace it
+bool conv3x3_ws_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv3x3_kw_route(int dtype, const ConvArgs& a, ConvRoute& r);
+bool conv_mfma_route(int dtype, const ConvArgs& a, ConvRoute& r);
+void conv_generic_route(const ConvArgs& a, ConvRoute& r);
+// returns false when the shape is outside the MFMA kernels' common domain (every tiled kernel but the split-pass ones needs it)
 bool conv_mfma_supported(int dtype, const ConvArgs& a);
-int launch_conv_mfma(int dtype, const ConvArgs& a, hipStream_t s);
-// "conv_mfma_kernel<bf16,9,128,128>" for the variant launch_conv_mfma would pick
-void conv_mfma_label(int dtype, const ConvArgs& a, char* buf, int cap);
-// software-pipelined 3x3 stride-1 variant (conv_pipe.hip); preferred when it applies
-bool conv_pipe_supported(int dtype, const ConvArgs& a);
-// can the wave-specialised kernel take this conv WITH the residual segment described in a.r_* (ConvArgs::r_w)?
-bool conv_pipe_rseg_supported(int dtype, const ConvArgs& a);
-// would this conv run on the wave-specialised kernel, and can that kernel merge its norm's partials itself (ConvArgs::gni)?
-bool conv_gn_in_query(int dtype, const ConvArgs& a);
-int launch_conv_pipe(int dtype, const ConvArgs& a, hipStream_t s);
-void conv_pipe_label(int dtype, const ConvArgs& a, char* buf, int cap);
-// the 3- / 6-channel output conv as one 27- / 54-column GEMM + a 9-term gather (conv_thin.hip)
-bool conv_out_thin_supported(int dtype, const ConvArgs& a);
+// the families' launchers: they run what the route says and pick nothing
+int launch_conv_generic(int dtype, const ConvArgs& a, hipStream_t s);
+const char* conv_generic_kernel_name(const ConvArgs& a);
+int launch_conv_mfma(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s);
 int launch_conv_out_thin(const ConvArgs& a, hipStream_t s);
-// K-split-over-waves 3x3 kernel for layers with few output pixels (conv_kw.hip); launch_conv_pipe dispatches to it
-struct ConvTile;
-bool conv_kw_pick(int dtype, const ConvArgs& a, ConvTile& g, int* ni, int* ring, int* bm);
-int launch_conv_kw(int dtype, const ConvArgs& a, const ConvTile& g, int NI, int ring, int BM, int ksplit, hipStream_t s);
-// will the kernel that runs this conv finish the norms consuming its output (ConvArgs::n_gno set; cg[k]: their group sizes)?
-bool conv_gn_direct_query(int dtype, const ConvArgs& a, const int* cg, int n);
-bool conv_gn_direct_ws_query(int dtype, const ConvArgs& a, const int* cg, int n);  // a.gn_cg: the output tensor's own group size
-// software-pipelined 1x1 variant (conv1x1_pipe.hip); preferred for taps == 1
-bool conv1x1_pipe_supported(int dtype, const ConvArgs& a);
-int launch_conv1x1_pipe(int dtype, const ConvArgs& a, hipStream_t s);
-void conv1x1_pipe_label(int dtype, const ConvArgs& a, char* buf, int cap);
-bool conv1x1_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px);
-bool conv1x1_pipe_gn_in_ok(int dtype, const ConvArgs& a);
-// activation-stationary 1x1 variant for K <= 256 (conv1x1_as.hip); launch_conv1x1_pipe dispatches to it
-bool conv1x1_as_supported(int dtype, const ConvArgs& a);
-bool conv1x1_as_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px);
+int launch_conv1x1(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s);  // CONV1X1_SPLIT / CONV1X1_TILED
 int launch_conv1x1_as(const ConvArgs& a, hipStream_t s);
-// can the kernel that would run this conv also emit GroupNorm partials of its output (group size cg)?
-// on success: tiles = spatial tiles per image, px = pixels per tile (the partial's element count is px*cg)
+int launch_conv3x3(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s);  // the four CONV3X3_* families
+int launch_conv_kw(int dtype, const ConvArgs& a, const ConvTile& g, int NI, int ring, int BM, int ksplit, hipStream_t s);
+// the one dispatch: route, then the family's launcher.  force (dmme_conv2d's force_generic): 1 the generic kernels, 2 the first-generation
+// MFMA kernel where it applies
+int launch_conv(int dtype, const ConvArgs& a, hipStream_t s, int force = 0);
+int launch_conv(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s);
+// "conv_mfma_kernel<bf16,9,128,128>": the kernel the route launches, as bench.py's tables and the tests name it
+void conv_label(const ConvRoute& r, int dtype, const ConvArgs& a, char* buf, int cap);
+// can the kernel that runs this conv also emit GroupNorm partials of its output (group size cg)?
+// on success: tiles = partials per image, px = pixels per partial (the partial's element count is px*cg)
 bool conv_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px);
+// can the kernel that runs this conv merge its norm's partials itself (ConvArgs::gni)?
+bool conv_gn_in_query(int dtype, const ConvArgs& a);
+bool conv1x1_tiled_gn_in_ok(const ConvArgs& a, const ConvRoute& r);
+bool conv3x3_pipe_gn_in_ok(int dtype, const ConvArgs& a, const ConvRoute& r);
+// will the kernel that runs this conv finish the n norms consuming its output (ConvArgs::n_gno set; cg[k]: their group sizes; a.gn_cg:
+// the output tensor's own)?  0: no; 1: yes, with the consumer's pre-activated input; 2: scale / shift / {mean, rstd} only
+int conv_gn_direct_query(int dtype, const ConvArgs& a, const int* cg, int n);
 // merge producer partials of one or two (concatenated) tensors into scale/shift (+ mean/rstd)
 int launch_gn_finalize_parts(const float* part1, int tiles1, int cnt1, int C1, const float* part2, int tiles2, int cnt2, int C2, int N, int groups,
                              const float* gamma, const float* beta, float eps, float* scale, float* shift, float* mean_rstd, const float* t_shift,
@@ -409,14 +457,6 @@ int launch_wgrad_small(int dtype, const ConvArgs& a, const void* dY, float* dW, 
 bool wgrad_mfma_supported(int dtype, const ConvArgs& a);
 int launch_wgrad_mfma(int dtype, const ConvArgs& a, const void* dY, float* dWp, hipStream_t s);
 struct PackItem;
-struct ConvTile {  // host-computed geometry, passed by value
-    int TW, TH, TN;       // output tile: TN images x TH x TW pixels (product = BM)
-    int HH, HWd;          // halo extent in (virtual) input space
-    int tiles_x, tiles_y; // tiles per image
-    int tiles_m, tiles_n;
-    int a_rows;           // TN*HH*HWd
-    unsigned magic_px, magic_w;  // ceil(2^32 / (HH*HWd)), ceil(2^32 / HWd): exact x/d by __umulhi for x*d < 2^32
-};
 
 // grouped (deferred) 3x3 weight gradients: plan-time tables, one launch per backward (wgrad_mfma.hip)
 struct WgLayer {

@@ -429,17 +429,13 @@ static bool as_shape_ok(int dtype, const ConvArgs& a) {
     return true;
 }
 
-bool conv1x1_as_supported(int dtype, const ConvArgs& a) {
+// fused statistics of this kernel: one partial per 32 pixels, groups inside a 32-cout block
+bool conv1x1_as_route(int dtype, const ConvArgs& a, ConvRoute& r) {
     if (!as_shape_ok(dtype, a)) return false;
     if (a.gn_part && (!as_stats_cg_ok(a.gn_cg) || (a.Hout * a.Wout) % 32)) return false;
-    return true;
-}
-
-// fused statistics of this kernel: one partial per 32 pixels
-bool conv1x1_as_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px) {
-    if (!as_shape_ok(dtype, a) || !as_stats_cg_ok(cg) || (a.Hout * a.Wout) % 32) return false;
-    *tiles = a.Hout * a.Wout / 32;
-    *px = 32;
+    r = make_route(CONV1X1_AS, 128, 64, 8);
+    r.stat_bn = r.stat_px = 32;
+    r.stat_tiles = (a.Hout * a.Wout) % 32 ? 0 : a.Hout * a.Wout / 32;
     return true;
 }
 
@@ -461,7 +457,6 @@ static int launch_as_inst(const ConvArgs& a, size_t lds, hipStream_t s) {
 }
 
 int launch_conv1x1_as(const ConvArgs& a, hipStream_t s) {
-    DMME_REQUIRE(conv1x1_as_supported(a.f16 ? DMME_F16 : DMME_BF16, a), DMME_ERR_UNSUPPORTED, "conv1x1_as: unsupported shape");
     const int KCH = (a.C1 + a.C2) / 64;
     const bool res = a.res1 != nullptr;
     const size_t lds = (size_t)as_ring(res) * 64 * KCH * ROW_DATA + as_fold_bytes(a.Cout) + 2 * as_stage_bytes(res);

@@ -376,63 +376,55 @@ static int pick1(const ConvArgs& a) {
     return pick;
 }
 
-bool conv1x1_pipe_supported(int dtype, const ConvArgs& a) {
-    if (a.mix) return dtype == DMME_F16 && split1_ok(a);
+bool conv1x1_split_route(int dtype, const ConvArgs& a, ConvRoute& r) {
+    if (dtype != DMME_F16 || !split1_ok(a)) return false;
+    r = make_route(CONV1X1_SPLIT, 128, 128, 4);  // fp32 output vectors of 4 channels
+    r.stat_tiles = (a.Hout * a.Wout) % 128 ? 0 : a.Hout * a.Wout / 128;
+    return true;
+}
+
+bool conv1x1_domain(int dtype, const ConvArgs& a) {
     if (!conv_mfma_supported(dtype, a)) return false;
     if (a.taps != 1 || a.stride != 1 || a.up) return false;
     if (a.tproj && a.nt != 1) return false;  // per-image time rows need the image-aligned tiles of the 3x3 kernels
     if ((int64_t)a.Cout * (a.C1 + a.C2) >= (1ll << 31)) return false;
-    return pick1(a) >= 0;
-}
-
-// can the tiled kernel finish the norm in front of this conv itself (its tile inside one image, LDS budget)?
-bool conv1x1_pipe_gn_in_ok(int dtype, const ConvArgs& a) {
-    if (!is16(dtype) || debug_route("no_gn_in_pipe") || debug_route("no_gn_in_pipe1") || !conv1x1_pipe_supported(dtype, a)) return false;
-    const int pick = pick1(a);
-    if (pick < 0) return false;
-    const int BM = k1Cand[pick][0], BN = k1Cand[pick][1], HW = a.Hout * a.Wout;
-    size_t lds = (size_t)2 * (BM + BN) * ROW_DATA;
-    if (lds < (size_t)BM * BN * 4) lds = (size_t)BM * BN * 4;
-    return HW % BM == 0 && lds + (size_t)2 * (a.C1 + a.C2) * 4 <= 80 * 1024;
-}
-
-bool conv1x1_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px) {
-    {
-        ConvArgs b = a;  // the activation-stationary kernel takes this conv (with or without statistics): its tiles
-        b.gn_part = nullptr;
-        if (conv1x1_as_supported(dtype, b)) return conv1x1_as_stats_query(dtype, a, cg, tiles, px);
-    }
-    if (a.mix) {  // 128 x 128 tiles, fp32 output vectors of 4 channels
-        const int HWm = a.Hout * a.Wout;
-        if (!split1_ok(a) || HWm % 128 || a.Cout % 128 || cg % 4 || 128 % cg) return false;
-        *tiles = HWm / 128;
-        *px = 128;
-        return true;
-    }
-    const int pick = pick1(a);
-    if (pick < 0) return false;
-    const int BM = k1Cand[pick][0], BN = k1Cand[pick][1], HW = a.Hout * a.Wout, vec = is16(dtype) ? 8 : 4;
-    if (HW % BM) return false;
-    if (a.out_silu || a.out_nchw || a.Cout % BN || a.Cout % vec || !(cg % vec == 0 || (vec == 8 && cg == 4)) || BN % cg) return false;
-    *tiles = HW / BM;
-    *px = BM;
     return true;
 }
 
-template <typename T, bool ACC3 = false>
-static int launch1_t(const ConvArgs& a, hipStream_t s) {
+bool conv1x1_tiled_route(int dtype, const ConvArgs& a, ConvRoute& r) {
     const int pick = pick1(a);
-    DMME_REQUIRE(pick >= 0, DMME_ERR_UNSUPPORTED, "conv1x1_pipe: no tile");
-    const int BM = k1Cand[pick][0], BN = k1Cand[pick][1], HW = a.Hout * a.Wout;
+    if (pick < 0) return false;
+    r = make_route(CONV1X1_TILED, k1Cand[pick][0], k1Cand[pick][1], is16(dtype) ? 8 : 4);
+    r.cand = pick;
+    r.stat_tiles = (a.Hout * a.Wout) % r.BM ? 0 : a.Hout * a.Wout / r.BM;
+    return true;
+}
+
+static size_t tiled1_lds(const ConvArgs& a, int BM, int BN) {
+    size_t lds = (size_t)2 * (BM + BN) * ROW_DATA;
+    if (lds < (size_t)BM * BN * 4) lds = (size_t)BM * BN * 4;
+    if (a.has_gni) lds += (size_t)2 * (a.C1 + a.C2) * 4;
+    return lds;
+}
+
+// can the tiled kernel finish the norm in front of this conv itself (its tile inside one image, LDS budget)?
+bool conv1x1_tiled_gn_in_ok(const ConvArgs& a, const ConvRoute& r) {
+    if (debug_route("no_gn_in_pipe") || debug_route("no_gn_in_pipe1")) return false;
+    ConvArgs b = a;
+    b.has_gni = 1;
+    return (a.Hout * a.Wout) % r.BM == 0 && tiled1_lds(b, r.BM, r.BN) <= 80 * 1024;
+}
+
+template <typename T, bool ACC3 = false>
+static int launch1_t(const ConvRoute& r, const ConvArgs& a, hipStream_t s) {
+    const int BM = r.BM, BN = r.BN, HW = a.Hout * a.Wout;
     const int64_t M = (int64_t)a.N * HW;
     const int tiles_n = (a.Cout + BN - 1) / BN;
     const int64_t tiles_m = (M + BM - 1) / BM;
     const dim3 grid((unsigned)(tiles_m * tiles_n));
     const bool xcd_off = (debug_route("no_xcd_order") != 0);
     const int xcd_order = (!xcd_off && tiles_n > 1 && tiles_m % 8 == 0) ? 1 : 0;
-    size_t lds = (size_t)2 * (BM + BN) * ROW_DATA;
-    if (lds < (size_t)BM * BN * 4) lds = (size_t)BM * BN * 4;
-    if (a.has_gni) lds += (size_t)2 * (a.C1 + a.C2) * 4;
+    const size_t lds = tiled1_lds(a, BM, BN);
     static bool attr_done[3] = {false, false, false};
     int rc = DMME_OK;
 #define DMME_C1_CASE(IDX, BM_, BN_)                                                                                                   \
@@ -445,7 +437,7 @@ static int launch1_t(const ConvArgs& a, hipStream_t s) {
         }                                                                                                                             \
         if (rc == DMME_OK) hipLaunchKernelGGL((conv1x1_pipe_kernel<T, BM_, BN_, ACC3>), grid, dim3(256), lds, s, a, HW, tiles_n, xcd_order); \
         break;
-    switch (pick) {
+    switch (r.cand) {
         DMME_C1_CASE(0, 128, 128)
         DMME_C1_CASE(1, 128, 64)
         DMME_C1_CASE(2, 64, 64)
@@ -456,27 +448,11 @@ static int launch1_t(const ConvArgs& a, hipStream_t s) {
     return DMME_OK;
 }
 
-int launch_conv1x1_pipe(int dtype, const ConvArgs& a, hipStream_t s) {
-    DMME_REQUIRE(conv1x1_pipe_supported(dtype, a), DMME_ERR_UNSUPPORTED, "conv1x1_pipe: unsupported shape");
-    if (a.mix) return launch1_split(a, s);
-    if (conv1x1_as_supported(dtype, a)) return launch_conv1x1_as(a, s);
-    if (dtype == DMME_BF16) return launch1_t<bf16>(a, s);
-    if (dtype == DMME_F16) return launch1_t<f16>(a, s);
-    return a.x3 ? launch1_t<float, true>(a, s) : launch1_t<float>(a, s);
-}
-
-void conv1x1_pipe_label(int dtype, const ConvArgs& a, char* buf, int cap) {
-    if (a.mix) {
-        snprintf(buf, (size_t)cap, "conv1x1_split_kernel<128,128>");
-        return;
-    }
-    if (conv1x1_as_supported(dtype, a)) {
-        snprintf(buf, (size_t)cap, "conv1x1_as_kernel<%d>", (a.C1 + a.C2) / 64);
-        return;
-    }
-    const int pick = pick1(a);
-    snprintf(buf, (size_t)cap, "conv1x1_pipe_kernel<%s,%d,%d>", dtype == DMME_BF16 ? "bf16" : dtype == DMME_F16 ? "f16" : a.x3 ? "float:bf16x3" : "float", pick >= 0 ? k1Cand[pick][0] : 0,
-             pick >= 0 ? k1Cand[pick][1] : 0);
+int launch_conv1x1(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s) {
+    if (r.family == CONV1X1_SPLIT) return launch1_split(a, s);
+    if (dtype == DMME_BF16) return launch1_t<bf16>(r, a, s);
+    if (dtype == DMME_F16) return launch1_t<f16>(r, a, s);
+    return a.x3 ? launch1_t<float, true>(r, a, s) : launch1_t<float>(r, a, s);
 }
 
 }  // namespace dmme

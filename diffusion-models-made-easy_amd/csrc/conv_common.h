@@ -1014,10 +1014,9 @@ inline int min_wgs() {
     return 512;
 }
 
-// fused statistics need: the staged fast epilogue, one image per tile, whole cout tiles, 16-byte group slices
-inline bool stats_tile_ok(const ConvArgs& a, const ConvTile& g, int BN, int cg, int vec) {
-    return g.TN == 1 && !a.out_silu && !a.out_nchw && a.Cout % BN == 0 && a.Cout % vec == 0 && (cg % vec == 0 || (vec == 8 && cg == 4)) && BN % cg == 0 &&
-           (!a.tproj || a.nt == 1 || g.TN == 1);
+// fused statistics need: the staged fast epilogue, whole cout tiles, 16-byte group slices (and one image per tile: ConvRoute::stat_tiles)
+inline bool stats_cols_ok(const ConvArgs& a, int BN, int cg, int vec) {
+    return !a.out_silu && !a.out_nchw && a.Cout % BN == 0 && a.Cout % vec == 0 && (cg % vec == 0 || (vec == 8 && cg == 4)) && BN % cg == 0;
 }
 
 inline bool make_tile(const ConvArgs& a, int BM, int BN, ConvTile& g) {

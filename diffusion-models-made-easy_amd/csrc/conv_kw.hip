@@ -466,7 +466,7 @@ static size_t kw_lds(const ConvArgs& a, const ConvTile& g, int BM, int NI, int r
 }
 
 // which instance (BM, NI, RING) runs this conv; false: not this kernel's shape
-bool conv_kw_pick(int dtype, const ConvArgs& a, ConvTile& g, int* ni_out, int* ring_out, int* bm_out) {
+static bool conv_kw_pick(int dtype, const ConvArgs& a, ConvTile& g, int* ni_out, int* ring_out, int* bm_out) {
     const bool off = getenv("DMME_NO_KW") != nullptr;
     constexpr int force_ni = 0, max_ring = 6;
     const int force_bm = debug_route("kw_bm64") ? 64 : 0;  // (the 8x8 level on 64-pixel tiles instead of two whole images per workgroup)
@@ -512,6 +512,26 @@ bool conv_kw_pick(int dtype, const ConvArgs& a, ConvTile& g, int* ni_out, int* r
         return true;
     }
     return false;
+}
+
+// The 64 x 64 four-wave instances (8x8 / 4x4 maps, small batches) give way to this kernel: candidate 3 of the four-wave kernel (layers
+// with fewer than 512 workgroups) always; the 512-workgroup 8x8 layers (candidate 2) only where the 128-pixel tile applies (with 64-pixel
+// tiles the two-per-CU four-wave kernel is as fast: 20.8 vs 21.4 us).  r: the four-wave kernel's route for this conv.
+// (A split of K over workgroups for this kernel was measured and removed: B = 1: 775 -> 846 steps/s without it, B = 8: 728 -> 792,
+// B = 32: 586 -> 611 - a workgroup's fixed cost is ~5 us whatever its share of K, the finish kernel is one more dependent launch, and
+// an unsplit conv finishes its norms itself.)
+bool conv3x3_kw_route(int dtype, const ConvArgs& a, ConvRoute& r) {
+    if (r.cand != 3 && r.cand != 2) return false;
+    ConvTile g{};
+    int ni = 0, ring = 0, bm = 0;
+    if (!conv_kw_pick(dtype, a, g, &ni, &ring, &bm) || (r.cand != 3 && bm != 128)) return false;
+    r = make_route(CONV3X3_KW, bm, 32 * ni, 8);
+    r.tile = g;
+    r.NI = ni;
+    r.ring = ring;
+    r.ksplit = 1;
+    r.stat_tiles = g.TN == 1 ? g.tiles_x * g.tiles_y : 0;
+    return true;
 }
 
 static int ilog2_kw(int v) {

@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(256) conv_mfma_kernel(ConvArgs a, ConvTile g) 
 }
 
 bool conv_mfma_supported(int dtype, const ConvArgs& a) {
-    if (a.mix) return false;  // (mixed-precision convs have their own kernels: conv_pipe_supported / conv_out_thin_supported)
+    if (a.mix) return false;  // (mixed-precision convs have their own kernels: the *_split_route functions / conv_thin_route)
     const int KC = is16(dtype) ? 64 : 32;
     if (a.in_nchw) return false;
     if ((int64_t)a.N * a.Hout * a.Wout * a.Cout >= (1ll << 31)) return false;  // 32-bit offsets in the epilogue
@@ -165,16 +165,25 @@ static int pick_tile(const ConvArgs& a, ConvTile& g) {
     return pick;
 }
 
-template <typename T, int TAPS, bool ACC3 = false>
-static int launch_sized(const ConvArgs& a, hipStream_t s) {
+bool conv_mfma_route(int dtype, const ConvArgs& a, ConvRoute& r) {
+    if (!conv_mfma_supported(dtype, a)) return false;
     ConvTile g{};
-    const int pick = pick_tile(a, g);
-    DMME_REQUIRE(pick >= 0, DMME_ERR_UNSUPPORTED, "conv_mfma: no tile fits (H=%d W=%d)", a.Hout, a.Wout);
+    const int pick = pick_tile(a, g);  // (>= 0: conv_mfma_supported checked the last candidate)
+    r = make_route(CONV_MFMA, kCand[pick][0], kCand[pick][1], is16(dtype) ? 8 : 4);
+    r.tile = g;
+    r.cand = pick;
+    r.stat_tiles = r.tile.TN == 1 ? r.tile.tiles_x * r.tile.tiles_y : 0;
+    return true;
+}
+
+template <typename T, int TAPS, bool ACC3 = false>
+static int launch_sized(const ConvRoute& r, const ConvArgs& a, hipStream_t s) {
+    const ConvTile& g = r.tile;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
-    size_t lds = tile_lds(g, kCand[pick][1]);
-    const size_t stage = (size_t)kCand[pick][0] * kCand[pick][1] * sizeof(float);  // epilogue staging image
+    size_t lds = tile_lds(g, r.BN);
+    const size_t stage = (size_t)r.BM * r.BN * sizeof(float);  // epilogue staging image
     if (lds < stage) lds = stage;
-    switch (pick) {
+    switch (r.cand) {
         case 0: hipLaunchKernelGGL((conv_mfma_kernel<T, TAPS, 128, 128, ACC3>), grid, dim3(256), lds, s, a, g); break;
         case 1: hipLaunchKernelGGL((conv_mfma_kernel<T, TAPS, 128, 64, ACC3>), grid, dim3(256), lds, s, a, g); break;
         default: hipLaunchKernelGGL((conv_mfma_kernel<T, TAPS, 64, 64, ACC3>), grid, dim3(256), lds, s, a, g); break;
@@ -183,34 +192,11 @@ static int launch_sized(const ConvArgs& a, hipStream_t s) {
     return DMME_OK;
 }
 
-bool conv_pipe_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px);
-
-bool conv_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px) {
-    if (conv1x1_pipe_supported(dtype, a)) return conv1x1_stats_query(dtype, a, cg, tiles, px);
-    if (conv_pipe_supported(dtype, a)) return conv_pipe_stats_query(dtype, a, cg, tiles, px);
-    if (!conv_mfma_supported(dtype, a)) return conv_in_stats_query(dtype, a, cg, tiles, px);
-    ConvTile g{};
-    const int pick = pick_tile(a, g);
-    if (pick < 0) return false;
-    if (!stats_tile_ok(a, g, kCand[pick][1], cg, is16(dtype) ? 8 : 4)) return false;
-    *tiles = g.tiles_x * g.tiles_y;
-    *px = kCand[pick][0];
-    return true;
-}
-
-void conv_mfma_label(int dtype, const ConvArgs& a, char* buf, int cap) {
-    ConvTile g{};
-    const int pick = pick_tile(a, g);
-    snprintf(buf, (size_t)cap, "conv_mfma_kernel<%s,%d,%d,%d>", dtype == DMME_BF16 ? "bf16" : dtype == DMME_F16 ? "f16" : a.x3 ? "float:bf16x3" : "float", a.taps,
-             pick >= 0 ? kCand[pick][0] : 0, pick >= 0 ? kCand[pick][1] : 0);
-}
-
-int launch_conv_mfma(int dtype, const ConvArgs& a, hipStream_t s) {
-    DMME_REQUIRE(conv_mfma_supported(dtype, a), DMME_ERR_UNSUPPORTED, "conv_mfma: unsupported shape");
-    if (dtype == DMME_BF16) return a.taps == 9 ? launch_sized<bf16, 9>(a, s) : launch_sized<bf16, 1>(a, s);
-    if (dtype == DMME_F16) return a.taps == 9 ? launch_sized<f16, 9>(a, s) : launch_sized<f16, 1>(a, s);
-    if (a.x3) return a.taps == 9 ? launch_sized<float, 9, true>(a, s) : launch_sized<float, 1, true>(a, s);
-    return a.taps == 9 ? launch_sized<float, 9>(a, s) : launch_sized<float, 1>(a, s);
+int launch_conv_mfma(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s) {
+    if (dtype == DMME_BF16) return a.taps == 9 ? launch_sized<bf16, 9>(r, a, s) : launch_sized<bf16, 1>(r, a, s);
+    if (dtype == DMME_F16) return a.taps == 9 ? launch_sized<f16, 9>(r, a, s) : launch_sized<f16, 1>(r, a, s);
+    if (a.x3) return a.taps == 9 ? launch_sized<float, 9, true>(r, a, s) : launch_sized<float, 1, true>(r, a, s);
+    return a.taps == 9 ? launch_sized<float, 9>(r, a, s) : launch_sized<float, 1>(r, a, s);
 }
 
 }  // namespace dmme

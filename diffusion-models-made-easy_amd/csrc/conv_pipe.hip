@@ -1410,23 +1410,66 @@ static bool rseg_shape_ok(const ConvArgs& a) {
     return a.r_src1 && a.r_bias && a.r_C1 > 0 && a.r_C1 % 64 == 0 && a.r_C2 >= 0 && (a.r_C2 == 0 || a.r_src2) && Cres % 128 == 0 && Cres <= 512 && !a.up && !a.res1 &&
            !a.res2 && (int64_t)a.Cout * Cres < (1ll << 30) && (int64_t)a.N * a.Hin * a.Win * Cres < (1ll << 30);
 }
-bool conv_pipe_rseg_supported(int dtype, const ConvArgs& a) {
-    if (!is16(dtype) || a.mix || !a.r_w || getenv("DMME_NO_WS") || !rseg_shape_ok(a) || !conv_pipe_supported(dtype, a)) return false;
-    ConvTile gw{};
-    return ws_pick(a, gw) != 0;
+
+// ---- the 3x3 families' routes (conv_route() orders them: split-pass, then - where the four-wave kernel has a tile - the
+// wave-specialised kernel, the K-split kernel of conv_kw.hip, the four-wave kernel itself) ---------------------------------------------
+bool conv3x3_split_route(int dtype, const ConvArgs& a, ConvRoute& r) {
+    ConvTile g{};
+    if (dtype != DMME_F16 || a.taps != 9 || !ws2s_pick(a, g)) return false;
+    r = make_route(CONV3X3_SPLIT, 256, 128, 4);  // fp32 output vectors of 4 channels
+    r.tile = g;
+    r.stat_px = 128;  // one partial per 128-pixel epilogue pass
+    r.stat_tiles = g.tiles_x * g.tiles_y * 2;
+    return true;
 }
 
-bool conv_pipe_supported(int dtype, const ConvArgs& a) {
-    if (a.mix) {
-        ConvTile gs{};
-        return dtype == DMME_F16 && a.taps == 9 && ws2s_pick(a, gs);
-    }
+bool conv3x3_pipe_route(int dtype, const ConvArgs& a, ConvRoute& r) {
     if (!conv_mfma_supported(dtype, a)) return false;
     if (a.taps != 9 || (a.stride != 1 && a.stride != 2)) return false;
     if ((int64_t)a.Cout * 9 * (a.C1 + a.C2) >= (1ll << 31)) return false;
     if ((int64_t)a.N * a.Hin * a.Win >= (1ll << 31)) return false;
-    ConvTile g;
-    return pipe_pick(a, g) >= 0;
+    ConvTile g{};
+    const int pick = pipe_pick(a, g);
+    if (pick < 0) return false;
+    r = make_route(CONV3X3_PIPE, kPipeCand[pick][0], kPipeCand[pick][1], is16(dtype) ? 8 : 4);
+    r.tile = g;
+    r.cand = pick;
+    r.GT = kPipeCand[pick][2];
+    r.UA = kPipeUA[pick];
+    r.ksplit = pipe_ksplit(a, g, pick, is16(dtype) ? 64 : 32);
+    r.stat_tiles = g.TN == 1 ? g.tiles_x * g.tiles_y : 0;
+    return true;
+}
+
+bool conv3x3_ws_route(int dtype, const ConvArgs& a, ConvRoute& r) {
+    ConvTile g{};
+    if (!is16(dtype) || getenv("DMME_NO_WS") || !ws_pick(a, g)) return false;
+    r = make_route(CONV3X3_WS, g.TH * g.TW, 128, 8);
+    r.tile = g;
+    r.rseg = a.r_w && rseg_shape_ok(a);
+    r.stat_px = 128;  // one partial per 128-pixel epilogue pass
+    r.stat_tiles = g.tiles_x * g.tiles_y * (r.BM / 128);
+    return true;
+}
+
+// dynamic LDS of the four-wave kernel's launch; *dma: filter tiles by LDS-DMA into a second buffer (ConvArgs::dma_b)
+static size_t pipe_launch_lds(int dtype, const ConvArgs& a, const ConvRoute& r, bool* dma) {
+    size_t lds = pipe_lds(r.tile, r.BN, r.GT);
+    *dma = pipe_dma_ok(dtype, r.tile, r.BN, r.GT);
+    if (*dma) lds += (size_t)r.GT * r.BN * ROW_DATA;
+    if (a.has_gni) lds += (size_t)2 * (a.C1 + a.C2) * 4;  // scale / shift rows behind the operand buffers
+    if (a.n_gno && lds < (size_t)kDirectLds) lds = kDirectLds;
+    return lds;
+}
+
+// the four-wave kernel merging its norm's partials itself: rows in LDS behind its operand buffers (two workgroups per CU: the 80 KB
+// budget must still hold)
+bool conv3x3_pipe_gn_in_ok(int dtype, const ConvArgs& a, const ConvRoute& r) {
+    if (debug_route("no_gn_in_pipe") || r.tile.TN != 1) return false;
+    ConvArgs b = a;
+    b.has_gni = 1;
+    bool dma = false;
+    return pipe_launch_lds(dtype, b, r, &dma) <= (size_t)(r.GT == 9 ? 128 : 80) * 1024;
 }
 
 template <typename K>
@@ -1435,9 +1478,8 @@ static int set_lds_limit(K kernel, size_t bytes) {
     return DMME_OK;
 }
 
-static int launch_ws2_split(const ConvArgs& a, hipStream_t s) {
-    ConvTile gw{};
-    DMME_REQUIRE(ws2s_pick(a, gw), DMME_ERR_UNSUPPORTED, "conv3x3 (split fp16 passes): unsupported shape");
+static int launch_ws2_split(const ConvRoute& r, const ConvArgs& a, hipStream_t s) {
+    const ConvTile& gw = r.tile;
     static bool attr = false;
     if (!attr) {
         int rc0 = set_lds_limit(conv3x3_ws2_kernel<11, f16, 256, 1>, 160 * 1024);
@@ -1455,90 +1497,51 @@ static int launch_ws2_split(const ConvArgs& a, hipStream_t s) {
     return DMME_OK;
 }
 
-// the 64 x 64 four-wave instances (8x8 / 4x4 maps, small batches) give way to the K-split-over-waves kernel (conv_kw.hip): pick 3
-// (layers with fewer than 512 workgroups) always; the 512-workgroup 8x8 layers only where its 128-pixel tile applies (with 64-pixel
-// tiles the two-per-CU four-wave kernel is as fast: 20.8 vs 21.4 us)
-static bool kw_takes(int dtype, const ConvArgs& a, int pick, ConvTile& gk, int* ni, int* ring, int* bm) {
-    constexpr int all = 0;
-    if (pick != 3 && pick != 2) return false;
-    if (!conv_kw_pick(dtype, a, gk, ni, ring, bm)) return false;
-    return pick == 3 || all || *bm == 128;
-}
-// (a split of K over workgroups for this kernel was measured and removed: B = 1: 775 -> 846 steps/s without it, B = 8: 728 -> 792,
-// B = 32: 586 -> 611 - a workgroup's fixed cost is ~5 us whatever its share of K, the finish kernel is one more dependent launch, and
-// an unsplit conv finishes its norms itself)
-static int kw_ksplit(const ConvArgs&, const ConvTile&) { return 1; }
 template <typename T>
-static int launch_kw_t(const ConvArgs& a, const ConvTile& gk, int ni, int ring, int bm, hipStream_t s) {
-    const int ksplit = kw_ksplit(a, gk);
-    const int rc = launch_conv_kw(dtype_of<T>::value, a, gk, ni, ring, bm, ksplit, s);
-    if (rc != DMME_OK) return rc;
-    if (ksplit > 1) {
-        const int64_t total4 = (int64_t)a.N * a.Hout * a.Wout * (a.Cout / 4);
-        hipLaunchKernelGGL(conv_splitk_finish_kernel<T>, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, a, ksplit, total4);
-        DMME_CHECK_LAUNCH();
+static int launch_ws_t(const ConvRoute& r, const ConvArgs& a, hipStream_t s) {
+    const ConvTile& gw = r.tile;
+    static bool ws_attr = false;  // (one flag per instantiation of this launcher, i.e. per T)
+    if (!ws_attr) {
+        int rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256>, 160 * 1024);
+        if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<7, T, 128>, 160 * 1024);
+        if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256, 0, true>, 160 * 1024);
+        if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<7, T, 128, 0, true>, 160 * 1024);
+        if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256, 0, false, true>, 160 * 1024);
+        if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256, 0, true, true>, 160 * 1024);
+        if (rc0 != DMME_OK) return rc0;
+        ws_attr = true;
     }
+    const int ntiles = gw.tiles_m * gw.tiles_n;
+    const dim3 wgrid((unsigned)(ntiles < 256 ? ntiles : 256));
+    // no residual INPUT tensor (the blocks' first convs, convs with a residual segment, data gradients that do not accumulate):
+    // the 16-bit staged epilogue on transposed accumulators (DMME_DEBUG_ROUTE=no_ws_e16: the fp32-staged two-pass form)
+    const bool e16 = !a.res1 && !a.res2 && !debug_route("no_ws_e16");
+    if (a.r_w) {
+        if (r.BM == 128)
+            hipLaunchKernelGGL((conv3x3_ws2_kernel<7, T, 128, 0, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
+        else if (e16)
+            hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256, 0, true, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
+        else
+            hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256, 0, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
+    } else if (r.BM == 128)
+        hipLaunchKernelGGL((conv3x3_ws2_kernel<7, T, 128>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
+    else if (e16)
+        hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256, 0, false, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
+    else
+        hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
+    DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
 
 template <typename T, bool ACC3 = false>
-static int launch_pipe_t(const ConvArgs& a, hipStream_t s) {
-    ConvTile g{};
-    const int pick = pipe_pick(a, g);
-    DMME_REQUIRE(pick >= 0, DMME_ERR_UNSUPPORTED, "conv_pipe: no tile fits");
-    const int ksplit = pipe_ksplit(a, g, pick, Frag<T>::KC);
+static int launch_pipe_t(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s) {
+    const ConvTile& g = r.tile;
+    const int ksplit = r.ksplit;
     const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)ksplit);
-    if constexpr (sizeof(T) == 2) {
-        const bool ws_off = getenv("DMME_NO_WS") != nullptr;
-        ConvTile gw{};
-        const int ws = ws_off ? 0 : ws_pick(a, gw);
-        if (ws) {
-            static bool ws_attr = false;  // (one flag per instantiation of this launcher, i.e. per T)
-            if (!ws_attr) {
-                int rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256>, 160 * 1024);
-                if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<7, T, 128>, 160 * 1024);
-                if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256, 0, true>, 160 * 1024);
-                if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<7, T, 128, 0, true>, 160 * 1024);
-                if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256, 0, false, true>, 160 * 1024);
-                if (rc0 == DMME_OK) rc0 = set_lds_limit(conv3x3_ws2_kernel<11, T, 256, 0, true, true>, 160 * 1024);
-                if (rc0 != DMME_OK) return rc0;
-                ws_attr = true;
-            }
-            const int ntiles = gw.tiles_m * gw.tiles_n;
-            const dim3 wgrid((unsigned)(ntiles < 256 ? ntiles : 256));
-            // no residual INPUT tensor (the blocks' first convs, convs with a residual segment, data gradients that do not accumulate):
-            // the 16-bit staged epilogue on transposed accumulators (DMME_DEBUG_ROUTE=no_ws_e16: the fp32-staged two-pass form)
-            const bool e16 = !a.res1 && !a.res2 && !debug_route("no_ws_e16");
-            if (a.r_w) {
-                DMME_REQUIRE(rseg_shape_ok(a), DMME_ERR_UNSUPPORTED, "conv3x3 with a residual segment: raw channel counts outside the wave-specialised kernel's domain");
-                if (ws == 4)
-                    hipLaunchKernelGGL((conv3x3_ws2_kernel<7, T, 128, 0, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
-                else if (e16)
-                    hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256, 0, true, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
-                else
-                    hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256, 0, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
-            } else if (ws == 4)
-                hipLaunchKernelGGL((conv3x3_ws2_kernel<7, T, 128>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
-            else if (e16)
-                hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256, 0, false, true>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
-            else
-                hipLaunchKernelGGL((conv3x3_ws2_kernel<11, T, 256>), wgrid, dim3(512), ws2_lds(a, gw), s, a, gw, ilog2(gw.TW), ilog2(gw.TH), ntiles);
-            DMME_CHECK_LAUNCH();
-            return DMME_OK;
-        }
-    }
-    DMME_REQUIRE(!a.r_w, DMME_ERR_UNSUPPORTED, "conv3x3 with a residual segment: only the wave-specialised kernel takes it");
-    if constexpr (sizeof(T) == 2) {
-        ConvTile gk{};
-        int kni = 0, kring = 0, kbm = 0;
-        if (kw_takes(dtype_of<T>::value, a, pick, gk, &kni, &kring, &kbm)) return launch_kw_t<T>(a, gk, kni, kring, kbm, s);
-    }
-    size_t lds = pipe_lds(g, kPipeCand[pick][1], kPipeCand[pick][2]);
     ConvArgs ad = a;
-    ad.dma_b = (sizeof(T) == 2 && !ACC3 && pipe_dma_ok(dtype_of<T>::value, g, kPipeCand[pick][1], kPipeCand[pick][2])) ? 1 : 0;
-    if (ad.dma_b) lds += (size_t)kPipeCand[pick][2] * kPipeCand[pick][1] * ROW_DATA;
-    if (a.has_gni) lds += (size_t)2 * (a.C1 + a.C2) * 4;  // scale / shift rows behind the operand buffers
-    if (a.n_gno && lds < (size_t)kDirectLds) lds = kDirectLds;
+    bool dma = false;
+    const size_t lds = pipe_launch_lds(dtype, a, r, &dma);
+    ad.dma_b = dma ? 1 : 0;
     const int shTW = ilog2(g.TW), shTH = ilog2(g.TH);
     static bool attr_done[5] = {false, false, false, false, false};
     int rc = DMME_OK;
@@ -1550,7 +1553,7 @@ static int launch_pipe_t(const ConvArgs& a, hipStream_t s) {
         }                                                                                                                     \
         if (rc == DMME_OK) hipLaunchKernelGGL((conv3x3_pipe_kernel<T, BM_, BN_, GT_, UA_, ACC3>), grid, dim3(256), lds, s, ad, g, shTW, shTH, ksplit); \
         break;
-    switch (pick) {
+    switch (r.cand) {
         DMME_PIPE_CASE(0, 128, 128, 3, 8, 80)
         DMME_PIPE_CASE(1, 128, 64, 3, 8, 80)
         DMME_PIPE_CASE(2, 64, 64, 3, 8, 80)
@@ -1568,156 +1571,16 @@ static int launch_pipe_t(const ConvArgs& a, hipStream_t s) {
     return DMME_OK;
 }
 
-int launch_conv_pipe(int dtype, const ConvArgs& a, hipStream_t s) {
-    DMME_REQUIRE(conv_pipe_supported(dtype, a), DMME_ERR_UNSUPPORTED, "conv_pipe: unsupported shape");
-    if (a.mix) return launch_ws2_split(a, s);
-    if (dtype == DMME_BF16) return launch_pipe_t<bf16>(a, s);
-    if (dtype == DMME_F16) return launch_pipe_t<f16>(a, s);
-    return a.x3 ? launch_pipe_t<float, true>(a, s) : launch_pipe_t<float>(a, s);
-}
-
-bool conv_gn_in_query(int dtype, const ConvArgs& a) {
-    if (getenv("DMME_NO_GN_IN") || !is16(dtype)) return false;  // (read per plan build, like DMME_NO_GN_DIRECT: the tests toggle it)
-    if (conv_out_thin_supported(dtype, a)) return true;       // the thin output conv keeps its image's rows in LDS anyway
-    if (a.mix) return conv_pipe_supported(dtype, a);          // the split-pass kernel fills its rows like the wave-specialised kernel it is
-    if (a.taps == 1) return conv1x1_as_supported(dtype, a) || conv1x1_pipe_gn_in_ok(dtype, a);  // the store team / the tiled kernel's preamble
-    if (!conv_pipe_supported(dtype, a)) return false;
-    ConvTile gw{};
-    if (!getenv("DMME_NO_WS") && ws_pick(a, gw)) return true;
-    // the K-split kernel (small batches): one image per tile, the wave's own chunk rows in its LDS
-    ConvTile g{}, gk{};
-    const int pick = pipe_pick(a, g);
-    int kni = 0, kring = 0, kbm = 0;
-    if (pick < 0) return false;
-    if (!debug_route("no_gn_in_kw") && kw_takes(dtype, a, pick, gk, &kni, &kring, &kbm)) return gk.TN == 1 && kw_ksplit(a, gk) == 1;
-    if (kw_takes(dtype, a, pick, gk, &kni, &kring, &kbm)) return false;
-    // the four-wave kernel: rows in LDS behind its operand buffers (two workgroups per CU: the 80 KB budget must still hold)
-    if (debug_route("no_gn_in_pipe") || g.TN != 1) return false;
-    ConvArgs b = a;
-    b.has_gni = 1;
-    b.splitk = nullptr;
-    size_t lds = pipe_lds(g, kPipeCand[pick][1], kPipeCand[pick][2]);
-    if (pipe_dma_ok(dtype, g, kPipeCand[pick][1], kPipeCand[pick][2])) lds += (size_t)kPipeCand[pick][2] * kPipeCand[pick][1] * ROW_DATA;
-    lds += (size_t)2 * (a.C1 + a.C2) * 4;
-    return lds <= (size_t)(kPipeCand[pick][2] == 9 ? 128 : 80) * 1024;
-}
-
-bool conv_gn_direct_query(int dtype, const ConvArgs& a, const int* cg, int n) {
-    const bool off = getenv("DMME_NO_GN_DIRECT") != nullptr;
-    if (off || a.mix || n < 1 || n > 2 || a.taps != 9 || !conv_pipe_supported(dtype, a)) return false;
-    const int VEC = is16(dtype) ? 8 : 4;
-    const int HW = a.Hout * a.Wout;
-    if (a.out_silu || a.out_nchw || a.res2 || a.Cout % VEC || HW > 64 || (HW & (HW - 1))) return false;
-    if (is16(dtype) && !getenv("DMME_NO_WS")) {
-        ConvTile gw{};
-        if (ws_pick(a, gw)) return false;  // (conv_gn_direct_ws_query answers for that kernel)
+int launch_conv3x3(const ConvRoute& r, int dtype, const ConvArgs& a, hipStream_t s) {
+    switch (r.family) {
+        case CONV3X3_SPLIT: return launch_ws2_split(r, a, s);
+        case CONV3X3_WS: return dtype == DMME_F16 ? launch_ws_t<f16>(r, a, s) : launch_ws_t<bf16>(r, a, s);
+        case CONV3X3_KW: return launch_conv_kw(dtype, a, r.tile, r.NI, r.ring, r.BM, r.ksplit, s);
+        default: break;
     }
-    ConvArgs b = a;  // would the split-K heuristic (few workgroups) take this conv?  then it keeps that path
-    b.n_gno = 0;
-    b.gn_part = nullptr;
-    b.splitk = (float*)4096;
-    b.splitk_cap = (int64_t)1 << 40;
-    ConvTile g{};
-    const int pick = pipe_pick(a, g);
-    if (pick < 0) return false;
-    int BN = 0, BM = 64;
-    ConvTile gk{};
-    int kni = 0, kring = 0, kbm = 0;
-    if (kw_takes(dtype, a, pick, gk, &kni, &kring, &kbm)) {
-        if (a.up || kw_ksplit(b, gk) != 1) return false;
-        g = gk;
-        BN = 32 * kni;
-        BM = kbm;
-    } else {
-        if (kPipeCand[pick][0] != 64 || pipe_ksplit(b, g, pick, is16(dtype) ? 64 : 32) != 1) return false;
-        BN = kPipeCand[pick][1];
-    }
-    if (g.TH != a.Hout || g.TW != a.Wout || g.TN * g.TH * g.TW != BM || a.Cout % BN) return false;  // whole images, whole cout tiles
-    if (HW < 64 / (BN / VEC)) return false;  // a wave's pixels per channel vector must not straddle images
-    for (int k = 0; k < n; ++k)
-        if (cg[k] % VEC || BN % cg[k]) return false;
-    return true;
-}
-
-// the wave-specialised kernel: its 256-pixel tile is a whole 16x16 image, stored in two passes whose statistics it merges itself
-// (scale / shift / {mean, rstd} only - the first pass is in memory before the statistics exist, so no pre-activated output)
-bool conv_gn_direct_ws_query(int dtype, const ConvArgs& a, const int* cg, int n) {
-    const bool off = getenv("DMME_NO_GN_DIRECT") != nullptr || (debug_route("no_gn_direct_ws") != 0);
-    if (off || a.mix || !is16(dtype) || getenv("DMME_NO_WS") || n < 1 || n > 2 || !conv_pipe_supported(dtype, a)) return false;
-    ConvTile gw{};
-    if (!ws_pick(a, gw) || gw.TH != a.Hout || gw.TW != a.Wout || gw.TH * gw.TW != 256) return false;
-    const int cgs = a.gn_cg;  // this tensor's own group size
-    if (cgs < 8 || cgs % 8 || 128 % cgs || !stats_tile_ok(a, gw, 128, cgs, 8)) return false;
-    for (int k = 0; k < n; ++k) {
-        const int f = cg[k] / cgs;
-        if (cg[k] % cgs || (f != 1 && f != 2 && f != 4) || 128 % cg[k]) return false;
-    }
-    return true;
-}
-
-bool conv_pipe_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px) {
-    if (a.mix) {  // fp32 output vectors of 4 channels, one partial per 128-pixel epilogue pass
-        ConvTile gs{};
-        if (!ws2s_pick(a, gs) || !stats_tile_ok(a, gs, 128, cg, 4)) return false;
-        *tiles = gs.tiles_x * gs.tiles_y * 2;
-        *px = 128;
-        return true;
-    }
-    if (is16(dtype) && !getenv("DMME_NO_WS")) {  // the wave-specialised kernel's tile, when it will run this conv
-        ConvTile gw{};
-        const int ws = ws_pick(a, gw);
-        if (ws) {
-            if (!stats_tile_ok(a, gw, 128, cg, 8)) return false;
-            *tiles = gw.tiles_x * gw.tiles_y * (ws == 4 ? 1 : 2);  // one partial per 128-pixel epilogue pass
-            *px = 128;
-            return true;
-        }
-    }
-    ConvTile g{};
-    const int pick = pipe_pick(a, g);
-    if (pick < 0) return false;
-    {
-        ConvTile gk{};
-        int kni = 0, kring = 0, kbm = 0;
-        if (kw_takes(dtype, a, pick, gk, &kni, &kring, &kbm)) {
-            if (!stats_tile_ok(a, gk, 32 * kni, cg, 8)) return false;
-            *tiles = gk.tiles_x * gk.tiles_y;
-            *px = kbm;
-            return true;
-        }
-    }
-    if (!stats_tile_ok(a, g, kPipeCand[pick][1], cg, is16(dtype) ? 8 : 4)) return false;
-    *tiles = g.tiles_x * g.tiles_y;
-    *px = kPipeCand[pick][0];
-    return true;
-}
-
-void conv_pipe_label(int dtype, const ConvArgs& a, char* buf, int cap) {
-    if (a.mix) {
-        snprintf(buf, (size_t)cap, a.mix == 2 ? "conv3x3_ws2_kernel<11,f16x3,src16>" : "conv3x3_ws2_kernel<11,f16x3>");
-        return;
-    }
-    if (is16(dtype) && !getenv("DMME_NO_WS")) {
-        ConvTile gw{};
-        const int ws = ws_pick(a, gw);
-        if (ws) {
-            snprintf(buf, (size_t)cap, ws == 4 ? (a.r_w ? "conv3x3_ws2_kernel<7,128,res>" : "conv3x3_ws2_kernel<7,128>") : a.r_w ? "conv3x3_ws2_kernel<11,res>" : "conv3x3_ws2_kernel<11>");
-            return;
-        }
-    }
-    ConvTile g{};
-    const int pick = pipe_pick(a, g);
-    {
-        ConvTile gk{};
-        int kni = 0, kring = 0, kbm = 0;
-        if (kw_takes(dtype, a, pick, gk, &kni, &kring, &kbm)) {
-            snprintf(buf, (size_t)cap, "conv3x3_kw_kernel<%d,%d,%d>", kni, kring, kbm);
-            return;
-        }
-    }
-    snprintf(buf, (size_t)cap, "conv3x3_pipe_kernel<%s,%d,%d,%d,%d>", dtype == DMME_BF16 ? "bf16" : dtype == DMME_F16 ? "f16" : a.x3 ? "float:bf16x3" : "float",
-             pick >= 0 ? kPipeCand[pick][0] : 0, pick >= 0 ? kPipeCand[pick][1] : 0, pick >= 0 ? kPipeCand[pick][2] : 0,
-             pick >= 0 ? kPipeUA[pick] : 0);
+    if (dtype == DMME_BF16) return launch_pipe_t<bf16>(r, dtype, a, s);
+    if (dtype == DMME_F16) return launch_pipe_t<f16>(r, dtype, a, s);
+    return a.x3 ? launch_pipe_t<float, true>(r, dtype, a, s) : launch_pipe_t<float>(r, dtype, a, s);
 }
 
 }  // namespace dmme

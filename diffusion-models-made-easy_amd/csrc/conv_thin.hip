@@ -190,7 +190,7 @@ static int thin_rows(const ConvArgs& a) {  // band height: the z image of R + 2 
     return 0;
 }
 
-bool conv_out_thin_supported(int dtype, const ConvArgs& a) {
+bool conv_thin_route(int dtype, const ConvArgs& a, ConvRoute& r) {
     const bool off = getenv("DMME_NO_CONV_THIN") != nullptr;
     if (a.mix && a.mix != 3) return false;
     if (off || !is16(dtype) || a.x3) return false;
@@ -198,7 +198,9 @@ bool conv_out_thin_supported(int dtype, const ConvArgs& a) {
     if (a.taps != 9 || a.stride != 1 || a.up || a.C2 || a.in_nchw || !a.out_nchw || a.out_silu || a.tproj || a.res1 || a.dmask || a.gn_part || a.n_gno)
         return false;
     if (a.Cout * 9 > 64 || a.C1 % 16 || a.C1 > kThinMaxC || a.Wout % 32 || a.Hin != a.Hout || a.Win != a.Wout) return false;
-    return thin_rows(a) > 0;
+    if (thin_rows(a) <= 0) return false;
+    r = make_route(CONV_THIN);
+    return true;
 }
 
 int launch_conv_out_thin(const ConvArgs& a, hipStream_t s) {

@@ -262,12 +262,14 @@ static bool conv_in_mfma_supported(const ConvArgs& a) {
            ((int64_t)a.N * a.Hout * a.Wout) % 32 == 0 && (int64_t)a.N * a.Hout * a.Wout * a.Cout < (1ll << 31) && !debug_route("no_conv_in_mfma");
 }
 
-// the first-conv kernel can emit GroupNorm partials of its output: one per 32-pixel block, groups of exactly 4 channels
-bool conv_in_stats_query(int dtype, const ConvArgs& a, int cg, int* tiles, int* px) {
-    if (cg != 4 || !conv_in_mfma_supported(a) || (a.Hout * a.Wout) % 32) return false;  // (16-bit and fp32 instances alike)
-    *tiles = a.Hout * a.Wout / 32;
-    *px = 32;
-    return true;
+// the first-conv kernel can emit GroupNorm partials of its output: one per 32-pixel block, groups of exactly 4 channels (16-bit and
+// fp32 instances alike)
+void conv_generic_route(const ConvArgs& a, ConvRoute& r) {
+    r = make_route(CONV_GENERIC);
+    if (!conv_in_mfma_supported(a) || (a.Hout * a.Wout) % 32) return;
+    r.vec = r.stat_bn = 4;
+    r.stat_px = 32;
+    r.stat_tiles = a.Hout * a.Wout / 32;
 }
 
 static bool conv_in_supported(const ConvArgs& a) {

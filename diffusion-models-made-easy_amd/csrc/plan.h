@@ -265,7 +265,6 @@ static inline int conv_dt(const dmme_plan* P, const Op& o) { return o.route_f32 
 static inline int wg_index(const Op& o) { return o.taps == 1 ? 1 : o.stride == 2 ? 2 : 0; }
 
 // plan.hip
-int run_any_conv(int dtype, const ConvArgs& a, hipStream_t s);
 void fill_conv(const dmme_plan* P, const Op& o, const char* packed, const float* x, float* y, char* ws, const float* drop_masks, int nt, ConvArgs& a,
                bool fwd = false);
 bool gn_from_parts(const dmme_plan* P, const Op& o);

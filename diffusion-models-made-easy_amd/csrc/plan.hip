@@ -667,49 +667,6 @@ void build_unpack_items(const dmme_plan* P, std::vector<PackItem>& items) {
     }
 }
 
-// ---- which kernel runs a convolution -----------------------------------------------------------------------------------------------
-// ONE table for the whole dispatch (the *_supported / *_pick functions below and in the kernel files implement exactly this; times are
-// per launch at the benchmark configuration - default UNet, batch 128, bf16 - from profiles/r04_sample_b128_bf16_kernel_stats.csv and
-// bench.py's event-bracketed forward; "B <= 32" rows from profiles/r04_bench_n1.json: small_batch):
-//
-//   shape class (16-bit plans)                               kernel                                   launches/step   us/launch
-//   3x3 s1, 32x32 and 16x16 maps, Cin % 128 == 0, >= 256     conv3x3_ws2_kernel<11, T, 256>               18            66-72
-//     256-pixel tiles of one image (the dominant kernel)       wave-specialised, persistent
-//   ... the same where only 128-pixel tiles fill the chip    conv3x3_ws2_kernel<7, T, 128>                 4            41
-//     (128-cout layers of the 16x16 level; 32x32 at B = 32)
-//   3x3 s1 on 8x8 / 4x4 maps, DDPM blocks, <= 2 iterations   lvl_engine_kernel (plan_lvl.hip: a whole     3        131 / 181
-//     per workgroup                                            level per launch; includes its 1x1 convs,
-//                                                              norms and the 4x4 attention)
-//   3x3 s1, few output pixels (small batches; IDDPM small    conv3x3_kw_kernel<NI, RING, DENSE, BM>       -           13-18
-//     maps; 8x8 / 4x4 with DMME_NO_LVL)                        K split over the four waves
-//   3x3 s2 (DownSample), 3x3 with fused 2x upsampling,       conv3x3_pipe_kernel<T, 64, 64, 3 | 9, UA>     4           36-45
-//     everything the rows above decline                        four-wave software pipeline
-//   1x1, K = 128 / 256, >= 128 tiles of 128 pixels           conv1x1_as_kernel<KCH, RES>                  15           14-25
-//     (qkv, proj; the blocks' residual convs of the 32x32 /    activations stationary in registers
-//      16x16 levels only with DMME_DEBUG_ROUTE=no_rseg: they
-//      are a second K segment of conv2's launch, assign_rseg)
-//   1x1 otherwise (K = 384 / 512, small maps, small batches) conv1x1_pipe_kernel<T, BM, BN>                2           20-30
-//   output conv (<= 7 couts, NCHW fp32 out)                  conv_out_thin_kernel<NT, T>                   1            15
-//   input conv (NCHW fp32 in, <= 4 channels)                 conv_in_mfma_kernel<T, CT> (generic file)     1            31
-//   fp32 plans / precision="bf16x3" (fp32 tensors)           conv3x3_pipe / conv1x1_pipe <float[, ACC3]>;  -             -
-//                                                              the 3-cout output conv: conv_mfma_kernel
-//   precision="fp16r32", full-resolution level (ConvArgs::mix)  conv3x3_ws2_kernel<11, f16, 256, SPLIT>   11          120-240
-//                                                              conv_out_thin_kernel<.., SPLIT>; its 1x1 residual
-//                                                              convs and input conv on the fp32-tensor kernels
-//   anything else (odd channel counts: the tiny test net)    conv_generic_kernel                           -             -
-//
-// A/B switches (read when a plan is built or a launch is dispatched; they select among these kernels, never a CPU path): a dozen
-// product switches as environment variables of their own - DMME_NO_LVL, DMME_NO_WS, DMME_NO_KW, DMME_NO_CONV1X1_AS, DMME_NO_CONV_THIN,
-// DMME_NO_FUSED_GN, DMME_NO_GN_IN, DMME_NO_GN_DIRECT, DMME_NO_PREACT, DMME_NO_ATTN_FULL, DMME_NO_WGRAD_GROUP, DMME_NO_GN_BWD_REGS,
-// DMME_NO_GRAD_BUCKETS - and every experiment / comparison route as a key of DMME_DEBUG_ROUTE="key[=int],..." (debug_route()).
-int run_any_conv(int dtype, const ConvArgs& a, hipStream_t s) {
-    if (conv_out_thin_supported(dtype, a)) return launch_conv_out_thin(a, s);
-    if (conv1x1_pipe_supported(dtype, a)) return launch_conv1x1_pipe(dtype, a, s);
-    if (conv_pipe_supported(dtype, a)) return launch_conv_pipe(dtype, a, s);
-    if (conv_mfma_supported(dtype, a)) return launch_conv_mfma(dtype, a, s);
-    return launch_conv_generic(dtype, a, s);
-}
-
 // fill the device-side descriptor of a conv op
 // fwd: the forward launch (a conv whose GroupNorm pre-activated its input reads that tensor and applies nothing); the backward
 // passes false and sees the raw sources with their scale / shift / mask, which is what it differentiates through
@@ -933,8 +890,8 @@ void assign_direct(dmme_plan* P) {
             cgs[k] = C / G;
         }
         a.gn_cg = P->tensors[t].C / G;
-        if (ok && conv_gn_direct_query(conv_dt(P, o), a, cgs, (int)uses[t].size())) elig[t] = 1;
-        else if (ok && P->tensors[t].C % G == 0 && conv_gn_direct_ws_query(conv_dt(P, o), a, cgs, (int)uses[t].size())) elig[t] = 2;  // no act output
+        if (ok) elig[t] = (char)conv_gn_direct_query(conv_dt(P, o), a, cgs, (int)uses[t].size());
+        if (elig[t] == 2 && P->tensors[t].C % G) elig[t] = 0;  // (2: no act output)
     }
     for (bool changed = true; changed;) {  // a norm needs all its sources, a tensor all its norms
         changed = false;
@@ -1070,7 +1027,7 @@ void assign_rseg(dmme_plan* P) {
             c2.rseg = ri;
             ConvArgs a{};
             fill_conv(P, c2, (const char*)4096, (const float*)4096, (float*)4096, (char*)4096, nullptr, 1, a, true);
-            if (!conv_pipe_rseg_supported(P->dtype, a)) {
+            if (!conv_route(P->dtype, a).rseg) {
                 c2.rseg = -1;
                 continue;
             }
@@ -1170,7 +1127,7 @@ int run_op(const dmme_plan* P, const Op& o, const char* pk, const float* x, cons
         case OP_CONV: {
             ConvArgs a{};
             fill_conv(P, o, pk, x, y, ws, drop_masks, nt, a, true);
-            return run_any_conv(conv_dt(P, o), a, s);
+            return launch_conv(conv_dt(P, o), a, s);
         }
         case OP_CAST: {
             const Tensor& ts = P->tensors[o.cast_src];
@@ -1249,16 +1206,7 @@ void op_account(const dmme_plan* P, const Op& o, char* label, int cap, double* f
             ConvArgs a{};
             fill_conv(P, o, (const char*)4096, (const float*)4096, (float*)4096, (char*)4096, nullptr, 1, a, true);
             const int cdt = conv_dt(P, o);
-            if (conv_out_thin_supported(cdt, a))
-                snprintf(label, cap, a.mix == 3 ? "conv_out_thin_kernel<%d,f16x3>" : "conv_out_thin_kernel<%d>", a.Cout * 9 <= 32 ? 1 : 2);
-            else if (conv1x1_pipe_supported(cdt, a))
-                conv1x1_pipe_label(cdt, a, label, cap);
-            else if (conv_pipe_supported(cdt, a))
-                conv_pipe_label(cdt, a, label, cap);
-            else if (conv_mfma_supported(cdt, a))
-                conv_mfma_label(cdt, a, label, cap);
-            else
-                snprintf(label, cap, "%s<%s>", conv_generic_kernel_name(a), o.route_f32 ? "float" : tn);
+            conv_label(conv_route(cdt, a), cdt, a, label, cap);
             const double Cin = a.C1 + a.C2, opix = B * a.Hout * a.Wout;
             *flops = 2.0 * opix * a.Cout * Cin * a.taps;
             *bytes = B * a.Hin * a.Win * Cin * (a.in_nchw ? 4.0 : es) + opix * a.Cout * (a.out_nchw ? 4.0 : es) +
@@ -1332,7 +1280,7 @@ static int check_mix_kernels(const dmme_plan* P) {
         if (o.kind != OP_CONV || !(o.mix || o.route_f32)) continue;
         ConvArgs a{};
         fill_conv(P, o, (const char*)4096, (const float*)4096, (float*)4096, (char*)4096, nullptr, 1, a);
-        const bool ok = o.mix == 3 ? conv_out_thin_supported(P->dtype, a) : o.mix == 4 ? conv1x1_pipe_supported(P->dtype, a) : o.mix ? conv_pipe_supported(P->dtype, a) : true;
+        const bool ok = !o.mix || conv_route(P->dtype, a).family == (o.mix == 3 ? CONV_THIN : o.mix == 4 ? CONV1X1_SPLIT : CONV3X3_SPLIT);
         DMME_REQUIRE(ok, DMME_ERR_UNSUPPORTED, "plan_create: precision fp16r32 has no kernel for the %dx%d conv %d+%d -> %d channels on the %dx%d level (B = %d)",
                      o.taps == 9 ? 3 : 1, o.taps == 9 ? 3 : 1, a.C1, a.C2, a.Cout, a.Hout, a.Wout, P->B);
     }
@@ -1421,10 +1369,11 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
     DMME_TRY(build_plan(P));
     DMME_TRY(check_mix_kernels(P));
     assign_levels(P);
-    if (!getenv("DMME_NO_FUSED_GN")) assign_stats(P);
-    if (!getenv("DMME_NO_FUSED_GN") && !getenv("DMME_NO_GN_DIRECT")) assign_direct(P);
+    const bool fused_gn = !getenv("DMME_NO_FUSED_GN");
+    if (fused_gn) assign_stats(P);
+    if (fused_gn && !getenv("DMME_NO_GN_DIRECT")) assign_direct(P);
     if (!getenv("DMME_NO_PREACT")) assign_preact(P);
-    if (!getenv("DMME_NO_FUSED_GN")) assign_gn_in(P);
+    if (fused_gn) assign_gn_in(P);
     assign_rseg(P);
     assign_attn_proj(P);
     assign_lvl_nograd(P);
@@ -1850,24 +1799,12 @@ DMME_API int dmme_conv2d(const dmme_conv_desc* d, const void* src1, const void* 
         // filter packed by dmme_pack_weight(DMME_F16R32): [Cout][taps][Cin / 32][hi 32 | lo 32] halves.  No fall-back to other kernels.
         a.mix = a.out_nchw ? 3 : a.taps == 1 ? 4 : 1;
         a.f16 = 1;
-        if (a.mix == 4) {
-            DMME_REQUIRE(conv1x1_pipe_supported(DMME_F16, a), DMME_ERR_UNSUPPORTED, "conv2d(fp16r32): the split-pass 1x1 kernel does not take this shape");
-            return launch_conv1x1_pipe(DMME_F16, a, (hipStream_t)stream);
-        }
-        if (a.mix == 3) {
-            DMME_REQUIRE(conv_out_thin_supported(DMME_F16, a), DMME_ERR_UNSUPPORTED, "conv2d(fp16r32): the thin output conv does not take this shape");
-            return launch_conv_out_thin(a, (hipStream_t)stream);
-        }
-        DMME_REQUIRE(conv_pipe_supported(DMME_F16, a), DMME_ERR_UNSUPPORTED, "conv2d(fp16r32): the split-pass 3x3 kernel does not take this shape");
-        return launch_conv_pipe(DMME_F16, a, (hipStream_t)stream);
+        const ConvRoute r = conv_route(DMME_F16, a);
+        DMME_REQUIRE(r.family == (a.mix == 4 ? CONV1X1_SPLIT : a.mix == 3 ? CONV_THIN : CONV3X3_SPLIT), DMME_ERR_UNSUPPORTED, "conv2d(fp16r32): the %s does not take this shape",
+                     a.mix == 4 ? "split-pass 1x1 kernel" : a.mix == 3 ? "thin output conv" : "split-pass 3x3 kernel");
+        return launch_conv(r, DMME_F16, a, (hipStream_t)stream);
     }
-    const int dt = a.x3 ? DMME_F32 : d->dtype;
-    if (d->force_generic == 2 && conv_mfma_supported(dt, a)) return launch_conv_mfma(dt, a, (hipStream_t)stream);
-    if (!d->force_generic && conv_out_thin_supported(dt, a)) return launch_conv_out_thin(a, (hipStream_t)stream);
-    if (!d->force_generic && conv1x1_pipe_supported(dt, a)) return launch_conv1x1_pipe(dt, a, (hipStream_t)stream);
-    if (!d->force_generic && conv_pipe_supported(dt, a)) return launch_conv_pipe(dt, a, (hipStream_t)stream);
-    if (!d->force_generic && conv_mfma_supported(dt, a)) return launch_conv_mfma(dt, a, (hipStream_t)stream);
-    return launch_conv_generic(dt, a, (hipStream_t)stream);
+    return launch_conv(a.x3 ? DMME_F32 : d->dtype, a, (hipStream_t)stream, d->force_generic);
 }
 
 DMME_API int dmme_conv2d_res(const dmme_conv_desc* d, const void* src1, const void* src2, const void* weight, const float* bias, const float* scale,
@@ -1884,10 +1821,11 @@ DMME_API int dmme_conv2d_res(const dmme_conv_desc* d, const void* src1, const vo
     a.f16 = d->dtype == DMME_F16;
     a.stamps = g_stamps;
     a.r_src1 = r_src1; a.r_src2 = r_C2 > 0 ? r_src2 : nullptr; a.r_C1 = r_C1; a.r_C2 = r_C2 > 0 ? r_C2 : 0; a.r_w = r_weight; a.r_bias = r_bias;
-    DMME_REQUIRE(a.taps == 9 && a.stride == 1 && !a.up && conv_pipe_rseg_supported(d->dtype, a), DMME_ERR_UNSUPPORTED,
+    const ConvRoute r = conv_route(d->dtype, a);
+    DMME_REQUIRE(a.taps == 9 && a.stride == 1 && !a.up && r.rseg, DMME_ERR_UNSUPPORTED,
                  "conv2d_res: the wave-specialised 3x3 kernel does not take this shape with a residual segment (%d+%d -> %d channels, %d+%d raw, %dx%dx%d)", a.C1, a.C2,
                  a.Cout, a.r_C1, a.r_C2, a.N, a.Hin, a.Win);
-    return launch_conv_pipe(d->dtype, a, (hipStream_t)stream);
+    return launch_conv(r, d->dtype, a, (hipStream_t)stream);
 }
 
 DMME_API int dmme_groupnorm_scale_shift(int dtype, const void* src1, const void* src2, int N, int HW, int C1, int C2, int groups,

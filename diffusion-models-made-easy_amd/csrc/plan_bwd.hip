@@ -552,7 +552,6 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
             d.w = pkb + P->params[o.w].packed_bwd_off;
             d.dst = tmp;
             d.x3 = P->x3;
-        d.f16 = P->dtype == DMME_F16;  // (launchers without a dtype argument: conv1x1_as, the thin output conv)
             d.f16 = P->dtype == DMME_F16;  // (launchers without a dtype argument: conv1x1_as, the thin output conv)
             if (P->splitk_floats > 0) {
                 d.splitk = (float*)(ws + P->ws_splitk);
@@ -588,7 +587,7 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
                     d.R1 = Cin;
                 }
             }
-            rc = run_any_conv(dt, d, s);
+            rc = launch_conv(dt, d, s);
             if (rc != DMME_OK) break;
 
             if (o.gn >= 0) {
@@ -633,9 +632,8 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
             d.dst = d_x;
             d.out_nchw = 1;
             d.x3 = P->x3;
-        d.f16 = P->dtype == DMME_F16;  // (launchers without a dtype argument: conv1x1_as, the thin output conv)
             d.f16 = P->dtype == DMME_F16;  // (launchers without a dtype argument: conv1x1_as, the thin output conv)
-            rc = conv_mfma_supported(dt, d) ? launch_conv_mfma(dt, d, s) : launch_conv_generic(dt, d, s);
+            rc = launch_conv(dt, d, s, 2);  // (the first-generation MFMA kernel where it applies, else the generic one)
             if (rc != DMME_OK) break;
         }
         // 4. residual branch: d(res) += dY
@@ -774,12 +772,8 @@ DMME_API int dmme_unet_plan_bwd_summary(const dmme_plan* plan, char* buf, int ca
             d.splitk_cap = P->splitk_floats;
         }
         char label[128] = "generic";
-        if (conv1x1_pipe_supported(P->dtype, d))
-            conv1x1_pipe_label(P->dtype, d, label, sizeof(label));
-        else if (conv_pipe_supported(P->dtype, d))
-            conv_pipe_label(P->dtype, d, label, sizeof(label));
-        else if (conv_mfma_supported(P->dtype, d))
-            conv_mfma_label(P->dtype, d, label, sizeof(label));
+        const ConvRoute r = conv_route(P->dtype, d);
+        if (r.family != CONV_GENERIC) conv_label(r, P->dtype, d, label, sizeof(label));
         dgrad[label] += 1;
     }
     for (const auto& kv : dgrad) {
