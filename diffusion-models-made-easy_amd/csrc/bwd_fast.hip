@@ -11,19 +11,6 @@
 
 namespace dmme {
 
-
-template <typename T>
-__device__ __forceinline__ void load_vec(const T* p, float (&v)[16 / sizeof(T)]) {
-    const uint4 raw = *reinterpret_cast<const uint4*>(p);
-    if constexpr (sizeof(T) == 4) {
-        const float4 f = __builtin_bit_cast(float4, raw);
-        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    } else {
-        const typename Vec8<T>::type b = __builtin_bit_cast(typename Vec8<T>::type, raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)b[j];
-    }
-}
 // The pixel loops below issue the 16-byte loads of FOUR pixels before touching any of them: at one or two loads in flight per
 // thread these kernels ran at ~2.3 TB/s (bandwidth = bytes in flight / memory latency), far under what HBM delivers.  The
 // accumulation order per thread is unchanged (pixels in ascending order), so the results are the same bit for bit.
@@ -41,6 +28,10 @@ __device__ __forceinline__ void unpack_vec(const uint4& raw, float (&v)[16 / siz
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (float)b[j];
     }
+}
+template <typename T>
+__device__ __forceinline__ void load_vec(const T* p, float (&v)[16 / sizeof(T)]) {
+    unpack_vec<T>(load_raw<T>(p), v);
 }
 template <typename T>
 __device__ __forceinline__ void store_vec(T* p, const float (&v)[16 / sizeof(T)]) {
@@ -185,12 +176,10 @@ int colsum_group_chunks(int dtype, int HW, int C, int* chunk_px, int* ppw) {
 int launch_colsum_group(int dtype, const ColJob* jobs_dev, int njobs, void* bws, int N, hipStream_t s) {
     if (njobs <= 0) return DMME_OK;
     dim3 grid((unsigned)njobs, (unsigned)N);
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(colsum_group_kernel<bf16>, grid, dim3(256), 0, s, jobs_dev, (char*)bws);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(colsum_group_kernel<f16>, grid, dim3(256), 0, s, jobs_dev, (char*)bws);
-    else
-        hipLaunchKernelGGL(colsum_group_kernel<float>, grid, dim3(256), 0, s, jobs_dev, (char*)bws);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(colsum_group_kernel<T>, grid, dim3(256), 0, s, jobs_dev, (char*)bws);
+    });
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -230,12 +219,10 @@ int launch_colsum_fast(int dtype, const void* dY, int N, int HW, int C, float* r
     int chunk_px, nchunks, ppw;
     DMME_REQUIRE(vec_geometry(dtype, HW, C, chunk_px, nchunks, ppw), DMME_ERR_UNSUPPORTED, "colsum_fast: unsupported geometry");
     dim3 grid(nchunks, N);
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(colsum_vec_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dY, HW, C, chunk_px, ppw, rowsum);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(colsum_vec_kernel<f16>, grid, dim3(256), 0, s, (const f16*)dY, HW, C, chunk_px, ppw, rowsum);
-    else
-        hipLaunchKernelGGL(colsum_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)dY, HW, C, chunk_px, ppw, rowsum);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(colsum_vec_kernel<T>, grid, dim3(256), 0, s, (const T*)dY, HW, C, chunk_px, ppw, rowsum);
+    });
     DMME_CHECK_LAUNCH();
     if (!dbias && !dtproj) return DMME_OK;  // the caller reduces rowsum later (launch_bias_tproj_group)
     hipLaunchKernelGGL(bias_tproj_fast_kernel, dim3((C + 31) / 32), dim3(256), 0, s, rowsum, N, C, dbias, dtproj, ld, nt);
@@ -655,12 +642,10 @@ int launch_grad_acc_fast(int dtype, const void* src, void* d1, void* d2, int C1,
     if (nvec == 0) return DMME_OK;
     int64_t blocks = (nvec + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(grad_acc_vec_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16*)src, (bf16*)d1, (bf16*)d2, C1, C2, acc1, acc2, nvec);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(grad_acc_vec_kernel<f16>, dim3((unsigned)blocks), dim3(256), 0, s, (const f16*)src, (f16*)d1, (f16*)d2, C1, C2, acc1, acc2, nvec);
-    else
-        hipLaunchKernelGGL(grad_acc_vec_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)src, (float*)d1, (float*)d2, C1, C2, acc1, acc2, nvec);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(grad_acc_vec_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)src, (T*)d1, (T*)d2, C1, C2, acc1, acc2, nvec);
+    });
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -1028,8 +1013,6 @@ __global__ void __launch_bounds__(NT) gn_bwd_regs_kernel(const T* __restrict__ d
 #undef REGS_PHASE2
 }
 
-// channel slices for gn_bwd_regs_kernel (0: the shape does not fit it): whole groups, whole 16-byte vectors, not straddling the two
-// concatenated sources, a power-of-two vector count per pixel, at most 8 pixels per thread of the 512
 // Configurations of gn_bwd_regs_kernel, in order of preference: (vectors per thread, threads).  1024 x 4 is the 32x32 / 16x16 form
 // (one workgroup of 16 waves per CU); 1024 x 2 the same on tensors whose 1024 x 4 slicing leaves CUs without a workgroup (16x16 maps
 // of 128 channels: 128 workgroups); 256 x 2 / 256 x 1 the 8x8 and 4x4 maps.
@@ -1054,8 +1037,7 @@ static int gn_bwd_regs_slices_cfg(GnRegsCfg cf, int N, int HW, int C1, int C2, i
     return 0;
 }
 // the configuration for a shape (-1: none) and its slices: the first that gives every CU a workgroup, else the first that fits
-static int gn_bwd_regs_pick(int dtype, int N, int HW, int C1, int C2, int groups, int* slices) {
-    if (getenv("DMME_NO_GN_BWD_REGS") || !is16(dtype)) return -1;
+static int gn_bwd_regs_pick(int N, int HW, int C1, int C2, int groups, int* slices) {
     int first = -1, first_slices = 0;
     for (int i = 0; i < (int)(sizeof(GN_REGS_CFGS) / sizeof(GN_REGS_CFGS[0])); ++i) {
         const int sl = gn_bwd_regs_slices_cfg(GN_REGS_CFGS[i], N, HW, C1, C2, groups);
@@ -1072,58 +1054,91 @@ static int gn_bwd_regs_pick(int dtype, int N, int HW, int C1, int C2, int groups
     *slices = first_slices;
     return first;
 }
-static int gn_bwd_regs_slices(int dtype, int N, int HW, int C1, int C2, int groups) {
-    int sl = 0;
-    return gn_bwd_regs_pick(dtype, N, HW, C1, C2, groups, &sl) < 0 ? 0 : sl;
-}
 
-static bool gn_bwd_small_supported(int dtype, int HW, int C1, int C2, int groups) {
+static bool gn_bwd_small_fits(int dtype, int HW, int C1, int C2, int groups) {
     const int EPV = is16(dtype) ? 8 : 4, C = C1 + C2;
-    return HW <= 64 && C <= 512 && groups <= 64 && C % groups == 0 && C1 % EPV == 0 && C2 % EPV == 0 && C / EPV <= 256 && !debug_route("no_gn_small");
+    return HW <= 64 && C <= 512 && groups <= 64 && C % groups == 0 && C1 % EPV == 0 && C2 % EPV == 0 && C / EPV <= 256;
+}
+// channel slices of the one-workgroup-per-image kernel: whole groups, whole 16-byte vectors, not straddling the two concatenated
+// sources, <= 256 threads per pixel row
+static int gn_bwd_small_slices(int dtype, int N, int C1, int C2, int groups) {
+    const int Call = C1 + C2, cgs = Call / groups, epv = is16(dtype) ? 8 : 4;
+    for (int cand = 4; cand >= 2; cand >>= 1) {
+        const int w = Call / cand;
+        if (Call % cand == 0 && w % cgs == 0 && w % epv == 0 && C1 % w == 0 && (int64_t)N * cand <= 1024) return cand;
+    }
+    return 1;
 }
 
-// pixel chunks of the two-pass GroupNorm backward = partial rows of its channel-sum scratch ([chunks][N][C][2] floats); 1 when the
-// one-workgroup-per-image kernel or the generic path serves the shape
-int gn_bwd_fast_chunks(int dtype, int HW, int C) {
-    int cp, nc, pw;
-    if (!vec_geometry(dtype, HW, C, cp, nc, pw)) return 1;
-    return nc;
+// Which kernels run the backward of a GroupNorm(+SiLU+Dropout2d): ONE decision, gn_bwd_route(), read by the launch (launch_gn_bwd) and by
+// everything in the plan that must agree with the launch beforehand - the size of the channel-sum scratch (Op::b_ab), the activated
+// tensor a norm's backward writes for the grouped weight gradient (Op::wg_act), the per-image dgamma / dbeta rows the grouped bias
+// launch reduces (Op::gn_rows_deferred) and the waiting residual gradient the walk hands over as one more addend.  The families, in the
+// order they are tried (written here and nowhere else), with the norms of the default UNet (16-bit plan, batch 128) that land there:
+//
+//   family    kernels                                            shapes
+//   GENERIC   gn_bwd_generic kernels (kernels_bwd.hip)            channel counts that are no whole 16-byte vectors (the tiny test net)
+//   REGS      gn_bwd_regs_kernel<T, iters, threads, ...>          16-bit, no scale-shift conditioning, a slice of <= 128 channels of one
+//             one launch, the tensor read once                      image in registers: every single-source norm and the 256- / 512-channel
+//                                                                    concatenations - 32x32 (4 x 1024), 16x16 (4 or 2 x 1024), 8x8 (2 x 256),
+//                                                                    4x4 (1 x 256)
+//   SMALL     gn_bwd_small_kernel<T>                              maps of <= 64 pixels, <= 512 channels, no conditioning, that REGS declines:
+//             one workgroup per (image, channel slice)              fp32 plans' 8x8 / 4x4 norms (and the 16-bit ones with DMME_NO_GN_BWD_REGS)
+//   SUMS      gn_bwd_sums_kernel + finalize + gn_bwd_apply_kernel   everything else: the 384-channel concatenations of the 32x32 and 16x16
+//             finalize FUSED: the apply kernel merges the chunk      up blocks, every scale-shift conditioned norm (IDDPM), fp32 plans'
+//             sums itself (C <= 1024, groups <= 256); IMAGE: one     32x32 / 16x16 norms
+//             workgroup per image; GLOBAL: per-column blocks
+//
+// A/B switches: DMME_NO_GN_BWD_REGS and the DMME_DEBUG_ROUTE keys no_gn_small, no_gn_bwd_slices, no_gn_bwd_image, no_gn_bwd_fused_fin,
+// no_gn_bwd_rows are read here and nowhere else.  The route is a pure function of its arguments and the environment, evaluated when a
+// plan is built and again at every dispatch: a plan must be built and run under one environment.
+GnBwdRoute gn_bwd_route(int dtype, int N, int HW, int C1, int C2, int groups, bool has_mod) {
+    GnBwdRoute r{};
+    const int EPV = is16(dtype) ? 8 : 4, C = C1 + C2;
+    // (the chunk geometry is answered for every shape that has one: Op::b_ab is sized by it whichever family runs)
+    if (!vec_geometry(dtype, HW, C, r.chunk_px, r.nchunks, r.ppw)) {
+        r.nchunks = 1;
+        return r;
+    }
+    if (C1 % EPV) return r;
+    r.takes_extra = r.writes_act = true;
+    const bool rows_on = !debug_route("no_gn_bwd_rows");
+    if (!has_mod && is16(dtype) && !getenv("DMME_NO_GN_BWD_REGS")) r.regs_cfg = gn_bwd_regs_pick(N, HW, C1, C2, groups, &r.regs_slices);
+    if (r.regs_cfg >= 0) {
+        r.family = GN_BWD_REGS;
+        r.rows = rows_on;
+        return r;
+    }
+    if (!has_mod && !debug_route("no_gn_small") && gn_bwd_small_fits(dtype, HW, C1, C2, groups)) {
+        r.family = GN_BWD_SMALL;
+        if (!debug_route("no_gn_bwd_slices")) r.small_slices = gn_bwd_small_slices(dtype, N, C1, C2, groups);
+        r.rows = rows_on;
+        return r;
+    }
+    r.family = GN_BWD_SUMS;
+    const bool per_image = !debug_route("no_gn_bwd_image") && C <= 1024 && groups <= 256;
+    r.finalize = per_image && !debug_route("no_gn_bwd_fused_fin") ? GN_FIN_FUSED : per_image ? GN_FIN_IMAGE : GN_FIN_GLOBAL;
+    r.rows = rows_on && r.finalize == GN_FIN_FUSED;  // (only the apply kernel's own merge leaves the per-image rows)
+    return r;
 }
 
-bool gn_bwd_fast_supported(int dtype, int HW, int C1, int C2) {
-    const int EPV = is16(dtype) ? 8 : 4;
-    int a, b, c;
-    return (C1 % EPV) == 0 && vec_geometry(dtype, HW, C1 + C2, a, b, c);
-}
-
-// will launch_gn_bwd_fast leave the batch sums of dgamma / dbeta as per-image rows (instead of same-address atomics)?  Mirrors its dispatch.
-bool gn_bwd_rows_supported(int dtype, int HW, int C1, int C2, int groups, bool has_mod) {
-    if (debug_route("no_gn_bwd_rows")) return false;
-    if (!has_mod && gn_bwd_small_supported(dtype, HW, C1, C2, groups)) return true;
-    if (!has_mod && gn_bwd_regs_slices(dtype, 1, HW, C1, C2, groups)) return true;
+// Launches what the route says.  AB: route.nchunks * N*C*2 floats (every entry is written: no zeroing needed);  S: N*groups*2 floats of
+// scratch;  act, rows, extra: optional (rows is dropped where the route leaves none: the plan read the same field)
+int launch_gn_bwd(const GnBwdRoute& r, int dtype, const void* dv, const void* x1, const void* x2, int N, int HW, int C1, int C2, int groups,
+                  const float* gamma, const float* mean_rstd, const float* scale, const float* shift, const float* dmask, int pro_silu,
+                  void* dx1, void* dx2, int acc1, int acc2, float* dgamma, float* dbeta, float* AB, float* S, GnMod mod, hipStream_t s,
+                  void* act, float* rows, const void* extra) {
+    if (!r.rows) rows = nullptr;
     const int C = C1 + C2;
-    return !debug_route("no_gn_bwd_image") && !debug_route("no_gn_bwd_fused_fin") && C <= 1024 && groups <= 256;
-}
-
-// AB: gn_bwd_fast_chunks * N*C*2 floats (every entry is written: no zeroing needed);  S: N*groups*2 floats of scratch
-int launch_gn_bwd_fast(int dtype, const void* dv, const void* x1, const void* x2, int N, int HW, int C1, int C2, int groups,
-                       const float* gamma, const float* mean_rstd, const float* scale, const float* shift, const float* dmask,
-                       int pro_silu, void* dx1, void* dx2, int acc1, int acc2, float* dgamma, float* dbeta, float* AB, float* S, GnMod mod,
-                       hipStream_t s, void* act, float* rows, const void* extra) {
-    if (rows && !gn_bwd_rows_supported(dtype, HW, C1, C2, groups, mod.t_scale != nullptr)) rows = nullptr;  // (the plan asked the same question)
-    int rslices = 0;
-    if (const int rcfg = mod.t_scale ? -1 : gn_bwd_regs_pick(dtype, N, HW, C1, C2, groups, &rslices); rcfg >= 0) {
-        // the four uniform switches of the two phases are template arguments: as branches inside one kernel the variants of a phase
-        // shared one register allocation and spilled (240 bytes per lane against none)
-#define REGS_LAUNCH_T(TT, I_, NT_, S_, A_, C_, E_)                                                                                              \
-    hipLaunchKernelGGL((gn_bwd_regs_kernel<TT, I_, NT_, S_, A_, C_, E_>), dim3(N, rslices), dim3(NT_), 0, s, (const TT*)dv, (const TT*)x1,          \
-                       (const TT*)x2, HW, C1, C2, groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (TT*)dx1, (TT*)dx2, acc1, acc2,          \
-                       dgamma, dbeta, (TT*)act, rows, (const TT*)extra)
-#define REGS_LAUNCH(I_, NT_, S_, A_, C_, E_)                              \
-    do {                                                                  \
-        if (dtype == DMME_F16) REGS_LAUNCH_T(f16, I_, NT_, S_, A_, C_, E_); \
-        else REGS_LAUNCH_T(bf16, I_, NT_, S_, A_, C_, E_);                \
-    } while (0)
+    const dim3 grid(r.nchunks, N);
+    switch (r.family) {
+        case GN_BWD_REGS:
+            // the four uniform switches of the two phases are template arguments: as branches inside one kernel the variants of a phase
+            // shared one register allocation and spilled (240 bytes per lane against none)
+#define REGS_LAUNCH(I_, NT_, S_, A_, C_, E_)                                                                                                 \
+    hipLaunchKernelGGL((gn_bwd_regs_kernel<T, I_, NT_, S_, A_, C_, E_>), dim3(N, r.regs_slices), dim3(NT_), 0, s, (const T*)dv, (const T*)x1,   \
+                       (const T*)x2, HW, C1, C2, groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (T*)dx1, (T*)dx2, acc1, acc2, dgamma, \
+                       dbeta, (T*)act, rows, (const T*)extra)
 #define REGS_LAUNCH_CE(I_, NT_, S_, A_)                              \
     do {                                                             \
         if (acc1 || acc2) {                                          \
@@ -1144,81 +1159,60 @@ int launch_gn_bwd_fast(int dtype, const void* dv, const void* x1, const void* x2
             else REGS_LAUNCH_CE(I_, NT_, false, false);        \
         }                                                      \
     } while (0)
-        switch (rcfg) {
-            case 0: REGS_LAUNCH_SA(4, 1024); break;
-            case 1: REGS_LAUNCH_SA(2, 1024); break;
-            case 2: REGS_LAUNCH_SA(2, 256); break;
-            default: REGS_LAUNCH_SA(1, 256); break;
-        }
+            with_dtype(dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                if constexpr (sizeof(T) == 2) {  // (the route takes 16-bit tensors only)
+                    switch (r.regs_cfg) {
+                        case 0: REGS_LAUNCH_SA(4, 1024); break;
+                        case 1: REGS_LAUNCH_SA(2, 1024); break;
+                        case 2: REGS_LAUNCH_SA(2, 256); break;
+                        default: REGS_LAUNCH_SA(1, 256); break;
+                    }
+                }
+            });
 #undef REGS_LAUNCH_SA
 #undef REGS_LAUNCH_CE
 #undef REGS_LAUNCH
-        DMME_CHECK_LAUNCH();
-        return DMME_OK;
-    }
-    if (!mod.t_scale && gn_bwd_small_supported(dtype, HW, C1, C2, groups)) {
-        // channel slices: whole groups, whole 16-byte vectors, not straddling the two concatenated sources, <= 256 threads per pixel row
-        const int Call = C1 + C2, cgs = Call / groups, epv = is16(dtype) ? 8 : 4;
-        int slices = 1;
-        const bool slice_off = (debug_route("no_gn_bwd_slices") != 0);
-        for (int cand = 4; cand >= 2 && !slice_off; cand >>= 1) {
-            const int w = Call / cand;
-            if (Call % cand == 0 && w % cgs == 0 && w % epv == 0 && C1 % w == 0 && (int64_t)N * cand <= 1024) {
-                slices = cand;
-                break;
+            DMME_CHECK_LAUNCH();
+            return DMME_OK;
+        case GN_BWD_SMALL:
+            with_dtype(dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                hipLaunchKernelGGL(gn_bwd_small_kernel<T>, dim3(N, r.small_slices), dim3(256), 0, s, (const T*)dv, (const T*)x1, (const T*)x2, HW, C1, C2,
+                                   groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (T*)dx1, (T*)dx2, acc1, acc2, dgamma, dbeta, (T*)act, rows,
+                                   (const T*)extra);
+            });
+            DMME_CHECK_LAUNCH();
+            return DMME_OK;
+        case GN_BWD_SUMS: {
+            with_dtype(dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                hipLaunchKernelGGL(gn_bwd_sums_kernel<T>, grid, dim3(256), 0, s, (const T*)dv, (const T*)x1, (const T*)x2, HW, C1, C2, groups, mean_rstd,
+                                   scale, shift, dmask, pro_silu, r.chunk_px, r.ppw, AB);
+            });
+            DMME_CHECK_LAUNCH();
+            const bool fused_fin = r.finalize == GN_FIN_FUSED;  // the apply kernel merges the chunk sums itself
+            if (r.finalize == GN_FIN_IMAGE) {
+                hipLaunchKernelGGL(gn_bwd_finalize_image_kernel, dim3(N), dim3(256), 0, s, AB, r.nchunks, N, C, groups, gamma, S, dgamma, dbeta, mod);
+            } else if (r.finalize == GN_FIN_GLOBAL) {
+                const int nb_s = (N * groups + 255) / 256;
+                hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(nb_s + (C + 31) / 32), dim3(256), 0, s, AB, r.nchunks, N, C, groups, nb_s, gamma, S, dgamma,
+                                   dbeta, mod);
             }
+            DMME_CHECK_LAUNCH();
+            with_dtype(dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, grid, dim3(256), 0, s, (const T*)dv, (const T*)x1, (const T*)x2, HW, C1, C2, groups, gamma,
+                                   mean_rstd, scale, shift, dmask, pro_silu, S, r.chunk_px, r.ppw, (T*)dx1, (T*)dx2, acc1, acc2, mod, (T*)act,
+                                   fused_fin ? AB : nullptr, dgamma, dbeta, fused_fin ? rows : nullptr, (const T*)extra);
+            });
+            DMME_CHECK_LAUNCH();
+            return DMME_OK;
         }
-        if (dtype == DMME_BF16)
-            hipLaunchKernelGGL(gn_bwd_small_kernel<bf16>, dim3(N, slices), dim3(256), 0, s, (const bf16*)dv, (const bf16*)x1, (const bf16*)x2, HW, C1, C2, groups,
-                               gamma, mean_rstd, scale, shift, dmask, pro_silu, (bf16*)dx1, (bf16*)dx2, acc1, acc2, dgamma, dbeta, (bf16*)act, rows, (const bf16*)extra);
-        else if (dtype == DMME_F16)
-            hipLaunchKernelGGL(gn_bwd_small_kernel<f16>, dim3(N, slices), dim3(256), 0, s, (const f16*)dv, (const f16*)x1, (const f16*)x2, HW, C1, C2, groups,
-                               gamma, mean_rstd, scale, shift, dmask, pro_silu, (f16*)dx1, (f16*)dx2, acc1, acc2, dgamma, dbeta, (f16*)act, rows, (const f16*)extra);
-        else
-            hipLaunchKernelGGL(gn_bwd_small_kernel<float>, dim3(N, slices), dim3(256), 0, s, (const float*)dv, (const float*)x1, (const float*)x2, HW, C1, C2,
-                               groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (float*)dx1, (float*)dx2, acc1, acc2, dgamma, dbeta, (float*)act, rows, (const float*)extra);
-        DMME_CHECK_LAUNCH();
-        return DMME_OK;
+        default:
+            return launch_gn_bwd_generic(dtype, dv, x1, x2, N, HW, C1, C2, groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, dx1, dx2, acc1, acc2,
+                                         dgamma, dbeta, mod, s);
     }
-    int chunk_px, nchunks, ppw;
-    const int C = C1 + C2;
-    DMME_REQUIRE(vec_geometry(dtype, HW, C, chunk_px, nchunks, ppw), DMME_ERR_UNSUPPORTED, "gn_bwd_fast: unsupported geometry");
-    dim3 grid(nchunks, N);
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(gn_bwd_sums_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dv, (const bf16*)x1, (const bf16*)x2, HW, C1, C2, groups,
-                           mean_rstd, scale, shift, dmask, pro_silu, chunk_px, ppw, AB);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(gn_bwd_sums_kernel<f16>, grid, dim3(256), 0, s, (const f16*)dv, (const f16*)x1, (const f16*)x2, HW, C1, C2, groups,
-                           mean_rstd, scale, shift, dmask, pro_silu, chunk_px, ppw, AB);
-    else
-        hipLaunchKernelGGL(gn_bwd_sums_kernel<float>, grid, dim3(256), 0, s, (const float*)dv, (const float*)x1, (const float*)x2, HW, C1, C2,
-                           groups, mean_rstd, scale, shift, dmask, pro_silu, chunk_px, ppw, AB);
-    DMME_CHECK_LAUNCH();
-    const bool per_image_off = (debug_route("no_gn_bwd_image") != 0);
-    const bool fused_off = (debug_route("no_gn_bwd_fused_fin") != 0);
-    const bool fused_fin = !per_image_off && !fused_off && C <= 1024 && groups <= 256;  // the apply kernel merges the chunk sums itself
-    if (fused_fin) {
-    } else if (!per_image_off && C <= 1024 && groups <= 256) {
-        hipLaunchKernelGGL(gn_bwd_finalize_image_kernel, dim3(N), dim3(256), 0, s, AB, nchunks, N, C, groups, gamma, S, dgamma, dbeta, mod);
-    } else {
-        const int nb_s = (N * groups + 255) / 256;
-        hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(nb_s + (C + 31) / 32), dim3(256), 0, s, AB, nchunks, N, C, groups, nb_s, gamma, S, dgamma, dbeta, mod);
-    }
-    DMME_CHECK_LAUNCH();
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dv, (const bf16*)x1, (const bf16*)x2, HW, C1, C2, groups,
-                           gamma, mean_rstd, scale, shift, dmask, pro_silu, S, chunk_px, ppw, (bf16*)dx1, (bf16*)dx2, acc1, acc2, mod, (bf16*)act,
-                           fused_fin ? AB : nullptr, dgamma, dbeta, fused_fin ? rows : nullptr, (const bf16*)extra);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<f16>, grid, dim3(256), 0, s, (const f16*)dv, (const f16*)x1, (const f16*)x2, HW, C1, C2, groups,
-                           gamma, mean_rstd, scale, shift, dmask, pro_silu, S, chunk_px, ppw, (f16*)dx1, (f16*)dx2, acc1, acc2, mod, (f16*)act,
-                           fused_fin ? AB : nullptr, dgamma, dbeta, fused_fin ? rows : nullptr, (const f16*)extra);
-    else
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, grid, dim3(256), 0, s, (const float*)dv, (const float*)x1, (const float*)x2, HW, C1, C2,
-                           groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, S, chunk_px, ppw, (float*)dx1, (float*)dx2, acc1, acc2, mod, (float*)act,
-                           fused_fin ? AB : nullptr, dgamma, dbeta, fused_fin ? rows : nullptr, (const float*)extra);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
 }
 
 }  // namespace dmme

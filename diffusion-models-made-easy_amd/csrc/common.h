@@ -53,6 +53,18 @@ struct dtype_of<f16> {
 };
 
 __host__ __device__ inline size_t dtype_size(int dt) { return dt == DMME_BF16 || dt == DMME_F16 ? 2 : 4; }
+// Host-side choice of the element type a launch is instantiated for: fn receives a TypeTag<bf16 | f16 | float> value
+// (using T = typename decltype(tag)::type).  Anything that is not a 16-bit code takes the float kernels.
+template <typename T>
+struct TypeTag {
+    using type = T;
+};
+template <typename F>
+static inline auto with_dtype(int dtype, F&& fn) {
+    if (dtype == DMME_BF16) return fn(TypeTag<bf16>{});
+    if (dtype == DMME_F16) return fn(TypeTag<f16>{});
+    return fn(TypeTag<float>{});
+}
 __host__ __device__ inline bool is16(int dt) { return dt == DMME_BF16 || dt == DMME_F16; }  // the two 16-bit operand types share every kernel
 
 __device__ __forceinline__ float to_f(float v) { return v; }
@@ -537,13 +549,24 @@ int launch_colsum_group(int dtype, const ColJob* jobs_dev, int njobs, void* bws,
 // dbias == dtproj == nullptr: only the [N][C] column sums (the caller reduces them later with launch_bias_tproj_group)
 int launch_colsum_fast(int dtype, const void* dY, int N, int HW, int C, float* rowsum, float* dbias, float* dtproj, int ld, int nt,
                        hipStream_t s);
-bool gn_bwd_fast_supported(int dtype, int HW, int C1, int C2);
-int gn_bwd_fast_chunks(int dtype, int HW, int C);
-int launch_gn_bwd_fast(int dtype, const void* dv, const void* x1, const void* x2, int N, int HW, int C1, int C2, int groups,
-                       const float* gamma, const float* mean_rstd, const float* scale, const float* shift, const float* dmask,
-                       int pro_silu, void* dx1, void* dx2, int acc1, int acc2, float* dgamma, float* dbeta, float* AB_zeroed,
-                       float* S_scratch, GnMod mod, hipStream_t s, void* act = nullptr, float* rows = nullptr, const void* extra = nullptr);
-bool gn_bwd_rows_supported(int dtype, int HW, int C1, int C2, int groups, bool has_mod);
+// Which kernels run a GroupNorm backward (bwd_fast.hip: gn_bwd_route decides, launch_gn_bwd and the plan read the fields)
+enum GnBwdFamily { GN_BWD_GENERIC = 0, GN_BWD_REGS, GN_BWD_SMALL, GN_BWD_SUMS };
+enum GnBwdFinalize { GN_FIN_FUSED = 0, GN_FIN_IMAGE, GN_FIN_GLOBAL };
+struct GnBwdRoute {
+    int family = GN_BWD_GENERIC;
+    int regs_cfg = -1, regs_slices = 0;      // REGS: index of the register-resident configuration, channel slices per image
+    int small_slices = 1;                    // SMALL: channel slices per image
+    int chunk_px = 0, nchunks = 1, ppw = 0;  // SUMS: pixel chunks of one image; nchunks = partial rows of the channel-sum scratch
+    int finalize = GN_FIN_FUSED;             // SUMS: who merges the chunk sums
+    bool rows = false;         // the kernels leave per-image dgamma / dbeta rows (no same-address atomics) when given a rows buffer
+    bool takes_extra = false;  // one more addend (a waiting residual gradient) rides along
+    bool writes_act = false;   // writes the consumer's activated input when given a buffer
+};
+GnBwdRoute gn_bwd_route(int dtype, int N, int HW, int C1, int C2, int groups, bool has_mod);
+int launch_gn_bwd(const GnBwdRoute& r, int dtype, const void* dv, const void* x1, const void* x2, int N, int HW, int C1, int C2, int groups,
+                  const float* gamma, const float* mean_rstd, const float* scale, const float* shift, const float* dmask, int pro_silu,
+                  void* dx1, void* dx2, int acc1, int acc2, float* dgamma, float* dbeta, float* AB, float* S_scratch, GnMod mod, hipStream_t s,
+                  void* act = nullptr, float* rows = nullptr, const void* extra = nullptr);
 bool grad_acc_fast_supported(int dtype, int C1, int C2, int pool);
 int launch_grad_acc_fast(int dtype, const void* src, void* d1, void* d2, int C1, int C2, int acc1, int acc2, int64_t npix, hipStream_t s);
 int launch_grad_acc(int dtype, const void* src, void* d1, void* d2, int C1, int C2, int acc1, int acc2, int pool, int N, int H, int W,

@@ -94,12 +94,10 @@ int launch_wgrad_generic(int dtype, const ConvArgs& a, const void* dY, float* dW
     const int rpc = (rows + chunks - 1) / chunks;
     chunks = (rows + rpc - 1) / rpc;
     dim3 grid((unsigned)blocks, (unsigned)chunks);
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(wgrad_generic_kernel<bf16>, grid, dim3(256), 0, s, a, (const bf16*)dY, dW, rpc);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(wgrad_generic_kernel<f16>, grid, dim3(256), 0, s, a, (const f16*)dY, dW, rpc);
-    else
-        hipLaunchKernelGGL(wgrad_generic_kernel<float>, grid, dim3(256), 0, s, a, (const float*)dY, dW, rpc);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(wgrad_generic_kernel<T>, grid, dim3(256), 0, s, a, (const T*)dY, dW, rpc);
+    });
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -379,16 +377,13 @@ int launch_wgrad_small(int dtype, const ConvArgs& a, const void* dY, float* dW, 
     if (wgrad_thin_supported(a) && !debug_route("no_wgrad_thin")) {
         const int64_t total = (int64_t)a.N * a.Hout * a.Wout;
         const int tiles = (int)((total + 255) / 256), grid = tiles < 256 ? tiles : 256;  // few workgroups: they all end in atomics on the same addresses
-#define DMME_WTHIN(TT, FF) hipLaunchKernelGGL((wgrad_thin_kernel<TT, FF>), dim3(grid), dim3(256), 0, s, a, (const TT*)dY, dW, tiles, g0)
+#define DMME_WTHIN(FF) hipLaunchKernelGGL((wgrad_thin_kernel<T, FF>), dim3(grid), dim3(256), 0, s, a, (const T*)dY, dW, tiles, g0)
         const int G = a.in_nchw ? a.C1 : a.Cout;
         for (int g0 = 0; g0 < G; g0 += 3) {
-            if (dtype == DMME_BF16) {
-                if (a.in_nchw) DMME_WTHIN(bf16, true); else DMME_WTHIN(bf16, false);
-            } else if (dtype == DMME_F16) {
-                if (a.in_nchw) DMME_WTHIN(f16, true); else DMME_WTHIN(f16, false);
-            } else {
-                if (a.in_nchw) DMME_WTHIN(float, true); else DMME_WTHIN(float, false);
-            }
+            with_dtype(dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                if (a.in_nchw) DMME_WTHIN(true); else DMME_WTHIN(false);
+            });
             DMME_CHECK_LAUNCH();
         }
 #undef DMME_WTHIN
@@ -399,22 +394,17 @@ int launch_wgrad_small(int dtype, const ConvArgs& a, const void* dY, float* dW, 
     const int rpc = (rows + chunks - 1) / chunks;
     chunks = (rows + rpc - 1) / rpc;
     if (a.in_nchw) {
-#define DMME_WCIN(TT, CC) hipLaunchKernelGGL((wgrad_cin_small_kernel<TT, CC>), dim3(chunks), dim3(256), 0, s, a, (const TT*)dY, dW, rpc)
-        if (dtype == DMME_BF16) {
-            switch (a.C1) { case 1: DMME_WCIN(bf16, 1); break; case 2: DMME_WCIN(bf16, 2); break; case 3: DMME_WCIN(bf16, 3); break; default: DMME_WCIN(bf16, 4); }
-        } else if (dtype == DMME_F16) {
-            switch (a.C1) { case 1: DMME_WCIN(f16, 1); break; case 2: DMME_WCIN(f16, 2); break; case 3: DMME_WCIN(f16, 3); break; default: DMME_WCIN(f16, 4); }
-        } else {
-            switch (a.C1) { case 1: DMME_WCIN(float, 1); break; case 2: DMME_WCIN(float, 2); break; case 3: DMME_WCIN(float, 3); break; default: DMME_WCIN(float, 4); }
-        }
+#define DMME_WCIN(CC) hipLaunchKernelGGL((wgrad_cin_small_kernel<T, CC>), dim3(chunks), dim3(256), 0, s, a, (const T*)dY, dW, rpc)
+        with_dtype(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            switch (a.C1) { case 1: DMME_WCIN(1); break; case 2: DMME_WCIN(2); break; case 3: DMME_WCIN(3); break; default: DMME_WCIN(4); }
+        });
 #undef DMME_WCIN
     } else {
-        if (dtype == DMME_BF16)
-            hipLaunchKernelGGL(wgrad_cout_small_kernel<bf16>, dim3(chunks), dim3(256), 0, s, a, (const bf16*)dY, dW, rpc);
-        else if (dtype == DMME_F16)
-            hipLaunchKernelGGL(wgrad_cout_small_kernel<f16>, dim3(chunks), dim3(256), 0, s, a, (const f16*)dY, dW, rpc);
-        else
-            hipLaunchKernelGGL(wgrad_cout_small_kernel<float>, dim3(chunks), dim3(256), 0, s, a, (const float*)dY, dW, rpc);
+        with_dtype(dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL(wgrad_cout_small_kernel<T>, dim3(chunks), dim3(256), 0, s, a, (const T*)dY, dW, rpc);
+        });
     }
     DMME_CHECK_LAUNCH();
     return DMME_OK;
@@ -468,19 +458,13 @@ __global__ void __launch_bounds__(256) colsum_thin_kernel(const T* __restrict__ 
 int launch_colsum(int dtype, const void* dY, int N, int HW, int C, float* rowsum, float* dbias, float* dtproj, int ld, int nt,
                   hipStream_t s) {
     dim3 grid((C + 255) / 256, N);
-    if (C <= 8 && HW >= 256) {
-        if (dtype == DMME_BF16)
-            hipLaunchKernelGGL(colsum_thin_kernel<bf16>, dim3(N), dim3(256), 0, s, (const bf16*)dY, HW, C, rowsum);
-        else if (dtype == DMME_F16)
-            hipLaunchKernelGGL(colsum_thin_kernel<f16>, dim3(N), dim3(256), 0, s, (const f16*)dY, HW, C, rowsum);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (C <= 8 && HW >= 256)
+            hipLaunchKernelGGL(colsum_thin_kernel<T>, dim3(N), dim3(256), 0, s, (const T*)dY, HW, C, rowsum);
         else
-            hipLaunchKernelGGL(colsum_thin_kernel<float>, dim3(N), dim3(256), 0, s, (const float*)dY, HW, C, rowsum);
-    } else if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(colsum_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dY, HW, C, rowsum);
- else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(colsum_kernel<f16>, grid, dim3(256), 0, s, (const f16*)dY, HW, C, rowsum);
-    else
-        hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)dY, HW, C, rowsum);
+            hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, s, (const T*)dY, HW, C, rowsum);
+    });
     DMME_CHECK_LAUNCH();
     hipLaunchKernelGGL(bias_tproj_kernel, dim3((C + 255) / 256), dim3(256), 0, s, rowsum, N, C, dbias, dtproj, ld, nt);
     DMME_CHECK_LAUNCH();
@@ -564,15 +548,11 @@ int launch_gn_bwd_generic(int dtype, const void* dv, const void* x1, const void*
     const int cg = (C1 + C2) / groups;
     const size_t lds = (size_t)(2 * cg + 16) * sizeof(float);
     dim3 grid(groups, N);
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(gn_bwd_generic_kernel<bf16>, grid, dim3(256), lds, s, (const bf16*)dv, (const bf16*)x1, (const bf16*)x2, HW, C1, C2,
-                           groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (bf16*)dx1, (bf16*)dx2, acc1, acc2, dgamma, dbeta, mod);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(gn_bwd_generic_kernel<f16>, grid, dim3(256), lds, s, (const f16*)dv, (const f16*)x1, (const f16*)x2, HW, C1, C2,
-                           groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (f16*)dx1, (f16*)dx2, acc1, acc2, dgamma, dbeta, mod);
-    else
-        hipLaunchKernelGGL(gn_bwd_generic_kernel<float>, grid, dim3(256), lds, s, (const float*)dv, (const float*)x1, (const float*)x2, HW, C1,
-                           C2, groups, gamma, mean_rstd, scale, shift, dmask, pro_silu, (float*)dx1, (float*)dx2, acc1, acc2, dgamma, dbeta, mod);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(gn_bwd_generic_kernel<T>, grid, dim3(256), lds, s, (const T*)dv, (const T*)x1, (const T*)x2, HW, C1, C2, groups, gamma,
+                           mean_rstd, scale, shift, dmask, pro_silu, (T*)dx1, (T*)dx2, acc1, acc2, dgamma, dbeta, mod);
+    });
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -612,15 +592,10 @@ int launch_grad_acc(int dtype, const void* src, void* d1, void* d2, int C1, int 
     if (total == 0) return DMME_OK;
     int64_t b = (total + 255) / 256;
     if (b > 16384) b = 16384;
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(grad_acc_kernel<bf16>, dim3((unsigned)b), dim3(256), 0, s, (const bf16*)src, (bf16*)d1, (bf16*)d2, C1, C2, acc1, acc2, pool,
-                           H, W, total);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(grad_acc_kernel<f16>, dim3((unsigned)b), dim3(256), 0, s, (const f16*)src, (f16*)d1, (f16*)d2, C1, C2, acc1, acc2, pool,
-                           H, W, total);
-    else
-        hipLaunchKernelGGL(grad_acc_kernel<float>, dim3((unsigned)b), dim3(256), 0, s, (const float*)src, (float*)d1, (float*)d2, C1, C2, acc1, acc2,
-                           pool, H, W, total);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(grad_acc_kernel<T>, dim3((unsigned)b), dim3(256), 0, s, (const T*)src, (T*)d1, (T*)d2, C1, C2, acc1, acc2, pool, H, W, total);
+    });
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -727,21 +702,14 @@ int launch_attn_heads_bwd(int dtype, const void* qkv, const void* dO, int N, int
     const size_t ldsA = (size_t)(2 * d + 2 * S + 16) * sizeof(float), ldsB = (size_t)(2 * S) * sizeof(float);
     DMME_REQUIRE(ldsA <= 64 * 1024, DMME_ERR_UNSUPPORTED, "attention backward: d+S too large (%d+%d)", d, S);
     dim3 grid(S, N * heads);
-    if (dtype == DMME_BF16) {
-        hipLaunchKernelGGL(attn_bwd_rows_kernel<bf16>, grid, dim3(256), ldsA, s, (const bf16*)qkv, (const bf16*)dO, S, C, heads, N, P, dS, (bf16*)dqkv);
+    return with_dtype(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(attn_bwd_rows_kernel<T>, grid, dim3(256), ldsA, s, (const T*)qkv, (const T*)dO, S, C, heads, N, P, dS, (T*)dqkv);
         DMME_CHECK_LAUNCH();
-        hipLaunchKernelGGL(attn_bwd_cols_kernel<bf16>, grid, dim3(256), ldsB, s, (const bf16*)qkv, (const bf16*)dO, S, C, heads, N, P, dS, (bf16*)dqkv);
-    } else if (dtype == DMME_F16) {
-        hipLaunchKernelGGL(attn_bwd_rows_kernel<f16>, grid, dim3(256), ldsA, s, (const f16*)qkv, (const f16*)dO, S, C, heads, N, P, dS, (f16*)dqkv);
+        hipLaunchKernelGGL(attn_bwd_cols_kernel<T>, grid, dim3(256), ldsB, s, (const T*)qkv, (const T*)dO, S, C, heads, N, P, dS, (T*)dqkv);
         DMME_CHECK_LAUNCH();
-        hipLaunchKernelGGL(attn_bwd_cols_kernel<f16>, grid, dim3(256), ldsB, s, (const f16*)qkv, (const f16*)dO, S, C, heads, N, P, dS, (f16*)dqkv);
-    } else {
-        hipLaunchKernelGGL(attn_bwd_rows_kernel<float>, grid, dim3(256), ldsA, s, (const float*)qkv, (const float*)dO, S, C, heads, N, P, dS, (float*)dqkv);
-        DMME_CHECK_LAUNCH();
-        hipLaunchKernelGGL(attn_bwd_cols_kernel<float>, grid, dim3(256), ldsB, s, (const float*)qkv, (const float*)dO, S, C, heads, N, P, dS, (float*)dqkv);
-    }
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
+        return DMME_OK;
+    });
 }
 int launch_attn_bwd_generic(int dtype, const void* qkv, const void* dO, int N, int S, int C, float* P, float* dS, void* dqkv, hipStream_t s) {
     return launch_attn_heads_bwd(dtype, qkv, dO, N, S, C, 1, P, dS, dqkv, s);
@@ -780,12 +748,10 @@ __global__ void __launch_bounds__(256) silu_bwd_kernel(float* __restrict__ dy, c
 }
 int launch_lin_dinput(int dtype, const float* dY, const void* W, int R, int O, int K, float* dX, hipStream_t s) {
     const int total = R * K;
-    if (dtype == DMME_BF16)
-        hipLaunchKernelGGL(lin_dinput_kernel<bf16>, dim3((total + 255) / 256), dim3(256), 0, s, dY, (const bf16*)W, R, O, K, dX);
-    else if (dtype == DMME_F16)
-        hipLaunchKernelGGL(lin_dinput_kernel<f16>, dim3((total + 255) / 256), dim3(256), 0, s, dY, (const f16*)W, R, O, K, dX);
-    else
-        hipLaunchKernelGGL(lin_dinput_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, s, dY, (const float*)W, R, O, K, dX);
+    with_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(lin_dinput_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, dY, (const T*)W, R, O, K, dX);
+    });
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

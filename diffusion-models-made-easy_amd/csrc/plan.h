@@ -1,6 +1,12 @@
-// Shared definitions of the plan translation units (plan.hip: layer graph, layouts, plan creation and its device tables, forward;
-// plan_lvl.hip: level-engine planning and status; plan_bwd.hip: backward planning - gradient buckets, deferred tables - and the
-// backward pass): the plan's data model and the helpers that cross those files.
+// Shared definitions of the plan translation units (plan.hip: layer graph, forward layouts, plan creation and its device tables, forward;
+// plan_lvl.hip: level-engine planning and status; plan_bwd.hip: the backward): the plan's data model and the helpers that cross those files.
+//
+// The backward is planned in the phases of plan_backward(), after every forward phase: layout_backward (gradient buffers and their
+// aliases, the region cleared once per backward, per-op scratch, temporaries), plan_grad_buckets, build_wgrad_group (per bucket, then for
+// the whole plan: the grouped weight-gradient tables and the activated tensors they read), plan_deferred_reductions (bias / column-sum
+// jobs), plan_time_proj_tiles.  It runs as the reverse walk of backward_impl over the steps of BwdRun.  Which kernel serves an op is one
+// decision each, asked at plan time where the layout depends on it and again at dispatch: gn_bwd_route (bwd_fast.hip) for a GroupNorm's
+// backward, conv_route on dgrad_args for a data gradient, attn_bwd_route / bias_route / wgrad_route (plan_bwd.hip) for the rest.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>
@@ -277,7 +283,8 @@ void assign_lvl_nograd(dmme_plan* P);
 int lvl_check(const dmme_plan* P, const char* where, hipStream_t stream = nullptr, bool have_stream = false);
 // plan.hip: the weight-gradient image's unpack table, in parameter order (the gradient buckets cut it)
 void build_unpack_items(const dmme_plan* P, std::vector<PackItem>& items);
-// plan_bwd.hip: everything a backward of this plan is decided by at plan time (host arithmetic: plans without a device run it too)
+// plan_bwd.hip: everything a backward of this plan is decided by at plan time, the backward workspace's layout included (host
+// arithmetic: plans without a device run it too)
 void plan_backward(dmme_plan* P);
 
 }  // namespace dmme

@@ -502,96 +502,6 @@ int build_plan(dmme_plan* P) {
     P->ws_bytes = ws;
     P->n_launches = (int)ops.size();
 
-    // ---- backward workspace: one gradient buffer per forward tensor + temporaries ----
-    {
-        int64_t bw = 0;
-        auto balloc = [&](int64_t bytes) {
-            const int64_t o = bw;
-            bw = align_up(bw + bytes, 256);
-            return o;
-        };
-        int64_t tmp_max = 0, att_max = 0;
-        int cmax = c.in_channels;
-        for (const Tensor& t : P->tensors) {
-            P->gt_off.push_back(balloc((int64_t)B * t.H * t.W * t.C * es));
-            if (t.C > cmax) cmax = t.C;
-        }
-        // A ResBlock's 1x1 residual conv feeds nothing but the residual input of conv2: the gradient of its output IS the gradient of
-        // the block's output - the two tensors share one gradient buffer instead of a copy launch per block
-        if (!debug_route("no_res_alias")) {
-            std::vector<int> uses(P->tensors.size(), 0), producer(P->tensors.size(), -1);
-            for (int oi = 0; oi < (int)ops.size(); ++oi) {
-                const Op& o = ops[oi];
-                for (int id : {o.src1, o.src2, o.res1, o.res2, o.gn_src1, o.gn_src2, o.at_qkv})
-                    if (id >= 0) ++uses[id];
-                if (o.kind == OP_CONV && o.dst >= 0) producer[o.dst] = oi;
-            }
-            for (Op& o : ops) {
-                if (o.kind != OP_CONV || o.res1 < 0 || o.res2 >= 0 || o.dst < 0) continue;
-                const int r = o.res1;
-                if (uses[r] != 1 || producer[r] < 0 || ops[producer[r]].kind != OP_CONV || P->tensors[r].C != P->tensors[o.dst].C) continue;
-                P->gt_off[r] = P->gt_off[o.dst];
-                o.res_alias = 1;
-            }
-        }
-        for (const Op& o : ops) {
-            if (o.kind == OP_CONV && o.src1 >= 0) {
-                const Tensor& t1 = P->tensors[o.src1];
-                const int Cin = t1.C + (o.src2 >= 0 ? P->tensors[o.src2].C : 0);
-                const int64_t up = o.up ? 4 : 1;
-                const int64_t b = (int64_t)B * t1.H * t1.W * up * Cin * es;
-                if (b > tmp_max) tmp_max = b;
-            }
-            if (o.kind == OP_ATTN) {
-                const Tensor& q = P->tensors[o.at_qkv];
-                const int64_t b = (int64_t)B * o.at_heads * q.H * q.W * q.H * q.W * 4;
-                if (b > att_max) att_max = b;
-            }
-        }
-        {   // accumulation scratch, one contiguous region cleared by a single memset per backward:
-            // packed-layout weight-gradient image, per-conv column sums, per-GroupNorm channel sums
-            P->bws_zero = bw;
-            int64_t wfl = 0;
-            for (Param& p : P->params)
-                if (p.ndim == 4) {
-                    p.wp_off = wfl;
-                    wfl += (p.numel() + 63) / 64 * 64;
-                }
-            P->bws_wimage = balloc(wfl * 4);
-            for (Op& o : P->ops) {
-                if (o.kind != OP_CONV) continue;
-                o.b_rowsum = balloc((int64_t)B * P->params[o.w].cout * 4);
-            }
-            P->bws_zpage = balloc(256);  // a page of zeros: the padding rows of the DMA-fed weight gradient
-            P->bws_zero_bytes = bw - P->bws_zero;
-            for (Op& o : P->ops) {  // GroupNorm channel sums, one partial row per pixel chunk (written whole: outside the cleared region)
-                if (o.kind != OP_CONV || o.gn < 0) continue;
-                const Op& gop = P->ops[o.gn];
-                const Tensor& t1 = P->tensors[gop.gn_src1];
-                const int C = t1.C + (gop.gn_src2 >= 0 ? P->tensors[gop.gn_src2].C : 0);
-                o.b_ab = balloc((int64_t)gn_bwd_fast_chunks(P->dtype, t1.H * t1.W, C) * B * C * 2 * 4);
-                o.b_gnrows = balloc((int64_t)2 * B * C * 4);
-            }
-            P->bws_gnS = balloc((int64_t)B * c.num_groups * 2 * 4);
-        }
-        P->sink_half = (int64_t)2 * cmax;  // (a concatenated GroupNorm input has up to 2 x the widest tensor's channels)
-        P->bws_sink = balloc(2 * P->sink_half * 4);
-        if (cls) {
-            P->bws_hpool = balloc((int64_t)B * P->tensors[P->head_src].C * 4);
-            P->bws_hrows = balloc((int64_t)B * 2 * P->tensors[P->head_src].C * 4);
-        }
-        P->bws_tmp = balloc(tmp_max);
-        P->bws_dy = balloc(cls ? (int64_t)B * P->out_channels * 4 : (int64_t)B * P->H * P->W * P->out_channels * es);  // (classifier: d logits, fp32)
-        P->bws_rowsum = balloc((int64_t)B * cmax * 3 * 4);  // qkv convs have 3*C outputs
-        P->bws_dtproj = balloc((int64_t)B * tcols * 4);
-        P->bws_dtemb = balloc((int64_t)B * c.emb_dim * 4);
-        P->bws_dh1 = balloc((int64_t)B * c.emb_dim * 4);
-        P->bws_z = balloc((int64_t)B * c.emb_dim * 4);
-        P->bws_wT = balloc((int64_t)(tcols > c.emb_dim ? tcols : c.emb_dim) * c.emb_dim * es);
-        P->bws_attP = balloc(att_max);
-        P->bws_attdS = balloc(att_max);
-        P->bws_bytes = bw;
-    }
     return DMME_OK;
 }
 

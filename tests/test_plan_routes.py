@@ -1,6 +1,6 @@
-"""CPU: which kernels every plan of tools/plan_routes.py's matrix launches (networks x batches x precisions x forward route switches, host-only
-plans: device = -1) is what tests/plan_routes.json records - creation status, op labels, launch count, workspace bytes, backward
-summary.  The file is rewritten (python tools/plan_routes.py) only by a change that means to move a route; a refactor of the dispatch
+"""CPU: which kernels every plan of tools/plan_routes.py's matrix launches (networks x batches x precisions x forward route switches, and the
+backward switches each alone; host-only plans: device = -1) is what tests/plan_routes.json records - creation status, op labels, launch
+count, workspace bytes, backward summary, backward workspace bytes, bytes of the backward's packed weights.  The file is rewritten (python tools/plan_routes.py) only by a change that means to move a route; a refactor of the dispatch
 leaves it as the build before it produced it."""
 
 import importlib.util
@@ -37,3 +37,6 @@ def test_anchor_plans():
                               ("ddpm/b128/fp32", 128, 2_460_885_504)):
         assert (want[key]["launches"], want[key]["workspace_bytes"]) == (launches, ws), key
     assert want["tiny/b8/fp16r32"] == {"status": -2}  # (no silent 16-bit fall-back)
+    # the backward workspace: with and without the activated tensors the GroupNorm backward writes for the grouped weight gradient
+    assert want["ddpm/b128/bf16"]["bwd_workspace_bytes"] == 2_128_814_848
+    assert want["ddpm/b128/bf16/DMME_NO_WG_ACT"]["bwd_workspace_bytes"] == 1_449_337_600

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Which kernels every plan of a matrix of networks / batches / precisions / route switches launches, from host-only plans
 (device = -1: no GPU is touched).  Per plan: the creation status, the ordered op labels (one SHA-256), the launch count, the workspace
-bytes and the backward summary (one SHA-256 over its sorted key=value pairs: the library lists the dgrad[...] pairs in hash-map order).
+bytes, the backward summary (one SHA-256 over its sorted key=value pairs: the library lists the dgrad[...] pairs in hash-map order), the
+backward workspace bytes and the bytes of the backward's packed weights.
 
   python tools/plan_routes.py               rewrite tests/plan_routes.json from the library the package loads
   python tools/plan_routes.py --check       compare that library against tests/plan_routes.json (what tests/test_plan_routes.py does)
@@ -42,6 +43,13 @@ def switch_rows():
     return [("+".join(f"{k}={v}" if v != "1" else k for k, v in env.items()), env) for env, _ in FORWARD]
 
 
+def backward_switch_rows():
+    """(id, environment) of every backward switch of tests/test_gpu_switches.py, each set alone"""
+    from tests.test_gpu_switches import BACKWARD
+
+    return [(name, {name: "1"}) for name in BACKWARD]
+
+
 def matrix():
     """[(key, network, batch, precision, environment)]"""
     out = []
@@ -53,11 +61,17 @@ def matrix():
         for B in (BATCHES if net == "ddpm" else (1, 128)):
             for sid, env in switch_rows():
                 out.append((f"{net}/b{B}/bf16/{sid}", net, B, "bf16", env))
+    have = {key for key, *_ in out}  # (a few switches are in both lists)
+    for net in ("ddpm", "iddpm", "classifier"):
+        for B in (32, 128):
+            for sid, env in backward_switch_rows():
+                if f"{net}/b{B}/bf16/{sid}" not in have:
+                    out.append((f"{net}/b{B}/bf16/{sid}", net, B, "bf16", env))
     return out
 
 
 def listing(net, B, prec, env):
-    """status, op labels, launches, workspace bytes and backward summary of one host-only plan"""
+    """status, op labels, launches, workspace bytes, backward summary, backward workspace and packed bytes of one host-only plan"""
     from dmme_amd import _lib
     from dmme_amd.models.ddpm import _cfg_struct
     from tests.gpu_util import route_env
@@ -78,7 +92,8 @@ def listing(net, B, prec, env):
         buf = C.create_string_buffer(16384)
         _lib.check(lib.dmme_unet_plan_bwd_summary(h, buf, 16384), "bwd_summary")
         out = {"status": 0, "labels": labels, "launches": lib.dmme_unet_plan_num_launches(h), "workspace_bytes": lib.dmme_unet_plan_workspace_bytes(h),
-               "bwd_summary": sorted(buf.value.decode().split())}
+               "bwd_summary": sorted(buf.value.decode().split()), "bwd_workspace_bytes": lib.dmme_unet_plan_bwd_workspace_bytes(h),
+               "packed_bwd_bytes": lib.dmme_unet_plan_packed_bwd_bytes(h)}
         lib.dmme_unet_plan_destroy(h)
     return out
 
@@ -88,7 +103,7 @@ def entry(full):
         return {"status": full["status"]}
     sha = lambda lines: hashlib.sha256("\n".join(lines).encode()).hexdigest()
     return {"status": 0, "labels_sha256": sha(full["labels"]), "launches": full["launches"], "workspace_bytes": full["workspace_bytes"],
-            "bwd_summary_sha256": sha(full["bwd_summary"])}
+            "bwd_summary_sha256": sha(full["bwd_summary"]), "bwd_workspace_bytes": full["bwd_workspace_bytes"], "packed_bwd_bytes": full["packed_bwd_bytes"]}
 
 
 def table():
@@ -117,7 +132,7 @@ def main():
         full = listing(*rows[0][1:])
         print(f"{args.dump}: status {full['status']}")
         if full["status"] == 0:
-            print(f"launches {full['launches']}  workspace_bytes {full['workspace_bytes']}")
+            print(f"launches {full['launches']}  workspace_bytes {full['workspace_bytes']}  bwd_workspace_bytes {full['bwd_workspace_bytes']}  packed_bwd_bytes {full['packed_bwd_bytes']}")
             for i, l in enumerate(full["labels"]):
                 print(f"{i:4d}  {l}")
             print("\n".join(full["bwd_summary"]))
