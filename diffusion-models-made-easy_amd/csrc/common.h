@@ -399,6 +399,10 @@ int launch_time_sinusoid(const int64_t* t, int nt, const float* freqs, int half,
 // out[nt][Nout] = act(in[nt][K] . W[Nout][K]^T + b); in/out fp32, W in dtype
 int launch_linear_wave(int dtype, const float* in, int nt, int K, const void* W, const float* bias, int Nout,
                        int out_silu, float* out, hipStream_t s);
+// class conditioning (DMME_ARCH_DDPM_COND): temb = SiLU(z2 + E[y]) per image; the label table's gradient by one workgroup per row
+int launch_label_cond(const float* z2, int nt, const float* E, const int64_t* labels, int B, int K, int emb, float* temb, float* zsave, int* status,
+                      hipStream_t s);
+int launch_label_grad(const float* dz2, const int64_t* labels, int B, int K, int emb, float* dE, hipStream_t s);
 
 // mark / err (nullable): the backward's dY conversion checks the forward's mark (kFwdMarkNograd: NaN out, err = kErrNogradBackward)
 int launch_nchw_to_nhwc(int dtype, const float* src, int N, int C, int HW, void* dst, hipStream_t s, const unsigned* mark = nullptr,
@@ -435,6 +439,12 @@ int launch_slerp(const float* xa, const float* xb, const float* w, int n, int B,
 int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s);
 int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
                         hipStream_t s, const float* grad = nullptr, const float* noise = nullptr);
+// classifier-free guidance: x / out hold 2B images (conditional half, unconditional half); kinds DMME_CHAIN_DDPM_CFG / DMME_CHAIN_GDDIM_CFG
+int launch_cfg_step(int kind, float* x, const float* out, const float* z, float c0, float c1, float c2, float scale, int add_noise, int B, int64_t chw,
+                    hipStream_t s);
+int launch_chain_update_cfg(int kind, float* x, const float* out, const float* noise, const float* coef, const int64_t* t_table, void* state, int B,
+                            int64_t chw, hipStream_t s);
+int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient
 int launch_cls_head_fwd(int dtype, const void* top, int B, int HW, int C, int G, const float* gamma, const float* beta, const float* W,

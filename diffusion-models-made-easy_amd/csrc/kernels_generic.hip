@@ -544,6 +544,69 @@ int launch_time_sinusoid(const int64_t* t, int nt, const float* freqs, int half,
     return DMME_OK;
 }
 
+// Class conditioning (DMME_ARCH_DDPM_COND): temb[b] = SiLU(z2[r] + E[y_b]), r = b (nt == B) or 0 (nt == 1), one workgroup per image.
+// z2 is the second time Linear's pre-activation, E the (K+1, emb) label table whose row K is the null label.  zsave (nullable): also
+// receives z2[r] + E[y_b], the pre-activation the backward's SiLU' reads; it may be z2 itself where nt == B (every element is read and
+// written by the same thread), so neither pointer is __restrict__.  A label outside [0, K] is clamped BEFORE it indexes the table; its
+// temb row becomes NaN and *status (nullable) is set to 1, as by dmme_log_softmax_grad.
+__global__ void __launch_bounds__(256) label_cond_kernel(const float* z2, int nt, const float* __restrict__ E, const int64_t* __restrict__ labels, int K,
+                                                         int emb, float* __restrict__ temb, float* zsave, int* status) {
+    const int b = blockIdx.x;
+    const int64_t y = labels[b];
+    const bool ok = y >= 0 && y <= (int64_t)K;
+    const int row = y < 0 ? 0 : (y > (int64_t)K ? K : (int)y);
+    const float* zr = z2 + (int64_t)(nt == 1 ? 0 : b) * emb;
+    const float* er = E + (int64_t)row * emb;
+    for (int c = threadIdx.x; c < emb; c += blockDim.x) {
+        const float v = zr[c] + er[c];
+        if (zsave) zsave[(int64_t)b * emb + c] = v;
+        temb[(int64_t)b * emb + c] = ok ? silu_f(v) : NAN;
+    }
+    if (!ok && threadIdx.x == 0 && status) atomicExch(status, 1);
+}
+int launch_label_cond(const float* z2, int nt, const float* E, const int64_t* labels, int B, int K, int emb, float* temb, float* zsave, int* status,
+                      hipStream_t s) {
+    DMME_REQUIRE(z2 && E && labels && temb && B > 0 && K >= 1 && emb > 0 && (nt == 1 || nt == B), DMME_ERR_INVALID, "label_cond: bad argument");
+    DMME_REQUIRE(!zsave || zsave != z2 || nt == B, DMME_ERR_INVALID, "label_cond: in-place pre-activations need one time row per image");
+    hipLaunchKernelGGL(label_cond_kernel, dim3((unsigned)B), dim3(256), 0, s, z2, nt, E, labels, K, emb, temb, zsave, status);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// Gradient of the label table: dE[k] += sum over {b : y_b == k} of dz2[b], added in ascending b by the one workgroup that owns row k
+// (no atomics: equal inputs give equal bits).  A row no image of the batch carries is not touched; labels outside [0, K] match no row.
+// The batch goes through LDS in chunks of 256 match flags: every label is read from memory once per column pass, and the walk over a
+// chunk reads flags, not labels.  Every thread runs every barrier (the loops' bounds are uniform).
+__global__ void __launch_bounds__(256) label_grad_kernel(const float* __restrict__ dz2, const int64_t* __restrict__ labels, int B, int emb,
+                                                         float* __restrict__ dE) {
+    __shared__ unsigned char hit[256];
+    const int64_t k = blockIdx.x;
+    const int tid = threadIdx.x;
+    for (int c0 = 0; c0 < emb; c0 += 256) {
+        const int c = c0 + tid;
+        float acc = 0.f;
+        bool found = false;  // (the same in every thread: all walk the same flags)
+        for (int b0 = 0; b0 < B; b0 += 256) {
+            __syncthreads();
+            hit[tid] = (b0 + tid < B && labels[b0 + tid] == k) ? 1 : 0;
+            __syncthreads();
+            const int n = B - b0 < 256 ? B - b0 : 256;
+            for (int j = 0; j < n; ++j)
+                if (hit[j]) {
+                    found = true;
+                    if (c < emb) acc += dz2[(int64_t)(b0 + j) * emb + c];
+                }
+        }
+        if (found && c < emb) dE[k * emb + c] += acc;
+    }
+}
+int launch_label_grad(const float* dz2, const int64_t* labels, int B, int K, int emb, float* dE, hipStream_t s) {
+    DMME_REQUIRE(dz2 && labels && dE && B > 0 && K >= 1 && emb > 0, DMME_ERR_INVALID, "label_grad: bad argument");
+    hipLaunchKernelGGL(label_grad_kernel, dim3((unsigned)(K + 1)), dim3(256), 0, s, dz2, labels, B, emb, dE);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
 // nn.Linear on tiny batches: one wavefront per output feature, coalesced weight row,
 // shuffle reduction; loops over the nt input rows (1 when sampling, B when training).
 template <typename T>

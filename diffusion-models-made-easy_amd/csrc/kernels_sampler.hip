@@ -704,6 +704,133 @@ int launch_chain_update(int kind, float* x, const float* out, const float* coef,
     return DMME_OK;
 }
 
+// ------------------------------------------------------------------ classifier-free guidance (Ho & Salimans 2021)
+// x and the network output hold 2B images: the conditional half [0, B), then the unconditional half [B, 2B).  One element function for the
+// eager kernel (host scalars) and the chain kernel (device state): the mixed prediction e^ = e_u + s (e_c - e_u), three separately rounded
+// operations, then the base kind's update with e^.  s = 1 is plain conditional sampling (Ho & Salimans' w = s - 1).  The result goes to both
+// halves of x; noise is indexed by the element of the first half, so a chain at batch B draws exactly what an unguided chain at batch B does.
+template <int BASE>
+__device__ __forceinline__ float cfg_update(float x, float ec, float eu, float z, float c0, float c1, float c2, float s, int add_noise) {
+    const float e = __fadd_rn(eu, __fmul_rn(s, __fsub_rn(ec, eu)));
+    return sampler_update<BASE>(x, e, 0.f, 0.f, z, c0, c1, c2, 0.f, add_noise);
+}
+// the quad at element b of the first half (b + 3 < half, everything 16-byte aligned: chw % 4 == 0)
+template <int BASE>
+__device__ __forceinline__ void cfg_quad(float* __restrict__ x, const float* __restrict__ out, int64_t b, int64_t half, const float (&z)[4], float c0, float c1,
+                                         float c2, float s, int add_noise) {
+    float4 xv = load4(x + b);
+    const float4 cv = load4(out + b), uv = load4(out + half + b);
+    float* xs = reinterpret_cast<float*>(&xv);
+    const float *cs = reinterpret_cast<const float*>(&cv), *us = reinterpret_cast<const float*>(&uv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xs[j] = cfg_update<BASE>(xs[j], cs[j], us[j], z[j], c0, c1, c2, s, add_noise);
+    *reinterpret_cast<float4*>(x + b) = xv;
+    *reinterpret_cast<float4*>(x + half + b) = xv;
+}
+template <int BASE>
+__global__ void __launch_bounds__(256) cfg_eager_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ zin, float c0, float c1,
+                                                        float c2, float s, int add_noise, int64_t n4) {
+    const int64_t half = n4 * 4;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (add_noise) {
+            const float4 zv = load4(zin + q * 4);
+            z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+        }
+        cfg_quad<BASE>(x, out, q * 4, half, z, c0, c1, c2, s, add_noise);
+    }
+}
+// the chain form: scalars from coef[i] (s = coef[i][3]), normals drawn at Philox(seed, offset + quad of the FIRST half) unless zin is given;
+// the last block advances the state by the quads of ONE half
+template <int BASE>
+__global__ void __launch_bounds__(256) cfg_chain_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ coef,
+                                                        const long long* __restrict__ t_table, ChainState* st, int64_t n4, const float* __restrict__ zin) {
+    const long long i = st->i, t = st->t;
+    const unsigned long long off = st->offset, seed = st->seed;
+    const float c0 = coef[4 * i], c1 = coef[4 * i + 1], c2 = coef[4 * i + 2], sc = coef[4 * i + 3];
+    const int add_noise = BASE == DMME_CHAIN_GDDIM ? c2 != 0.0f : t != 1;
+    const int64_t half = n4 * 4;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (add_noise) {
+            if (zin) {
+                const float4 zv = load4(zin + q * 4);
+                z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+            } else {
+                normal4(seed, off + (uint64_t)q, z);
+            }
+        }
+        cfg_quad<BASE>(x, out, q * 4, half, z, c0, c1, c2, sc, add_noise);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned tk = atomicAdd(&st->ticket, 1u);
+        if (tk == gridDim.x - 1) {
+            const long long ni = i > 0 ? i - 1 : 0;
+            st->i = ni;
+            st->t = t_table[ni];
+            st->offset = off + (unsigned long long)n4;
+            atomicExch(&st->ticket, 0u);
+        }
+    }
+}
+static int cfg_check(const char* what, int kind, const void* x, const void* out, int B, int64_t chw) {
+    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_CFG || kind == DMME_CHAIN_GDDIM_CFG, DMME_ERR_INVALID, "%s: kind %d is not a classifier-free kind (6, 7)", what, kind);
+    DMME_REQUIRE(x && out && B > 0 && chw > 0, DMME_ERR_INVALID, "%s: bad argument", what);
+    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "%s: image size %lld is not a multiple of 4", what, (long long)chw);
+    return DMME_OK;
+}
+int launch_cfg_step(int kind, float* x, const float* out, const float* z, float c0, float c1, float c2, float scale, int add_noise, int B, int64_t chw,
+                    hipStream_t s) {
+    if (int rc = cfg_check("cfg_step", kind, x, out, B, chw)) return rc;
+    if (kind == DMME_CHAIN_GDDIM_CFG) add_noise = c2 != 0.0f;
+    DMME_REQUIRE(z || !add_noise, DMME_ERR_INVALID, "cfg_step: a step that adds noise needs z");
+    const int64_t n4 = (int64_t)B * chw / 4;
+    const dim3 g(grid_for(n4)), b(256);
+    if (kind == DMME_CHAIN_DDPM_CFG)
+        hipLaunchKernelGGL(cfg_eager_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, z, c0, c1, c2, scale, add_noise, n4);
+    else
+        hipLaunchKernelGGL(cfg_eager_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, z, c0, c1, c2, scale, add_noise, n4);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+int launch_chain_update_cfg(int kind, float* x, const float* out, const float* noise, const float* coef, const int64_t* t_table, void* state, int B,
+                            int64_t chw, hipStream_t s) {
+    if (int rc = cfg_check("chain_update_cfg", kind, x, out, B, chw)) return rc;
+    DMME_REQUIRE(coef && t_table && state, DMME_ERR_INVALID, "chain_update_cfg: null argument");
+    const int64_t n4 = (int64_t)B * chw / 4;
+    const dim3 g(grid_for(n4)), b(256);
+    if (kind == DMME_CHAIN_DDPM_CFG)
+        hipLaunchKernelGGL(cfg_chain_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, coef, (const long long*)t_table, (ChainState*)state, n4, noise);
+    else
+        hipLaunchKernelGGL(cfg_chain_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, coef, (const long long*)t_table, (ChainState*)state, n4, noise);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// Label dropout of classifier-free training: out[b] = K (the null label) where u_b < p, else labels[b]; u_b = u01(word b % 4 of the quad at
+// counter offset + b / 4), the layout of a span (seed, offset, B) of the stream (dmme_hip.h).  p >= 1 drops every label (u = 1 is on the grid).
+// A label outside [0, K] is copied through and sets *status (nullable).
+__global__ void __launch_bounds__(256) label_dropout_kernel(const int64_t* __restrict__ labels, int B, int K, float p, uint64_t seed, uint64_t offset,
+                                                            int64_t* __restrict__ out, int* status) {
+    const int quads = (B + 3) / 4;
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += gridDim.x * blockDim.x) {
+        uint32_t r[4];
+        philox4x32_10(seed, offset + (uint64_t)q, r);
+        for (int j = 0; j < 4 && q * 4 + j < B; ++j) {
+            const int64_t y = labels[q * 4 + j];
+            if ((y < 0 || y > (int64_t)K) && status) atomicExch(status, 1);
+            out[q * 4 + j] = (u01(r[j]) < p || p >= 1.0f) ? (int64_t)K : y;
+        }
+    }
+}
+int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s) {
+    DMME_REQUIRE(labels && out && B > 0 && K >= 1 && p >= 0.0f && p <= 1.0f, DMME_ERR_INVALID, "label_dropout: bad argument (B = %d, K = %d, p = %g)", B, K, (double)p);
+    hipLaunchKernelGGL(label_dropout_kernel, dim3(grid_for((B + 3) / 4)), dim3(256), 0, s, labels, B, K, p, seed, offset, out, status);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
 // ------------------------------------------------------------------ spherical interpolation of latents (dmme_hip.h: dmme_slerp)
 // Two launches.  (1) per image pair, <xa, xb>, |xa|^2 and |xb|^2: `parts` blocks per image each leave three partial sums
 // (float4 loads, wave / block sums; stores, no atomics: the result does not depend on arrival order).  (2) every block of the

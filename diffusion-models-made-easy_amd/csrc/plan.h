@@ -94,7 +94,7 @@ struct Tensor {  // an activation in the workspace, NHWC in the compute dtype
     int stats_tiles = 0, stats_cnt = 0;
 };
 
-enum OpKind { OP_SINUS, OP_LINEAR, OP_GN, OP_CONV, OP_ATTN, OP_CAST };
+enum OpKind { OP_SINUS, OP_LINEAR, OP_GN, OP_CONV, OP_ATTN, OP_CAST, OP_LABEL };  // OP_LABEL: temb = SiLU(z2 + E[y]) (conditional plans, between the second time Linear and the projections)
 
 struct Op {
     OpKind kind;
@@ -187,6 +187,10 @@ struct dmme_plan {
     // middle layers' output); its parameters: out.0 (gamma, beta) and out.2 (weight [K][C_top], bias), fp32 in the packed buffer
     int head_src = -1, p_hgw = -1, p_hgb = -1, p_hw = -1, p_hb = -1;
     int64_t bws_hpool = 0, bws_hrows = 0;  // backward: pooled activations [B][C_top], per-image d beta / d gamma [B][2][C_top]
+    // DMME_ARCH_DDPM_COND: cfg.arch is DMME_ARCH_DDPM here (routes, engine, residual segments and buckets are the DDPM UNet's) and cond says
+    // the rest: the label table `label_emb.weight` (cfg.num_classes + 1, emb_dim) is parameter p_lemb, op label_op adds its rows.  The second
+    // time Linear of such a plan writes its pre-activation (ws_tz2) only; every op behind label_op runs with B time rows.
+    int cond = 0, p_lemb = -1, label_op = -1;
     std::vector<Param> params;
     std::vector<Tensor> tensors;
     std::vector<Op> ops;

@@ -206,6 +206,8 @@ int build_plan(dmme_plan* P) {
         P->out_channels = c.arch == DMME_ARCH_IDDPM ? 2 * c.in_channels : c.in_channels;
         bld.conv("output_conv.2", chans[0], P->out_channels, 3, ocw, ocb);
     }
+    if (P->cond)  // behind everything else: an unconditional flat buffer is a prefix of a conditional one.  Row num_classes: the null label
+        P->p_lemb = bld.add_param("label_emb.weight", {c.num_classes + 1, c.emb_dim}, false, true, c.num_classes + 1, c.emb_dim, 1);
     P->ref_numel = bld.ref_cursor;
 
     // ---- packed layout: the per-block time projections form one [sumCout][emb] matrix ----
@@ -297,7 +299,18 @@ int build_plan(dmme_plan* P) {
         b.lin_in = P->ws_th1; b.lin_out = P->ws_temb; b.lin_K = c.emb_dim; b.lin_N = c.emb_dim;
         b.lin_pre = P->ws_tz2;
         b.lin_w = l2w; b.lin_b = l2b; b.lin_silu = 1;
+        if (P->cond) {  // the pre-activation alone (the wave kernel of small batches writes no second output): the label op finishes the layer
+            b.lin_out = P->ws_tz2;
+            b.lin_pre = -1;
+            b.lin_silu = 0;
+        }
         ops.push_back(b);
+        if (P->cond) {
+            Op l{};
+            l.kind = OP_LABEL;
+            P->label_op = (int)ops.size();
+            ops.push_back(l);
+        }
         Op d{};
         d.kind = OP_LINEAR;  // all per-block projections at once (w/b = -1: concatenated region)
         d.lin_in = P->ws_temb; d.lin_out = P->ws_tproj; d.lin_K = c.emb_dim; d.lin_N = tcols;
@@ -1015,7 +1028,7 @@ int run_gn(const dmme_plan* P, const Op& o, const char* pk, char* ws, int nt, co
 
 // keep_ctx: a backward pass may follow this forward (tensors only the backward reads are written: the fused attention block's context)
 int run_op(const dmme_plan* P, const Op& o, const char* pk, const float* x, const int64_t* t, int nt, float* y,
-           char* ws, const float* drop_masks, hipStream_t s, bool keep_ctx) {
+           char* ws, const float* drop_masks, hipStream_t s, bool keep_ctx, const int64_t* labels = nullptr, int* status = nullptr) {
     if (o.lvl >= 0) return o.lvl_first ? run_level(P, P->lvl_runs[o.lvl], pk, ws, nt, drop_masks, s, keep_ctx) : DMME_OK;
     if (o.fused_away) return DMME_OK;  // a residual 1x1 conv that runs inside its block's conv2 (assign_rseg)
     switch (o.kind) {
@@ -1031,6 +1044,11 @@ int run_op(const dmme_plan* P, const Op& o, const char* pk, const float* x, cons
                                          (float*)(ws + o.lin_out), o.lin_N, s, o.lin_pre >= 0 ? (float*)(ws + o.lin_pre) : nullptr);
             return launch_linear_wave(P->dtype, (const float*)(ws + o.lin_in), nt, o.lin_K, w, b, o.lin_N, o.lin_silu,
                                       (float*)(ws + o.lin_out), s);
+        }
+        case OP_LABEL: {  // nt: the rows the time MLP ran with; writes B rows (and keeps z2 + E[y] for the backward where they are B too)
+            float* z2 = (float*)(ws + P->ws_tz2);
+            return launch_label_cond(z2, nt, (const float*)(pk + P->params[P->p_lemb].packed_off), labels, P->B, P->cfg.num_classes, P->cfg.emb_dim,
+                                     (float*)(ws + P->ws_temb), nt == P->B ? z2 : nullptr, status, s);
         }
         case OP_GN:
             return run_gn(P, o, pk, ws, nt, drop_masks, s);
@@ -1091,6 +1109,11 @@ void op_account(const dmme_plan* P, const Op& o, char* label, int cap, double* f
     switch (o.kind) {
         case OP_SINUS:
             snprintf(label, cap, "time_sinusoid_kernel");
+            break;
+        case OP_LABEL:
+            snprintf(label, cap, "label_cond_kernel");
+            *flops = B * P->cfg.emb_dim;
+            *bytes = 4.0 * B * P->cfg.emb_dim * 3;
             break;
         case OP_LINEAR:
             snprintf(label, cap, "linear_wave_kernel<%s>", tn);
@@ -1165,8 +1188,13 @@ static int check_cfg(const dmme_unet_cfg* cfg, int B, int H, int W, int dtype) {
                  "plan_create: bad depth/blocks");
     DMME_REQUIRE(cfg->num_attention_depths >= 0 && cfg->num_attention_depths <= 8, DMME_ERR_INVALID, "bad attention_depths");
     DMME_REQUIRE(cfg->pos_dim >= 4 && cfg->pos_dim % 2 == 0, DMME_ERR_INVALID, "pos_dim must be even and >= 4");
-    DMME_REQUIRE(cfg->arch == DMME_ARCH_DDPM || cfg->arch == DMME_ARCH_IDDPM || cfg->arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
-                 "plan_create: unknown arch %d", cfg->arch);
+    DMME_REQUIRE(cfg->arch == DMME_ARCH_DDPM || cfg->arch == DMME_ARCH_IDDPM || cfg->arch == DMME_ARCH_CLASSIFIER || cfg->arch == DMME_ARCH_DDPM_COND,
+                 DMME_ERR_INVALID, "plan_create: unknown arch %d", cfg->arch);
+    if (cfg->arch == DMME_ARCH_DDPM_COND) {
+        const bool x3 = dtype == DMME_BF16X3, mix = dtype == DMME_F16R32;
+        DMME_REQUIRE(!x3 && !mix, DMME_ERR_UNSUPPORTED, "plan_create: the class-conditional UNet runs in fp32, bf16 or fp16 (not %s)", x3 ? "bf16x3" : "fp16r32");
+        DMME_REQUIRE(cfg->num_classes >= 1, DMME_ERR_INVALID, "plan_create: class-conditional UNet with num_classes=%d", cfg->num_classes);
+    }
     if (cfg->arch == DMME_ARCH_CLASSIFIER) {
         const bool x3 = dtype == DMME_BF16X3, mix = dtype == DMME_F16R32;
         DMME_REQUIRE(!x3 && !mix, DMME_ERR_UNSUPPORTED, "plan_create: the classifier runs in fp32, bf16 or fp16 (not %s)", x3 ? "bf16x3" : "fp16r32");
@@ -1256,7 +1284,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 109; }  // 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 110; }  // 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1269,6 +1297,10 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
     std::unique_ptr<dmme_plan> owned(new dmme_plan());  // (a failed create frees the plan and, through their types, its tables)
     dmme_plan* P = owned.get();
     P->cfg = *cfg;
+    if (cfg->arch == DMME_ARCH_DDPM_COND) {  // the DDPM UNet plus one parameter: everything that asks for the architecture sees DDPM
+        P->cond = 1;
+        P->cfg.arch = DMME_ARCH_DDPM;
+    }
     P->B = B;
     P->H = H;
     P->W = W;
@@ -1327,9 +1359,14 @@ DMME_API int dmme_unet_pack_params(const dmme_plan* plan, const float* ref_flat,
     return launch_pack_table(plan->dtype, plan->items_dev.get(), plan->n_items, ref_flat, packed, (hipStream_t)stream);
 }
 
+// labels / status: the conditional form (dmme_unet_forward_cond); a conditional plan never runs without labels
 static int unet_forward_impl(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len,
-                      float* y, void* workspace, const float* drop_masks, void* stream, bool keep_ctx) {
+                      float* y, void* workspace, const float* drop_masks, void* stream, bool keep_ctx, const int64_t* labels = nullptr,
+                      int* status = nullptr) {
     DMME_REQUIRE(plan && packed && x && t && y && workspace, DMME_ERR_INVALID, "unet_forward: null argument");
+    DMME_REQUIRE((plan->cond != 0) == (labels != nullptr), DMME_ERR_INVALID,
+                 plan->cond ? "unet_forward: a class-conditional plan (DMME_ARCH_DDPM_COND) takes labels: call dmme_unet_forward_cond / dmme_cfg_chain_step"
+                            : "unet_forward_cond: the plan is not class-conditional (DMME_ARCH_DDPM_COND)");
     DMME_REQUIRE(t_len == 1 || t_len == plan->B, DMME_ERR_INVALID,
                  "unet_forward: timestep tensor of length %d does not broadcast against batch %d", t_len, plan->B);
     {
@@ -1346,8 +1383,9 @@ static int unet_forward_impl(const dmme_plan* plan, const void* packed, const fl
     } else {
         plan->nograd_ws = workspace;
     }
-    for (const Op& o : P->ops) {
-        const int rc = run_op(P, o, pk, x, t, nt, y, ws, drop_masks, s, keep_ctx);
+    for (int oi = 0; oi < (int)P->ops.size(); ++oi) {
+        // behind the label op every image has its own time row, whatever t_len was
+        const int rc = run_op(P, P->ops[oi], pk, x, t, P->cond && oi > P->label_op ? P->B : nt, y, ws, drop_masks, s, keep_ctx, labels, status);
         if (rc != DMME_OK) return rc;
     }
     if (P->head_src >= 0) {  // classifier head: GroupNorm + SiLU + spatial mean + Linear -> logits (B, K), one launch
@@ -1369,6 +1407,12 @@ DMME_API int dmme_unet_forward_nograd(const dmme_plan* plan, const void* packed,
     return unet_forward_impl(plan, packed, x, t, t_len, y, workspace, drop_masks, stream, false);
 }
 
+DMME_API int dmme_unet_forward_cond(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len, const int64_t* labels,
+                                    float* y, void* workspace, const float* drop_masks, int keep_ctx, int* status, void* stream) {
+    DMME_REQUIRE(labels, DMME_ERR_INVALID, "unet_forward_cond: null argument (labels)");
+    return unet_forward_impl(plan, packed, x, t, t_len, y, workspace, drop_masks, stream, keep_ctx != 0, labels, status);
+}
+
 DMME_API int dmme_unet_plan_num_ops(const dmme_plan* plan) { return plan ? (int)plan->ops.size() : 0; }
 
 DMME_API int dmme_unet_plan_op_info(const dmme_plan* plan, int index, char* label, int label_cap, double* flops,
@@ -1384,6 +1428,7 @@ DMME_API int dmme_unet_forward_profiled(const dmme_plan* plan, const void* packe
                                         float* op_ms) {
     DMME_REQUIRE(plan && packed && x && t && y && workspace && op_ms, DMME_ERR_INVALID, "forward_profiled: null argument");
     DMME_REQUIRE(t_len == 1 || t_len == plan->B, DMME_ERR_INVALID, "forward_profiled: bad t_len %d", t_len);
+    DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "forward_profiled: a class-conditional plan takes labels (dmme_unet_forward_cond); this entry point has none");
     if (int rc0 = lvl_check(plan, "forward_profiled", (hipStream_t)stream, true)) return rc0;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = plan->ops.size();
@@ -1543,6 +1588,7 @@ DMME_API int dmme_chain_update_gddim(float* x, const float* model_out, const flo
 DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
                              const float* step_coef, const int64_t* t_table, void* state, void* stream) {
     DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state, DMME_ERR_INVALID, "chain_step: null argument");
+    DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "chain_step: a class-conditional plan takes labels: call dmme_cfg_chain_step");
     if (int rc0 = lvl_check(plan, "chain_step", (hipStream_t)stream, true)) return rc0;
     DMME_REQUIRE(((kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_IDDPM) || kind == DMME_CHAIN_GDDIM) && plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
                  "chain_step: sampler kind %d / architecture %d (guided kinds: dmme_guided_chain_step)", kind, plan->cfg.arch);
@@ -1554,6 +1600,34 @@ DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x
     if (rc != DMME_OK) return rc;
     return launch_chain_update(kind, x, model_out, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
                                (hipStream_t)stream);
+}
+
+DMME_API int dmme_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, void* stream) {
+    return launch_label_dropout(labels, B, K, p, seed, offset, out, status, (hipStream_t)stream);
+}
+
+DMME_API int dmme_cfg_step(int kind, float* x, const float* model_out, const float* z, float c0, float c1, float c2, float s, int add_noise, int B,
+                           int64_t chw, void* stream) {
+    return launch_cfg_step(kind, x, model_out, z, c0, c1, c2, s, add_noise, B, chw, (hipStream_t)stream);
+}
+
+DMME_API int dmme_chain_update_cfg(int kind, float* x, const float* model_out, const float* noise, const float* step_coef, const int64_t* t_table,
+                                   void* state, int B, int64_t chw, void* stream) {
+    return launch_chain_update_cfg(kind, x, model_out, noise, step_coef, t_table, state, B, chw, (hipStream_t)stream);
+}
+
+// Ho & Salimans 2021 as one launch sequence: both halves in one forward at batch 2B, then the mixing update (capturable)
+DMME_API int dmme_cfg_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
+                                 int* status, int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan_2B && packed && x_2B && labels_2B && model_out && workspace && step_coef && t_table && state, DMME_ERR_INVALID, "cfg_chain_step: null argument");
+    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_CFG || kind == DMME_CHAIN_GDDIM_CFG, DMME_ERR_INVALID, "cfg_chain_step: kind %d is not a classifier-free kind (6, 7)", kind);
+    DMME_REQUIRE(plan_2B->cond && plan_2B->B % 2 == 0, DMME_ERR_INVALID,
+                 "cfg_chain_step: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", plan_2B->B);
+    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
+    const int rc = unet_forward_impl(plan_2B, packed, x_2B, t_dev, 1, model_out, workspace, nullptr, stream, false, labels_2B, status);
+    if (rc != DMME_OK) return rc;
+    return launch_chain_update_cfg(kind, x_2B, model_out, nullptr, step_coef, t_table, state, plan_2B->B / 2,
+                                   (int64_t)plan_2B->cfg.in_channels * plan_2B->H * plan_2B->W, (hipStream_t)stream);
 }
 
 // The two launches of dmme_slerp hand three partial sums per (image, block) from one to the other.  The entry point takes no scratch
@@ -1603,7 +1677,7 @@ DMME_API int dmme_guided_chain_step(const dmme_plan* plan, const void* packed, c
     DMME_REQUIRE(plan && packed && cls && cls_packed && cls_packed_bwd && x && model_out && workspace && cls_workspace && cls_bwd_workspace && y &&
                  logits && d_logits && grad && step_coef && t_table && state, DMME_ERR_INVALID, "guided_chain_step: null argument");
     DMME_REQUIRE(kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED, DMME_ERR_INVALID, "guided_chain_step: kind %d is not a guided kind", kind);
-    DMME_REQUIRE(plan->cfg.arch == DMME_ARCH_DDPM && cls->cfg.arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+    DMME_REQUIRE(plan->cfg.arch == DMME_ARCH_DDPM && !plan->cond && cls->cfg.arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
                  "guided_chain_step: needs a DDPM UNet plan and a classifier plan (got architectures %d, %d)", plan->cfg.arch, cls->cfg.arch);
     DMME_REQUIRE(plan->B == cls->B && plan->H == cls->H && plan->W == cls->W && plan->cfg.in_channels == cls->cfg.in_channels, DMME_ERR_INVALID,
                  "guided_chain_step: the UNet plan (B=%d %dx%d) and the classifier plan (B=%d %dx%d) differ", plan->B, plan->H, plan->W, cls->B, cls->H, cls->W);

@@ -520,6 +520,7 @@ struct BwdRun {
     int next_bucket = 0;  // the bucket whose stretch the reverse walk is in
     float *wimage, *dtproj, *sink;  // sink: input-only form, the GroupNorm backward's d gamma / d beta land here, unread
     char* tmp;
+    const int64_t* labels = nullptr;  // conditional plans: the labels of the forward this backward follows
 
     BwdRun(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x_, int t_len, const float* dy_, void* workspace, void* bwd_workspace,
            const float* masks, float* grad, float* dx, void* stream, dmme_bucket_fn ready_, void* user_)
@@ -797,11 +798,13 @@ struct BwdRun {
         // temb = silu(z2), z2 = h1 W2^T + b2
         // (the forward kept both pre-activations when it ran at a training batch: no recompute GEMMs here)
         const bool saved_pre = nt > 4 && P->ws_tz1 >= 0 && P->ws_tz2 >= 0 && !time_pre_off;
-        if (saved_pre)
+        if (saved_pre || P->cond)  // (a conditional forward always keeps z2 + E[y] there: the label op wrote it)
             z = (float*)(ws + P->ws_tz2);
         else
             rc = launch_small_gemm(dt, 0, h1, emb, pk + P->params[P->p_l2w].packed_off, emb, nt, emb, emb, (const float*)(pk + P->params[P->p_l2b].packed_off), 0, z, emb, s);
         if (rc == DMME_OK) rc = launch_silu_bwd(dtemb, z, nt * emb, s);
+        if (rc == DMME_OK && P->cond)  // dtemb holds d z2 now: the label rows take their images' sums
+            rc = launch_label_grad(dtemb, labels, B, P->cfg.num_classes, emb, grad_flat + P->params[P->p_lemb].ref_off, s);
         if (rc == DMME_OK) rc = launch_small_gemm(dt, 2, dtemb, emb, h1, emb, emb, emb, nt, nullptr, 0, grad_flat + P->params[P->p_l2w].ref_off, emb, s);
         if (rc == DMME_OK) rc = launch_nsum(dtemb, nt, emb, emb, 1, grad_flat + P->params[P->p_l2b].ref_off, s);
         if (rc == DMME_OK) rc = launch_transpose(dt, pk + P->params[P->p_l2w].packed_off, emb, emb, wT, s);
@@ -821,11 +824,18 @@ struct BwdRun {
 
 static int backward_impl(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t, int t_len,
                          const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks, float* grad_flat, float* d_x,
-                         void* stream, dmme_bucket_fn ready, void* user) {
+                         void* stream, dmme_bucket_fn ready, void* user, const int64_t* labels = nullptr) {
     const bool weights = grad_flat != nullptr;  // (false: dmme_unet_backward_input)
     DMME_REQUIRE(plan && packed && packed_bwd && x && t && d_y && workspace && bwd_workspace && (weights || d_x), DMME_ERR_INVALID,
                  "unet_backward: null argument");
     DMME_REQUIRE(t_len == 1 || t_len == plan->B, DMME_ERR_INVALID, "unet_backward: bad t_len %d", t_len);
+    DMME_REQUIRE((plan->cond != 0) == (labels != nullptr), DMME_ERR_INVALID,
+                 plan->cond ? "unet_backward: a class-conditional plan (DMME_ARCH_DDPM_COND) takes labels: call dmme_unet_backward_cond / dmme_unet_backward_input_cond"
+                            : "unet_backward_cond: the plan is not class-conditional (DMME_ARCH_DDPM_COND)");
+    // (the conditional forward ran with one time row per image behind the label op: a shared t has no per-row gradient to reduce)
+    DMME_REQUIRE(!plan->cond || !weights || t_len == plan->B, DMME_ERR_INVALID,
+                 "unet_backward_cond: parameter gradients need one timestep per image (t_len = %d, B = %d)", t_len, plan->B);
+    if (plan->cond) t_len = plan->B;  // what the forward's ops behind the label op ran with
     if (int rc0 = lvl_check(plan, "unet_backward", (hipStream_t)stream, true)) return rc0;  // (the forward this backward differentiates ran through the engine)
     DMME_REQUIRE(!plan->mix, DMME_ERR_UNSUPPORTED, "unet_backward: precision fp16r32 is an inference mode");
     DMME_REQUIRE(plan->nograd_ws != workspace, DMME_ERR_INVALID,
@@ -833,6 +843,7 @@ static int backward_impl(const dmme_plan* plan, const void* packed, const void* 
                  "backward pass reads; run dmme_unet_forward first");
     const dmme_plan* P = plan;
     BwdRun R(P, packed, packed_bwd, x, t_len, d_y, workspace, bwd_workspace, drop_masks, grad_flat, d_x, stream, ready, user);
+    R.labels = labels;
     int rc = R.head();
     for (int oi = (int)P->ops.size() - 1; oi >= 0 && rc == DMME_OK; --oi) {
         if (R.bucket_done(oi)) {
@@ -878,6 +889,20 @@ DMME_API int dmme_unet_backward_buckets(const dmme_plan* plan, const void* packe
     DMME_REQUIRE(grad_flat, DMME_ERR_INVALID, "unet_backward: null argument (grad_flat)");
     DMME_REQUIRE(ready, DMME_ERR_INVALID, "unet_backward_buckets: null callback");
     return backward_impl(plan, packed, packed_bwd, x, t, t_len, d_y, workspace, bwd_workspace, drop_masks, grad_flat, d_x, stream, ready, user);
+}
+
+DMME_API int dmme_unet_backward_cond(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t, int t_len,
+                                     const int64_t* labels, const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks,
+                                     float* grad_flat, float* d_x, void* stream, dmme_bucket_fn ready, void* user) {
+    DMME_REQUIRE(grad_flat && labels, DMME_ERR_INVALID, "unet_backward_cond: null argument (grad_flat / labels)");
+    return backward_impl(plan, packed, packed_bwd, x, t, t_len, d_y, workspace, bwd_workspace, drop_masks, grad_flat, d_x, stream, ready, user, labels);
+}
+
+DMME_API int dmme_unet_backward_input_cond(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t,
+                                           int t_len, const int64_t* labels, const float* d_y, void* workspace, void* bwd_workspace,
+                                           const float* drop_masks, float* d_x, void* stream) {
+    DMME_REQUIRE(d_x && labels, DMME_ERR_INVALID, "unet_backward_input_cond: d_x and labels are required");
+    return backward_impl(plan, packed, packed_bwd, x, t, t_len, d_y, workspace, bwd_workspace, drop_masks, nullptr, d_x, stream, nullptr, nullptr, labels);
 }
 
 DMME_API int dmme_unet_plan_grad_buckets(const dmme_plan* plan, int64_t* offsets, int64_t* numels, int* bucket_of, int cap) {

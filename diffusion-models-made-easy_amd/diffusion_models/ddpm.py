@@ -64,6 +64,7 @@ class ChainRunner(ChainTables):
         super().__init__(rows, ttab, x.device)
         self.out = torch.empty((B, model.out_channels, H, W), dtype=torch.float32, device=x.device)
         self.quads = x.numel() // 4
+        self.noise_numel = x.numel()  # normals one step consumes (a runner whose buffer holds more than the images it draws for says so)
         self.use_graph = use_graph
         self.graph = None
         self.capture_error = None  # why this runner launches eagerly although a graph was asked for (None: it does not)
@@ -126,7 +127,7 @@ class ChainRunner(ChainTables):
         if not self.draws:  # a chain that draws nothing: torch's generator stays where the eager loop leaves it
             seed, off = 0, 0
         else:
-            seed, off = philox_reserve(self.x.device, self.x.numel() * count)
+            seed, off = philox_reserve(self.x.device, self.noise_numel * count)
         self.set(first, seed, off)
         for _ in range(count):
             self.step()

@@ -29,20 +29,19 @@ from .. import _lib
 from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..diffusion_models.ddim import DDIM
 from ..diffusion_models.ddpm import DDPM, ChainRunner, ChainTables, _scalar_index
+from ..models.cond import class_labels
 from ..models.ddpm import UNet
 
-__all__ = ["EncoderClassifier", "ClassifierGuidedDDPM", "ClassifierGuidedDDIM", "GuidedChainRunner", "classifier_loss", "cross_entropy_apply"]
+__all__ = ["EncoderClassifier", "ClassifierGuidedDDPM", "ClassifierGuidedDDIM", "GuidedChainRunner", "classifier_loss", "cross_entropy_apply",
+           "ClassifierFreeDDPM", "ClassifierFreeDDIM", "CFGChainRunner"]
+
+
+from .cfg import CFGChainRunner, ClassifierFreeDDIM, ClassifierFreeDDPM  # noqa: E402,F401  (classifier-free guidance: no classifier at all)
 
 
 def _labels(y, B: int, K: int, device) -> Tensor:
     """int64 device labels of shape (B,), refused (ValueError) when outside [0, K)"""
-    y = torch.as_tensor(y).reshape(-1).to(device=device, dtype=torch.int64).contiguous()
-    if y.numel() != B:
-        raise ValueError(f"expected {B} labels, got {y.numel()}")
-    lo, hi = int(y.min().item()), int(y.max().item())
-    if lo < 0 or hi >= K:
-        raise ValueError(f"class labels must lie in [0, {K}); got values in [{lo}, {hi}]")
-    return y
+    return class_labels(y, B, K, device, null=False)
 
 
 def _check_status(status: Tensor, what: str):

@@ -1,1 +1,2 @@
-from . import ddpm, iddpm  # noqa: F401
+from . import ddpm, iddpm, cond  # noqa: F401
+from .cond import ConditionalUNet  # noqa: F401

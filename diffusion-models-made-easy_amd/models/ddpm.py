@@ -398,11 +398,7 @@ class UNet(nn.Module):
 
             cb = _lib.BUCKET_FN(ready)
             try:
-                _lib.check(
-                    lib.dmme_unet_backward_buckets(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(d),
-                                                   _lib.ptr(plan.workspace), _lib.ptr(plan.bws), _lib.ptr(masks), _lib.ptr(g), _lib.ptr(dx), _lib.stream_ptr(), cb, None),
-                    "dmme_unet_backward_buckets",
-                )
+                self._launch_backward(plan, packed, xin, t, d, masks, g, dx, cb)
                 if errors:
                     raise errors[0]
             except Exception:
@@ -417,14 +413,42 @@ class UNet(nn.Module):
             if dx is not None and amp is not None:
                 dx.div_(amp[0])
             return dx
+        self._launch_backward(plan, packed, xin, t, d, masks, g, dx, None)
+        if dx is not None and amp is not None:
+            dx.div_(amp[0])
+        return dx
+
+    # the three launches a subclass with more inputs than (x, t) replaces (models/cond.py: the labels of ConditionalUNet)
+    def _launch_forward(self, plan: _Plan, packed: Tensor, xin: Tensor, t: Tensor, y: Tensor, masks: Optional[Tensor], want_ctx: bool):
+        # no backward pass will follow (sampling, evaluation): the form that skips tensors only the backward pass reads
+        fwd = plan.lib.dmme_unet_forward if want_ctx else plan.lib.dmme_unet_forward_nograd
+        _lib.check(
+            fwd(plan.h, _lib.ptr(packed), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(y), _lib.ptr(plan.workspace), _lib.ptr(masks), _lib.stream_ptr()),
+            "dmme_unet_forward",
+        )
+
+    def _launch_backward(self, plan: _Plan, packed: Tensor, xin: Tensor, t: Tensor, d: Tensor, masks: Optional[Tensor], g: Tensor, dx: Optional[Tensor], cb):
+        """cb: the bucket callback (a _lib.BUCKET_FN) of an overlapped exchange, or None"""
+        lib = plan.lib
+        if cb is not None:
+            _lib.check(
+                lib.dmme_unet_backward_buckets(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(d),
+                                               _lib.ptr(plan.workspace), _lib.ptr(plan.bws), _lib.ptr(masks), _lib.ptr(g), _lib.ptr(dx), _lib.stream_ptr(), cb, None),
+                "dmme_unet_backward_buckets",
+            )
+            return
         _lib.check(
             lib.dmme_unet_backward(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(d),
                                    _lib.ptr(plan.workspace), _lib.ptr(plan.bws), _lib.ptr(masks), _lib.ptr(g), _lib.ptr(dx), _lib.stream_ptr()),
             "dmme_unet_backward",
         )
-        if dx is not None and amp is not None:
-            dx.div_(amp[0])
-        return dx
+
+    def _launch_backward_input(self, plan: _Plan, packed: Tensor, xin: Tensor, t: Tensor, d: Tensor, masks: Optional[Tensor], dx: Tensor):
+        _lib.check(
+            plan.lib.dmme_unet_backward_input(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(d),
+                                              _lib.ptr(plan.workspace), _lib.ptr(plan.bws), _lib.ptr(masks), _lib.ptr(dx), _lib.stream_ptr()),
+            "dmme_unet_backward_input",
+        )
 
     def _bwd_buffers(self, plan: _Plan) -> Tensor:
         """backward workspace and data-gradient weights of `plan` (created / re-packed when needed); returns the packed weights"""
@@ -450,11 +474,7 @@ class UNet(nn.Module):
         packed = self._bwd_buffers(plan)
         d = dy.detach().to(torch.float32).contiguous()
         dx = torch.empty_like(xin)
-        _lib.check(
-            plan.lib.dmme_unet_backward_input(plan.h, _lib.ptr(packed), _lib.ptr(plan.packed_bwd), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(d),
-                                              _lib.ptr(plan.workspace), _lib.ptr(plan.bws), _lib.ptr(masks), _lib.ptr(dx), _lib.stream_ptr()),
-            "dmme_unet_backward_input",
-        )
+        self._launch_backward_input(plan, packed, xin, t, d, masks, dx)
         return dx
 
     def _out_shape(self, B: int, H: int, W: int) -> Tuple[int, ...]:
@@ -491,12 +511,7 @@ class UNet(nn.Module):
                 self._mask_calls += 1
                 seed, off = philox_reserve(x.device, plan.dropmask_numel)  # torch's CUDA generator: manual_seed restarts the draws
                 _lib.check(plan.lib.dmme_dropout_masks(plan.h, seed ^ 0x5DEECE66D, off, _lib.ptr(masks), _lib.stream_ptr()), "dmme_dropout_masks")
-        # no backward pass will follow (sampling, evaluation): the form that skips tensors only the backward pass reads
-        fwd = plan.lib.dmme_unet_forward if want_ctx else plan.lib.dmme_unet_forward_nograd
-        _lib.check(
-            fwd(plan.h, _lib.ptr(packed), _lib.ptr(xin), _lib.ptr(t), int(t.numel()), _lib.ptr(y), _lib.ptr(plan.workspace), _lib.ptr(masks), _lib.stream_ptr()),
-            "dmme_unet_forward",
-        )
+        self._launch_forward(plan, packed, xin, t, y, masks, want_ctx)
         self._last_plan = plan
         # every forward of this (B, H, W, dtype) overwrites the activations (plan.workspace) and the drawn masks a pending
         # backward would read: the generation stamp lets that backward refuse instead of producing wrong gradients

@@ -18,11 +18,12 @@ def synthetic_batch(batch_size: int, device, shape=(3, 32, 32)):
     return torch.rand((batch_size, *shape), device=device) * 2 - 1
 
 
-def train_step(module, optimizer, scheduler, x0, clip=None, reduce=True, exchange=None):
+def train_step(module, optimizer, scheduler, x0, clip=None, reduce=True, exchange=None, y=None):
     """one optimisation step: loss -> HIP backward (data parallel: the gradient exchange of the first bucket runs on a side
     stream under the rest of backward) -> clip+Adam(+EMA) -> LR step.  `reduce=False` leaves the gradient exchange out
     (bench.py times the step without its collective to tell exposed from hidden exchange time).  `exchange`: wire format of
-    the gradient mean (distributed.make_reducer: "fp32-allreduce" | "bf16-rs-ag"; default DMME_EXCHANGE or fp32)."""
+    the gradient mean (distributed.make_reducer: "fp32-allreduce" | "bf16-rs-ag"; default DMME_EXCHANGE or fp32).  `y`: the batch's class
+    labels, handed to a conditional module (lit_modules.LitClassifierFreeDDPM) next to the images."""
     model = module.diffusion_model.model
     reducer = getattr(model, "_grad_reducer", None)
     multi = reduce and D.dist.is_available() and D.dist.is_initialized() and D.dist.get_world_size() > 1
@@ -41,7 +42,7 @@ def train_step(module, optimizer, scheduler, x0, clip=None, reduce=True, exchang
         # no exchange in this step: the hook must be gone BEFORE backward runs, or that backward would issue all-reduces (and divide
         # the gradients) on the side stream with nobody waiting for them
         reducer.detach()
-    loss = module.training_step((x0,), 0)
+    loss = module.training_step((x0,) if y is None else (x0, y), 0)
     loss.backward()
     if multi:
         if reducer is not None and getattr(model, "_bucket_hook", None) is not None and reducer.finish():
@@ -77,20 +78,29 @@ def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=N
         model._dp_synced = True
     t0 = time.perf_counter()
     batches = None
+    conditional = bool(getattr(module, "conditional", False))  # the module's training_step takes (images, labels)
     for step in range(first, max_steps):
+        y = None
         if loader is None:
             x0 = synthetic_batch(batch_size, dev)
+            if conditional:
+                y = torch.randint(0, model.num_classes, (batch_size,), device=dev)
         else:  # epochs over the HBM-resident set: a fresh permutation each time the loader is exhausted
             try:
-                x0 = next(batches)[0]
+                batch = next(batches)
             except (StopIteration, TypeError):
                 batches = iter(loader)
-                x0 = next(batches)[0]
-        loss = train_step(module, opt, sched, x0, clip)
+                batch = next(batches)
+            x0 = batch[0]
+            if conditional:
+                y = batch[1]
+        loss = train_step(module, opt, sched, x0, clip, y=y)
         if (step + 1) % log_every == 0 or step + 1 == max_steps:
             torch.cuda.synchronize()
             if hasattr(model, "check_engine"):
                 model.check_engine()  # a level-engine hand-off that timed out since the last log line: stop, do not train on it
+            if conditional:
+                model.check_labels()  # a label outside [0, num_classes] that reached the device since the last log line
             dt = time.perf_counter() - t0
             print(json.dumps({"step": step + 1, "train/loss": round(float(loss.detach()), 5), "images_per_s": round((step + 1 - first) * batch_size / dt, 1)}), flush=True)
     if save_path and D.env_rank_world()[0] == 0:

@@ -18,6 +18,7 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml [--max-steps N] [--batch-size B]
   python -m dmme_amd.trainer sample --config configs/ddim/cifar10.yaml [--num-images N] [--steps K] [--sampler ddim-paper --eta E]
   python -m dmme_amd.trainer sample --config configs/iddpm/cifar10.yaml --sample-steps K    (Improved DDPM: K << T strided steps)
+  python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3,5 --guidance-scale 2.5   (classifier-free guidance)
 """
 
 from __future__ import annotations
@@ -214,6 +215,8 @@ def main(argv=None):
     ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table")
     ap.add_argument("--eta", type=float, default=0.0, help="sample --sampler ddim-paper: 0 deterministic ... 1 DDPM's posterior variance")
+    ap.add_argument("--labels", default=None, help="sample, class-conditional configs: comma-separated class labels, one per image or one for all (e.g. 3,5,7)")
+    ap.add_argument("--guidance-scale", type=float, default=None, help="sample, class-conditional configs: s of e_u + s (e_c - e_u); 1 = conditional, 0 = unconditional")
     ap.add_argument("--sample-steps", type=int, default=None,
                     help="sample, Improved DDPM configs: a strided chain over this many of the T timesteps, with the learned variance")
     args = ap.parse_args(argv)
@@ -263,7 +266,18 @@ def main(argv=None):
         t0 = time.perf_counter()
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)
-        if args.sample_steps is not None:
+        if getattr(module, "conditional", False):
+            if args.steps is not None or args.sample_steps is not None or args.sampler != "config":
+                raise SystemExit("class-conditional configs sample whole chains: --labels / --guidance-scale only")
+            if args.guidance_scale is not None:
+                dm.set_guidance_scale(args.guidance_scale)  # (the process stays what the YAML built: schedule, sampler, p_uncond)
+            labels = [int(v) for v in args.labels.split(",")] if args.labels else [dm.model.null_label]
+            if len(labels) == 1:
+                labels = labels * args.num_images
+            imgs = module.generate(shape, labels)
+        elif args.labels is not None or args.guidance_scale is not None:
+            raise SystemExit("--labels / --guidance-scale need a class-conditional config (LitClassifierFreeDDPM)")
+        elif args.sample_steps is not None:
             imgs = module.generate(shape, sample_steps=args.sample_steps)
         elif args.steps is None:
             imgs = module.generate(shape)

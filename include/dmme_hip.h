@@ -66,12 +66,20 @@ typedef enum {
     DMME_ARCH_DDPM = 0,  /* dmme.models.ddpm.UNet (src/dmme/models/ddpm.py:176-316): eps only */
     DMME_ARCH_IDDPM = 1, /* dmme.models.iddpm.UNet (src/dmme/models/iddpm.py:125-265): scale-shift ResBlocks,
                             multi-head attention, 2*in_channels outputs (eps, v) */
-    DMME_ARCH_CLASSIFIER = 2 /* the noise-aware classifier of classifier guidance (Dhariwal & Nichol 2021, the ADM "half UNet";
+    DMME_ARCH_CLASSIFIER = 2, /* the noise-aware classifier of classifier guidance (Dhariwal & Nichol 2021, the ADM "half UNet";
                             the reference's src/dmme/guidance/classifier.py sketch): the DDPM UNet's time MLP, input_conv,
                             down_layers and middle_layers (same keys and layouts), then the head `out` = GroupNorm -> SiLU ->
                             mean over H x W -> Linear(C_top, num_classes).  No up path, no output conv.  The output y is the
                             fp32 logits (B, num_classes).  fp32 / bf16 / fp16 only (bf16x3 / fp16r32: DMME_ERR_UNSUPPORTED);
                             per-op launches (no level engine); no gradient buckets. */
+    DMME_ARCH_DDPM_COND = 3 /* the DDPM UNet with a class label (classifier-free guidance, Ho & Salimans 2021; conditioning in the ADM form,
+                            Dhariwal & Nichol 2021): DMME_ARCH_DDPM's parameter table, unchanged, plus ONE entry behind it,
+                            `label_emb.weight` (num_classes + 1, emb_dim), fp32 in the packed buffer; row num_classes is the null label.  The
+                            label row enters the pre-activation of the second time Linear: c_b = SiLU(W2 h1_r + b2 + E[y_b]), r = b for
+                            t_len == B and 0 for t_len == 1; from the per-block projection on the forward runs with B time rows whatever
+                            t_len was.  Routes, level engine, residual segments and gradient buckets are DMME_ARCH_DDPM's (the table's
+                            gradient rides in the last bucket).  fp32 / bf16 / fp16 only (bf16x3 / fp16r32: DMME_ERR_UNSUPPORTED).  Runs
+                            through the dmme_*_cond entry points only: the label-less ones return DMME_ERR_INVALID on such a plan. */
 } dmme_unet_arch;
 
 /* Constructor arguments of the reference UNet (src/dmme/models/ddpm.py:190-200, models/iddpm.py:139-149). */
@@ -89,7 +97,8 @@ typedef struct {
     int arch;      /* dmme_unet_arch */
     int num_heads; /* DMME_ARCH_IDDPM: heads of MultiHeadAttention (the reference hard-codes 4, models/iddpm.py:82);
                       ignored (1) for DMME_ARCH_DDPM */
-    int num_classes; /* DMME_ARCH_CLASSIFIER: classes of the head (>= 1); ignored otherwise */
+    int num_classes; /* DMME_ARCH_CLASSIFIER: classes of the head (>= 1); DMME_ARCH_DDPM_COND: classes K of the label table (>= 1);
+                        ignored otherwise */
 } dmme_unet_cfg;
 
 typedef struct dmme_plan dmme_plan;
@@ -148,6 +157,19 @@ DMME_API int dmme_unet_forward(const dmme_plan* plan, const void* packed, const 
  * dmme_chain_step and dmme_unet_forward_profiled run this form. */
 DMME_API int dmme_unet_forward_nograd(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len,
                       float* y, void* workspace, const float* drop_masks, void* stream);
+
+/* ---- class-conditional forward / backward (DMME_ARCH_DDPM_COND plans) -----------------------------------------------
+ * labels: int64[B] on the device, values in [0, K]; K = cfg.num_classes is the null label.  The argument check cannot see device labels:
+ * a label outside [0, K] is clamped before it indexes the table, that image's time-embedding row (and with it its output) becomes NaN
+ * and *status (nullable, device int) is set to 1, as by dmme_log_softmax_grad.
+ * dmme_unet_forward_cond: dmme_unet_forward (keep_ctx != 0: a backward may follow) or dmme_unet_forward_nograd (keep_ctx == 0).
+ * dmme_unet_backward_cond: dmme_unet_backward_buckets with the labels of the matching forward; `ready` may be NULL (no hand-overs:
+ *   dmme_unet_backward).  Adds dE[k] += sum_{b: y_b = k} d z2[b] into grad_flat at the table's ref_offset, summed in ascending b by one
+ *   workgroup per row (no atomics: equal inputs give equal bits; a row no image carries is not touched).  Parameter gradients need one
+ *   time row per image: t_len == 1 with B > 1 is DMME_ERR_INVALID.
+ * dmme_unet_backward_input_cond: dmme_unet_backward_input on a conditional plan (the labels only say which forward it follows). */
+DMME_API int dmme_unet_forward_cond(const dmme_plan* plan, const void* packed, const float* x, const int64_t* t, int t_len, const int64_t* labels,
+                                    float* y, void* workspace, const float* drop_masks, int keep_ctx, int* status, void* stream);
 
 /* ---- per-op accounting + event-bracketed profiling (bench.py's roofline leg) --------
  * op_info: kernel label (the kernel symbol the op launches, e.g.
@@ -213,6 +235,12 @@ DMME_API int dmme_unet_backward_input(const dmme_plan* plan, const void* packed,
                                       int t_len, const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks, float* d_x,
                                       void* stream);
 DMME_API int dmme_unet_plan_grad_buckets(const dmme_plan* plan, int64_t* offsets, int64_t* numels, int* bucket_of, int cap);
+DMME_API int dmme_unet_backward_cond(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t, int t_len,
+                                     const int64_t* labels, const float* d_y, void* workspace, void* bwd_workspace, const float* drop_masks,
+                                     float* grad_flat, float* d_x, void* stream, dmme_bucket_fn ready, void* user);
+DMME_API int dmme_unet_backward_input_cond(const dmme_plan* plan, const void* packed, const void* packed_bwd, const float* x, const int64_t* t,
+                                           int t_len, const int64_t* labels, const float* d_y, void* workspace, void* bwd_workspace,
+                                           const float* drop_masks, float* d_x, void* stream);
 /* test / diagnostic: the kernels a backward of this plan launches, as space-separated key=value pairs
  * ("wgrad_group3x3_jobs=..", "colsum_group_jobs=..", "dgrad[conv3x3_ws2_kernel<11>]=..") */
 DMME_API int dmme_unet_plan_bwd_summary(const dmme_plan* plan, char* buf, int cap);
@@ -390,7 +418,8 @@ DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64
  * dmme_chain_update; x is updated in place, model_out receives the network output.  chw must be a multiple of 4.
  * DMME_CHAIN_GDDIM draws its normals only at loop indices whose k2 != 0; the offset advances at every step all the same.
  * dmme_chain_update_gddim = dmme_chain_update(DMME_CHAIN_GDDIM, ...) with `noise` (nullable) used in place of the drawn normals (tests). */
-enum { DMME_CHAIN_DDPM = 0, DMME_CHAIN_DDIM = 1, DMME_CHAIN_IDDPM = 2, DMME_CHAIN_DDPM_GUIDED = 3, DMME_CHAIN_DDIM_GUIDED = 4, DMME_CHAIN_GDDIM = 5 };
+enum { DMME_CHAIN_DDPM = 0, DMME_CHAIN_DDIM = 1, DMME_CHAIN_IDDPM = 2, DMME_CHAIN_DDPM_GUIDED = 3, DMME_CHAIN_DDIM_GUIDED = 4, DMME_CHAIN_GDDIM = 5,
+       DMME_CHAIN_DDPM_CFG = 6, DMME_CHAIN_GDDIM_CFG = 7 /* classifier-free guidance, below */ };
 DMME_API int dmme_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t philox_seed, uint64_t philox_offset, void* stream);
 DMME_API int dmme_chain_update(int kind, float* x, const float* model_out, const float* step_coef, const int64_t* t_table, void* state,
                       int B, int64_t chw, void* stream);
@@ -424,6 +453,32 @@ DMME_API int dmme_guided_chain_step(const dmme_plan* plan, const void* packed, c
                                     const void* cls_packed_bwd, float* x, float* model_out, void* workspace, void* cls_workspace,
                                     void* cls_bwd_workspace, const int64_t* y, float* logits, float* d_logits, float* grad, int* status,
                                     int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
+/* ---- classifier-free guidance (Ho & Salimans 2021) ------------------------------------------------------------------
+ * One network, evaluated with the label and with the null label, replaces the classifier.  Both evaluations ride in ONE forward at batch
+ * 2B: x and model_out hold 2B images, the conditional half [0, B) then the unconditional half [B, 2B); labels_2B = (y, K ... K).
+ * DMME_CHAIN_DDPM_CFG / DMME_CHAIN_GDDIM_CFG: for element j of image b < B
+ *     e^ = e_u + s (e_c - e_u)        three separately rounded fp32 operations (no fma), s = step_coef[i][3]
+ *     x' = the DMME_CHAIN_DDPM / DMME_CHAIN_GDDIM update of x[b] with e^ (step_coef[i][0..2] as for the base kind)
+ * and x' is stored into both halves of x (which therefore stay equal; x is read from the first).  s = 1 is plain conditional sampling,
+ * s = 0 unconditional; Ho & Salimans' w is s - 1.  Column 3 is free in both base kinds, so a table may carry a per-step schedule of s.
+ * Noise is indexed by the element of the FIRST half and the offset advances by B*chw/4 per step: a guided chain at batch B consumes
+ * exactly the normals of an unguided chain at batch B under the same seed.  B and chw below are those of ONE half.
+ * dmme_cfg_step: the eager twin (host scalars; z: B*chw normals, read where the step adds noise - DDPM: add_noise, GDDIM: c2 != 0).
+ * dmme_chain_update_cfg: the chain form (device state); noise (nullable) replaces the drawn normals (tests).
+ * dmme_cfg_chain_step: one capturable step: dmme_unet_forward_cond (no-grad form) of a DMME_ARCH_DDPM_COND plan of batch 2B at
+ *   t = state.t with labels_2B, then dmme_chain_update_cfg at B = plan batch / 2.  status: as dmme_unet_forward_cond (nullable).
+ * dmme_label_dropout: the label side of classifier-free training: out[b] = K where u_b < p (and everywhere when p >= 1), else labels[b];
+ *   u_b is uniform b of the span (seed, offset, B) of the device random stream above (word b % 4 of quad b / 4, u = ((x >> 8) + 1) / 2^24),
+ *   tests/philox_ref.py: uniforms(seed, offset, B).  A label outside [0, K] is copied through and sets *status (nullable, device int).
+ *   out must not alias labels. */
+DMME_API int dmme_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, void* stream);
+DMME_API int dmme_cfg_step(int kind, float* x, const float* model_out, const float* z, float c0, float c1, float c2, float s, int add_noise, int B,
+                           int64_t chw, void* stream);
+DMME_API int dmme_chain_update_cfg(int kind, float* x, const float* model_out, const float* noise, const float* step_coef, const int64_t* t_table,
+                                   void* state, int B, int64_t chw, void* stream);
+DMME_API int dmme_cfg_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
+                                 int* status, int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
