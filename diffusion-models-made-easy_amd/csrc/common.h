@@ -444,6 +444,11 @@ int launch_cfg_step(int kind, float* x, const float* out, const float* z, float 
                     hipStream_t s);
 int launch_chain_update_cfg(int kind, float* x, const float* out, const float* noise, const float* coef, const int64_t* t_table, void* state, int B,
                             int64_t chw, hipStream_t s);
+// DPM-Solver++(2M): `row` 8 host floats, coef [n+1][8]; cfg: x / out hold 2B images (planes 1), hist B; planes: chw-planes per image of `out`
+int launch_dpmpp_step(bool cfg, float* x, const float* out, float* hist, const float* row, int history_valid, int B, int64_t chw, int planes,
+                      hipStream_t s);
+int launch_chain_update_dpmpp(bool cfg, float* x, const float* out, float* hist, const float* coef, const int64_t* t_table, void* state, int B,
+                              int64_t chw, int planes, hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient

@@ -608,7 +608,8 @@ struct ChainState {
     unsigned long long offset;
     unsigned long long seed;
     unsigned int ticket, pad;
-    unsigned long long reserved[3];
+    unsigned long long history_valid;  // DPM-Solver++ kinds: the history buffer holds the x0 prediction of this chain's previous step
+    unsigned long long reserved[2];
 };
 static_assert(sizeof(ChainState) == 64, "ChainState is eight 64-bit words (dmme_hip.h: dmme_chain_*)");
 
@@ -619,6 +620,7 @@ __global__ void chain_set_kernel(ChainState* st, long long i, const long long* _
     st->seed = seed;
     st->ticket = 0u;
     st->pad = 0u;
+    st->history_valid = 0ull;  // a chain's first step is first order wherever it starts (no other kind reads the word)
 }
 
 // KIND: a DMME_CHAIN_* constant; coef[i][0..3] are c0..c3 of sampler_update<KIND> at loop index i.  The kinds with a DDPM mean add noise
@@ -804,6 +806,113 @@ int launch_chain_update_cfg(int kind, float* x, const float* out, const float* n
         hipLaunchKernelGGL(cfg_chain_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, coef, (const long long*)t_table, (ChainState*)state, n4, noise);
     else
         hipLaunchKernelGGL(cfg_chain_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, coef, (const long long*)t_table, (ChainState*)state, n4, noise);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// ------------------------------------------------------------------ DPM-Solver++(2M) (Lu et al. 2022), data-prediction form
+// The first kind whose update carries state of its own from one replay to the next: the previous step's x0 prediction, in a buffer of
+// x's layout that the thread owning a quad reads (only where the history is valid) and overwrites.  Per loop index, 8 floats:
+//   {q0 = 1/alpha_a, q1 = -sigma_a/alpha_a, k0 = sigma_p/sigma_a, k1 = -alpha_p expm1(-h), w = h / (2 h_prev), clip, s, -}
+//   x0 = q0 x + q1 e (clamped to [-1, 1] iff clip);  D = valid ? x0 + w (x0 - x0_prev) : x0;  x' = k0 x + k1 D;  history <- x0
+// every product and sum rounded on its own, like everything in this file.  CFG: e = e_u + s (e_c - e_u) over a 2B batch exactly as
+// cfg_update forms it, the result into both halves of x, a history of B images.
+constexpr int DPMPP_ROW = 8;
+struct DpmppRow {
+    float q0, q1, k0, k1, w, clip, s;
+};
+__device__ __forceinline__ float dpmpp_update(float x, float e, float prev, const DpmppRow& r, bool valid, float& x0) {
+    x0 = __fadd_rn(__fmul_rn(r.q0, x), __fmul_rn(r.q1, e));
+    if (r.clip != 0.0f) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float d = valid ? __fadd_rn(x0, __fmul_rn(r.w, __fsub_rn(x0, prev))) : x0;
+    return __fadd_rn(__fmul_rn(r.k0, x), __fmul_rn(r.k1, d));
+}
+// the quad at element b of x (CFG: of its first half; `half` = elements of one half).  planes: chw-sized planes per image of the network
+// output, the predicted noise in the first (2: an IDDPM network's (eps, v)); chw % 4 == 0 keeps every access 16-byte aligned and inside
+// one image.  The history is not loaded at all while it is not valid: it may hold anything, NaN included.
+template <bool CFG>
+__device__ __forceinline__ void dpmpp_quad(float* __restrict__ x, const float* __restrict__ out, float* __restrict__ hist, int64_t b, int64_t half,
+                                           int64_t chw, int planes, const DpmppRow& r, bool valid) {
+    const int64_t eo = planes == 2 ? b + (b / chw) * chw : b;
+    float4 xv = load4(x + b), ev = load4(out + eo), hv = make_float4(0.f, 0.f, 0.f, 0.f);
+    float* es = reinterpret_cast<float*>(&ev);
+    if (CFG) {
+        const float4 uv = load4(out + half + b);
+        const float* us = reinterpret_cast<const float*>(&uv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(r.s, __fsub_rn(es[j], us[j])));
+    }
+    if (valid) hv = load4(hist + b);
+    float *xs = reinterpret_cast<float*>(&xv), *hs = reinterpret_cast<float*>(&hv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xs[j] = dpmpp_update(xs[j], es[j], hs[j], r, valid, hs[j]);
+    *reinterpret_cast<float4*>(x + b) = xv;
+    if (CFG) *reinterpret_cast<float4*>(x + half + b) = xv;
+    *reinterpret_cast<float4*>(hist + b) = hv;
+}
+template <bool CFG>
+__global__ void __launch_bounds__(256) dpmpp_eager_kernel(float* __restrict__ x, const float* __restrict__ out, float* __restrict__ hist, DpmppRow r,
+                                                          int valid, int64_t chw, int planes, int64_t n4) {
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x)
+        dpmpp_quad<CFG>(x, out, hist, q * 4, n4 * 4, chw, planes, r, valid != 0);
+}
+// the chain form: the row at coef[8 i], `valid` from the loop state.  The block with the last ticket moves the state on and raises
+// history_valid; the Philox offset stays (the solver draws nothing).
+template <bool CFG>
+__global__ void __launch_bounds__(256) dpmpp_chain_kernel(float* __restrict__ x, const float* __restrict__ out, float* __restrict__ hist,
+                                                          const float* __restrict__ coef, const long long* __restrict__ t_table, ChainState* st, int64_t chw,
+                                                          int planes, int64_t n4) {
+    const long long i = st->i;
+    const bool valid = st->history_valid != 0ull;
+    const float* c = coef + DPMPP_ROW * i;
+    const DpmppRow r = {c[0], c[1], c[2], c[3], c[4], c[5], c[6]};
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x)
+        dpmpp_quad<CFG>(x, out, hist, q * 4, n4 * 4, chw, planes, r, valid);
+    __syncthreads();  // every thread of this block has read the state
+    if (threadIdx.x == 0) {
+        const unsigned tk = atomicAdd(&st->ticket, 1u);
+        if (tk == gridDim.x - 1) {  // last block: all others took their ticket after reading the state
+            const long long ni = i > 0 ? i - 1 : 0;
+            st->i = ni;
+            st->t = t_table[ni];
+            st->history_valid = 1ull;
+            atomicExch(&st->ticket, 0u);
+        }
+    }
+}
+static int dpmpp_check(const char* what, const void* x, const void* out, const void* hist, int B, int64_t chw, int planes) {
+    DMME_REQUIRE(x && out && hist && B > 0 && chw > 0, DMME_ERR_INVALID, "%s: bad argument", what);
+    DMME_REQUIRE(planes == 1 || planes == 2, DMME_ERR_INVALID, "%s: a network output of %d planes per image (1: eps, 2: eps and v)", what, planes);
+    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "%s: image size %lld is not a multiple of 4", what, (long long)chw);
+    return DMME_OK;
+}
+// row: the 8 floats of one table row, on the host.  cfg: x / out hold 2B images, history B.
+int launch_dpmpp_step(bool cfg, float* x, const float* out, float* hist, const float* row, int history_valid, int B, int64_t chw, int planes,
+                      hipStream_t s) {
+    const char* what = cfg ? "cfg_dpmpp_step" : "dpmpp_step";
+    if (int rc = dpmpp_check(what, x, out, hist, B, chw, planes)) return rc;
+    DMME_REQUIRE(row, DMME_ERR_INVALID, "%s: null argument", what);
+    const DpmppRow r = {row[0], row[1], row[2], row[3], row[4], row[5], row[6]};
+    const int64_t n4 = (int64_t)B * chw / 4;
+    const dim3 g(grid_for(n4)), b(256);
+    if (cfg)
+        hipLaunchKernelGGL(dpmpp_eager_kernel<true>, g, b, 0, s, x, out, hist, r, history_valid, chw, 1, n4);
+    else
+        hipLaunchKernelGGL(dpmpp_eager_kernel<false>, g, b, 0, s, x, out, hist, r, history_valid, chw, planes, n4);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+int launch_chain_update_dpmpp(bool cfg, float* x, const float* out, float* hist, const float* coef, const int64_t* t_table, void* state, int B,
+                              int64_t chw, int planes, hipStream_t s) {
+    const char* what = cfg ? "chain_update_cfg_dpmpp" : "chain_update_dpmpp";
+    if (int rc = dpmpp_check(what, x, out, hist, B, chw, planes)) return rc;
+    DMME_REQUIRE(coef && t_table && state, DMME_ERR_INVALID, "%s: null argument", what);
+    const int64_t n4 = (int64_t)B * chw / 4;
+    const dim3 g(grid_for(n4)), b(256);
+    if (cfg)
+        hipLaunchKernelGGL(dpmpp_chain_kernel<true>, g, b, 0, s, x, out, hist, coef, (const long long*)t_table, (ChainState*)state, chw, 1, n4);
+    else
+        hipLaunchKernelGGL(dpmpp_chain_kernel<false>, g, b, 0, s, x, out, hist, coef, (const long long*)t_table, (ChainState*)state, chw, planes, n4);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }

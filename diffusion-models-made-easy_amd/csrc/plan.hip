@@ -1284,7 +1284,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 110; }  // 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 111; }  // 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1628,6 +1628,55 @@ DMME_API int dmme_cfg_chain_step(const dmme_plan* plan_2B, const void* packed, f
     if (rc != DMME_OK) return rc;
     return launch_chain_update_cfg(kind, x_2B, model_out, nullptr, step_coef, t_table, state, plan_2B->B / 2,
                                    (int64_t)plan_2B->cfg.in_channels * plan_2B->H * plan_2B->W, (hipStream_t)stream);
+}
+
+// ---- DPM-Solver++(2M): kinds DMME_CHAIN_DPMPP / DMME_CHAIN_DPMPP_CFG, tables of 8 floats per index, a history buffer (kernels_sampler.hip)
+DMME_API int dmme_dpmpp_step(float* x, const float* model_out, float* history, const float* row, int history_valid, int B, int64_t chw, int out_planes,
+                             void* stream) {
+    return launch_dpmpp_step(false, x, model_out, history, row, history_valid, B, chw, out_planes, (hipStream_t)stream);
+}
+
+DMME_API int dmme_chain_update_dpmpp(float* x, const float* model_out, float* history, const float* step_coef, const int64_t* t_table, void* state, int B,
+                                     int64_t chw, int out_planes, void* stream) {
+    return launch_chain_update_dpmpp(false, x, model_out, history, step_coef, t_table, state, B, chw, out_planes, (hipStream_t)stream);
+}
+
+DMME_API int dmme_dpmpp_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, float* history,
+                                   const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && history && step_coef && t_table && state, DMME_ERR_INVALID, "dpmpp_chain_step: null argument");
+    DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "dpmpp_chain_step: a class-conditional plan takes labels: call dmme_cfg_dpmpp_chain_step");
+    DMME_REQUIRE(plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID, "dpmpp_chain_step: architecture %d predicts no noise", plan->cfg.arch);
+    const int planes = plan->out_channels / plan->cfg.in_channels;
+    DMME_REQUIRE(plan->out_channels == planes * plan->cfg.in_channels && (planes == 1 || planes == 2), DMME_ERR_INVALID,
+                 "dpmpp_chain_step: a network with %d output channels for %d input channels", plan->out_channels, plan->cfg.in_channels);
+    if (int rc0 = lvl_check(plan, "dpmpp_chain_step", (hipStream_t)stream, true)) return rc0;
+    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
+    const int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false);
+    if (rc != DMME_OK) return rc;
+    return launch_chain_update_dpmpp(false, x, model_out, history, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
+                                     planes, (hipStream_t)stream);
+}
+
+DMME_API int dmme_cfg_dpmpp_step(float* x_2B, const float* model_out, float* history, const float* row, int history_valid, int B, int64_t chw, void* stream) {
+    return launch_dpmpp_step(true, x_2B, model_out, history, row, history_valid, B, chw, 1, (hipStream_t)stream);
+}
+
+DMME_API int dmme_chain_update_cfg_dpmpp(float* x_2B, const float* model_out, float* history, const float* step_coef, const int64_t* t_table, void* state,
+                                         int B, int64_t chw, void* stream) {
+    return launch_chain_update_dpmpp(true, x_2B, model_out, history, step_coef, t_table, state, B, chw, 1, (hipStream_t)stream);
+}
+
+DMME_API int dmme_cfg_dpmpp_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
+                                       int* status, float* history, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan_2B && packed && x_2B && labels_2B && model_out && workspace && history && step_coef && t_table && state, DMME_ERR_INVALID,
+                 "cfg_dpmpp_chain_step: null argument");
+    DMME_REQUIRE(plan_2B->cond && plan_2B->B % 2 == 0, DMME_ERR_INVALID,
+                 "cfg_dpmpp_chain_step: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", plan_2B->B);
+    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
+    const int rc = unet_forward_impl(plan_2B, packed, x_2B, t_dev, 1, model_out, workspace, nullptr, stream, false, labels_2B, status);
+    if (rc != DMME_OK) return rc;
+    return launch_chain_update_dpmpp(true, x_2B, model_out, history, step_coef, t_table, state, plan_2B->B / 2,
+                                     (int64_t)plan_2B->cfg.in_channels * plan_2B->H * plan_2B->W, 1, (hipStream_t)stream);
 }
 
 // The two launches of dmme_slerp hand three partial sums per (image, block) from one to the other.  The entry point takes no scratch

@@ -78,6 +78,10 @@ class ChainRunner(ChainTables):
         )
         self.plan.overwritten()
 
+    def _carried(self):
+        """the buffers a step changes and the next step reads: what the trial step and the capture must leave as they found it"""
+        return [self.x, self.state]
+
     def _weights_key(self):
         """identifies the packed weights the captured graph reads"""
         return (self.plan.packed_version, self.plan.packed.data_ptr())
@@ -95,12 +99,17 @@ class ChainRunner(ChainTables):
             # capture: one eager step first (kernel attribute setup happens at first launch), on a saved copy of x / the state.
             # A kernel or DMME error in that trial step is a real error and propagates; only a failure of the CAPTURE itself makes
             # this runner (not the model) fall back to eager launches, and the cause is kept in `capture_error`.
-            saved_x, saved_state = self.x.clone(), self.state.clone()
+            carried = self._carried()
+            saved = [b.clone() for b in carried]
+
+            def restore():
+                for b, v in zip(carried, saved):
+                    b.copy_(v)
+
             self._launch(packed)
             torch.cuda.synchronize()
             self.plan.check()  # (outside the capture: a level-engine timeout in the trial step is a real error, raised here)
-            self.x.copy_(saved_x)
-            self.state.copy_(saved_state)
+            restore()
             try:
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
@@ -108,12 +117,10 @@ class ChainRunner(ChainTables):
             except RuntimeError as exc:  # stream capture unavailable / invalidated: stay eager (same launches)
                 self.capture_error = exc
                 self.graph = None
-                self.x.copy_(saved_x)
-                self.state.copy_(saved_state)
+                restore()
                 self._launch(packed)
                 return self.x
-            self.x.copy_(saved_x)
-            self.state.copy_(saved_state)
+            restore()
             self.graph, self._wkey = graph, wkey
         # (no synchronisation while the engine's status word is clear: an atomic load of pinned host memory; a hand-off timeout of an
         # earlier replayed step raises here, one step late at most, for callers that never reach `run`'s final check)
@@ -232,8 +239,8 @@ class DDPM(nn.Module):
         if runner is None:
             return None
         runner.x.copy_(x_t)
-        # (the paper-form DDIM kind at eta = 0 reserves nothing, like its eager step; every other kind keeps reserving one span per call)
-        seed, off = (0, 0) if runner.kind == _lib.CHAIN_GDDIM and not runner.draws else philox_reserve(x_t.device, x_t.numel())
+        # (the paper-form DDIM kind at eta = 0 and the DPM-Solver++ kind reserve nothing, like their eager steps; every other kind keeps reserving one span per call)
+        seed, off = (0, 0) if runner.kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_DPMPP) and not runner.draws else philox_reserve(x_t.device, x_t.numel())
         runner.set(index, seed, off)
         with torch.no_grad():
             runner.step()

@@ -33,10 +33,10 @@ from ..models.cond import class_labels
 from ..models.ddpm import UNet
 
 __all__ = ["EncoderClassifier", "ClassifierGuidedDDPM", "ClassifierGuidedDDIM", "GuidedChainRunner", "classifier_loss", "cross_entropy_apply",
-           "ClassifierFreeDDPM", "ClassifierFreeDDIM", "CFGChainRunner"]
+           "ClassifierFreeDDPM", "ClassifierFreeDDIM", "ClassifierFreeDPMSolver", "CFGChainRunner"]
 
 
-from .cfg import CFGChainRunner, ClassifierFreeDDIM, ClassifierFreeDDPM  # noqa: E402,F401  (classifier-free guidance: no classifier at all)
+from .cfg import CFGChainRunner, ClassifierFreeDDIM, ClassifierFreeDDPM, ClassifierFreeDPMSolver  # noqa: E402,F401  (classifier-free guidance: no classifier at all)
 
 
 def _labels(y, B: int, K: int, device) -> Tensor:

@@ -22,19 +22,21 @@ from torch import Tensor, nn
 from .. import _lib
 from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..diffusion_models.ddim import GeneralizedDDIM
+from ..diffusion_models.dpm_solver import DPMSolverPP, _row_arg
 from ..diffusion_models.ddpm import DDPM, ChainRunner, _scalar_index
 from ..models.cond import ConditionalUNet, class_labels
 
-__all__ = ["ClassifierFreeDDPM", "ClassifierFreeDDIM", "CFGChainRunner"]
+__all__ = ["ClassifierFreeDDPM", "ClassifierFreeDDIM", "ClassifierFreeDPMSolver", "CFGChainRunner"]
 
-_BASE_KIND = {_lib.CHAIN_DDPM_CFG: _lib.CHAIN_DDPM, _lib.CHAIN_GDDIM_CFG: _lib.CHAIN_GDDIM}
+_BASE_KIND = {_lib.CHAIN_DDPM_CFG: _lib.CHAIN_DDPM, _lib.CHAIN_GDDIM_CFG: _lib.CHAIN_GDDIM, _lib.CHAIN_DPMPP_CFG: _lib.CHAIN_DPMPP}
 
 
 class CFGChainRunner(ChainRunner):
     """ChainRunner over a `ConditionalUNet` with the labels in a static device buffer (`y`).
 
     guidance_scale != 1: plan, image buffer `x` and `y` are of batch 2B (conditional half, unconditional half) and the captured step
-    is dmme_cfg_chain_step.  guidance_scale == 1: batch B, the conditional forward followed by the base kind's update."""
+    is dmme_cfg_chain_step.  guidance_scale == 1: batch B, the conditional forward followed by the base kind's update.
+    The DPM-Solver++ kinds run their own entry points and carry `hist`, the previous x0 prediction of the B images."""
 
     def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         model = process.model
@@ -49,15 +51,26 @@ class CFGChainRunner(ChainRunner):
         elif x.shape[0] % 2:
             raise ValueError("CFGChainRunner: the image buffer holds 2B images")
         super().__init__(process, x, use_graph, (kind, tables))
-        self.draws = _BASE_KIND.get(kind, kind) == _lib.CHAIN_DDPM or any(r[2] != 0.0 for r in tables[1])
+        self.dpmpp = _BASE_KIND.get(kind, kind) == _lib.CHAIN_DPMPP
+        self.draws = not self.dpmpp and (_BASE_KIND.get(kind, kind) == _lib.CHAIN_DDPM or any(r[2] != 0.0 for r in tables[1]))
         self.images = x.shape[0] // 2 if self.batched else x.shape[0]
+        self.hist = torch.empty_like(x[:self.images]) if self.dpmpp else None
         self.noise_numel = self.images * x[0].numel()  # the normals of ONE half: what an unguided chain at batch B draws
         self.y = torch.full((x.shape[0],), model.null_label, dtype=torch.int64, device=x.device)
         self.status = model.label_status(x.device)
 
+    def _carried(self):
+        return super()._carried() + ([self.hist] if self.dpmpp else [])
+
     def _launch(self, packed):
         lib, plan = _lib.lib(), self.plan
-        if self.batched:
+        if self.batched and self.dpmpp:
+            _lib.check(
+                lib.dmme_cfg_dpmpp_chain_step(plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.y), _lib.ptr(self.out), _lib.ptr(plan.workspace),
+                                              _lib.ptr(self.status), _lib.ptr(self.hist), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
+                "dmme_cfg_dpmpp_chain_step",
+            )
+        elif self.batched:
             _lib.check(
                 lib.dmme_cfg_chain_step(plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.y), _lib.ptr(self.out), _lib.ptr(plan.workspace),
                                         _lib.ptr(self.status), self.kind, _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
@@ -70,11 +83,18 @@ class CFGChainRunner(ChainRunner):
                                            _lib.ptr(plan.workspace), None, 0, _lib.ptr(self.status), _lib.stream_ptr()),
                 "dmme_unet_forward_cond",
             )
-            _lib.check(
-                lib.dmme_chain_update(self.kind, _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
-                                      self.images, self.x[0].numel(), _lib.stream_ptr()),
-                "dmme_chain_update",
-            )
+            if self.dpmpp:
+                _lib.check(
+                    lib.dmme_chain_update_dpmpp(_lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.hist), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
+                                                self.images, self.x[0].numel(), 1, _lib.stream_ptr()),
+                    "dmme_chain_update_dpmpp",
+                )
+            else:
+                _lib.check(
+                    lib.dmme_chain_update(self.kind, _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
+                                          self.images, self.x[0].numel(), _lib.stream_ptr()),
+                    "dmme_chain_update",
+                )
         plan.overwritten()
 
 
@@ -262,6 +282,59 @@ class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
     def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
         """the S-step guided strided chain from pure noise, one captured graph per step"""
         return self._cfg_generate(img_size, y, self.sub_timesteps)
+
+    def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
+        return self.model(x, t, y)
+
+
+class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
+    """DPM-Solver++(2M) with classifier-free guidance: the solver's update on e^ = e_u + s (e_c - e_u); the history holds B images."""
+
+    _chain_kind = _lib.CHAIN_DPMPP_CFG
+
+    def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 20, tau_schedule: str = "logsnr", order: int = 2, clip_x0: bool = False,
+                 alpha_bar: Optional[Tensor] = None, guidance_scale: float = 1.0, p_uncond: float = 0.1) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, order, clip_x0, alpha_bar)
+        self._init_cfg(guidance_scale, p_uncond)
+
+    def _scaled_rows(self):
+        """the rows with the guidance scale in column 6, rebuilt only when the scale changed"""
+        if getattr(self, "_rows_scale", None) != self.guidance_scale:
+            self._rows_s, self._rows_scale = self._make_rows(self.guidance_scale), self.guidance_scale
+        return self._rows_s
+
+    def _chain_tables(self):
+        return self.n_steps, list(self._scaled_rows()), list(self._tau_host)
+
+    def _guided_update(self, x: Tensor, eps: Tensor, B: int, i: int, hist: Tensor, valid: bool) -> Tensor:
+        """in place on x (2B images where s != 1, else B) and hist (B images); returns the B images"""
+        if self.guidance_scale == 1.0:
+            return self._dpm_update(x, eps, i, hist, valid)
+        _lib.check(_lib.lib().dmme_cfg_dpmpp_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(hist), _row_arg(self._scaled_rows()[i]), int(valid), B,
+                                                  x[0].numel(), _lib.stream_ptr()), "dmme_cfg_dpmpp_step")
+        return x[:B]
+
+    def sampling_step(self, x_tau_i: Tensor, i: Tensor, y, history: Optional[Tensor] = None, history_valid: bool = False) -> Tensor:
+        r"""x_{tau_{i-1}} from x_{tau_i} with guidance; i has shape (1,); `history` / `history_valid` as in `DPMSolverPP.sampling_step` (B images)"""
+        idx = self._index(_scalar_index(i, "an index"), "sampling_step")
+        valid = self._history_valid(history, history_valid)
+        x, eps, B = self._predict(x_tau_i, self.tau[idx].reshape(1), y)
+        return self._guided_update(x, eps, B, idx, self._history(x[:B], history), valid)
+
+    denoise_once, decode = (_needs_labels(n) for n in ("denoise_once", "decode"))
+
+    def _eager_generate(self, x_T: Tensor, y) -> Tensor:
+        """the host loop over the eager twins, bit-identical to the captured chain of `generate`"""
+        x, hist = x_T, torch.empty_like(x_T)
+        for k, i in enumerate(range(self.n_steps, 0, -1)):
+            xb, eps, B = self._predict(x, self.tau_tensor(i, x.device), y)
+            x = self._guided_update(xb, eps, B, i, hist, k > 0)
+        return x.clone()
+
+    @torch.no_grad()
+    def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
+        """the n_steps guided chain from pure noise, one captured graph per step"""
+        return self._cfg_generate(img_size, y, self.n_steps)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
         return self.model(x, t, y)

@@ -19,6 +19,7 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddim/cifar10.yaml [--num-images N] [--steps K] [--sampler ddim-paper --eta E]
   python -m dmme_amd.trainer sample --config configs/iddpm/cifar10.yaml --sample-steps K    (Improved DDPM: K << T strided steps)
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3,5 --guidance-scale 2.5   (classifier-free guidance)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dpm++ --sample-steps 20   (DPM-Solver++(2M); any of the four configs)
 """
 
 from __future__ import annotations
@@ -198,6 +199,38 @@ def build_module(conf: Dict[str, Any]):
     return module
 
 
+def _check_solver_args(args) -> None:
+    """what goes with --sampler dpm++ and what does not; exits with a message (before anything touches the GPU)"""
+    solver_flags = [f for f, given in (("--solver-order", args.solver_order is not None), ("--tau-schedule", args.tau_schedule is not None),
+                                       ("--clip-x0", args.clip_x0)) if given]
+    if args.sampler != "dpm++":
+        if solver_flags:
+            raise SystemExit(f"{', '.join(solver_flags)} belong{'s' if len(solver_flags) == 1 else ''} to --sampler dpm++")
+        return
+    if args.command != "sample":
+        raise SystemExit("--sampler dpm++ belongs to `sample`: DPM-Solver++ is a sampler, training is the config's own")
+    if args.eta is not None:
+        raise SystemExit("--eta belongs to --sampler ddim-paper: DPM-Solver++(2M) is deterministic")
+    if args.steps is not None:
+        raise SystemExit("--sampler dpm++ runs whole chains: --sample-steps K sets their length, --steps does not apply")
+    if args.sample_steps is not None and args.sample_steps < 1:
+        raise SystemExit("--sample-steps must be at least 1")
+
+
+def _dpm_solver(module, args):
+    """DPM-Solver++(2M) over the network and the noise schedule of the process the YAML built (classifier-free where that one is)"""
+    from .diffusion_models import DPMSolverPP
+
+    old = module.diffusion_model
+    kw = dict(sub_timesteps=20 if args.sample_steps is None else args.sample_steps, tau_schedule=args.tau_schedule or "logsnr",
+              order=args.solver_order or 2, clip_x0=args.clip_x0)
+    if getattr(module, "conditional", False):
+        from .guidance.cfg import ClassifierFreeDPMSolver
+
+        return ClassifierFreeDPMSolver.from_process(old, guidance_scale=old.guidance_scale, p_uncond=old.p_uncond, **kw)
+    return DPMSolverPP.from_process(old, **kw)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="dmme_amd.trainer")
     ap.add_argument("command", choices=["fit", "sample"])
@@ -212,20 +245,27 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
-    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper"],
-                    help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table")
-    ap.add_argument("--eta", type=float, default=0.0, help="sample --sampler ddim-paper: 0 deterministic ... 1 DDPM's posterior variance")
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++"],
+                    help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table; "
+                         "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20)")
+    ap.add_argument("--eta", type=float, default=None, help="sample --sampler ddim-paper: 0 (default) deterministic ... 1 DDPM's posterior variance")
+    ap.add_argument("--solver-order", type=int, default=None, choices=[1, 2], help="sample --sampler dpm++: 2 (default) multistep second order, 1 first order")
+    ap.add_argument("--tau-schedule", default=None, choices=["linear", "quadratic", "logsnr"], help="sample --sampler dpm++: the timestep grid (default logsnr)")
+    ap.add_argument("--clip-x0", action="store_true", help="sample --sampler dpm++: clamp every x0 prediction to [-1, 1] (wanted with the cosine schedule of the iddpm config, "
+                         "whose abar_T = 1.9e-15 scales the first x0 prediction by 2.3e7)")
     ap.add_argument("--labels", default=None, help="sample, class-conditional configs: comma-separated class labels, one per image or one for all (e.g. 3,5,7)")
     ap.add_argument("--guidance-scale", type=float, default=None, help="sample, class-conditional configs: s of e_u + s (e_c - e_u); 1 = conditional, 0 = unconditional")
     ap.add_argument("--sample-steps", type=int, default=None,
-                    help="sample, Improved DDPM configs: a strided chain over this many of the T timesteps, with the learned variance")
+                    help="sample, Improved DDPM configs: a strided chain over this many of the T timesteps, with the learned variance; "
+                         "sample --sampler dpm++: the solver's steps")
     args = ap.parse_args(argv)
+    _check_solver_args(args)
 
     from . import _lib
     from . import distributed as D
 
     conf = parse_config(args.config)
-    if args.sample_steps is not None:
+    if args.sample_steps is not None and args.sampler != "dpm++":
         from .lit_modules import LitIDDPM
 
         cls = _resolve(conf["model_spec"]["class_path"])
@@ -260,14 +300,16 @@ def main(argv=None):
             old = module.diffusion_model
             if not isinstance(old, DDIM):
                 raise SystemExit("--sampler ddim-paper needs a DDIM config (sub_timesteps and a tau schedule)")
-            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta).cuda()
+            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta or 0.0).cuda()
+        elif args.sampler == "dpm++":
+            module.diffusion_model = _dpm_solver(module, args).cuda()
         module.eval()
         dm = module.diffusion_model
         t0 = time.perf_counter()
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)
         if getattr(module, "conditional", False):
-            if args.steps is not None or args.sample_steps is not None or args.sampler != "config":
+            if args.steps is not None or args.sampler == "ddim-paper" or (args.sample_steps is not None and args.sampler != "dpm++"):
                 raise SystemExit("class-conditional configs sample whole chains: --labels / --guidance-scale only")
             if args.guidance_scale is not None:
                 dm.set_guidance_scale(args.guidance_scale)  # (the process stays what the YAML built: schedule, sampler, p_uncond)
@@ -277,6 +319,8 @@ def main(argv=None):
             imgs = module.generate(shape, labels)
         elif args.labels is not None or args.guidance_scale is not None:
             raise SystemExit("--labels / --guidance-scale need a class-conditional config (LitClassifierFreeDDPM)")
+        elif args.sampler == "dpm++":
+            imgs = dm.generate(shape)
         elif args.sample_steps is not None:
             imgs = module.generate(shape, sample_steps=args.sample_steps)
         elif args.steps is None:

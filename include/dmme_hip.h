@@ -400,7 +400,8 @@ DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64
  * step is device-resident, so ONE launch sequence (time MLP + UNet + noise draw + update + loop-state advance) serves every
  * step and can be captured in a hipGraph and replayed:
  *   state     64 bytes of device memory (eight 64-bit words): int64 i (loop index), int64 t (= t_table[i], what the network is
- *             evaluated at), uint64 Philox offset in quads, uint64 Philox seed, uint32 ticket + pad, three reserved words.
+ *             evaluated at), uint64 Philox offset in quads, uint64 Philox seed, uint32 ticket + pad, the DPM-Solver++ kinds' "history valid" flag
+ *             (cleared by dmme_chain_set, read by no other kind), two reserved words.
  *             dmme_chain_set initialises it (a one-thread kernel: the values travel as kernel arguments, no host buffer to
  *             keep alive, and a graph captured once serves any later seed).
  *   t_table   int64[n+1]: DDPM / IDDPM: t_table[i] = i; DDIM: the tau table (diffusion_models/ddim.py:41-53)
@@ -479,6 +480,42 @@ DMME_API int dmme_chain_update_cfg(int kind, float* x, const float* model_out, c
                                    void* state, int B, int64_t chw, void* stream);
 DMME_API int dmme_cfg_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
                                  int* status, int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
+/* ---- DPM-Solver++(2M) (Lu et al. 2022): the second-order multistep solver of the diffusion ODE in data-prediction form -----------
+ * alpha_t = sqrt(abar_t), sigma_t = sqrt(1 - abar_t), lambda_t = log(alpha_t / sigma_t); grid tau_0 = 0 < tau_1 < ... < tau_n.  The step from
+ * loop index i (a = tau_i) to i - 1 (p = tau_{i-1}), h = lambda_p - lambda_a, with the scalars folded on the host in float64 and rounded to fp32:
+ *     x0 = q0 x + q1 e             q0 = 1/alpha_a, q1 = -sigma_a/alpha_a; clamped to [-1, 1] iff clip != 0
+ *     D  = history valid ? x0 + w (x0 - x0_prev) : x0        w = h / (2 h_prev), h_prev = lambda_a - lambda_{tau_{i+1}};
+ *                                                            w = 0 at i = n, at order 1 and at i = 1
+ *     x' = k0 x + k1 D             k0 = sigma_p/sigma_a, k1 = -alpha_p expm1(-h); at i = 1 (p = 0): k0 = 0, k1 = 1 (the chain ends on x0)
+ *     history <- x0
+ * every product and sum rounded to fp32 on its own (no fma).  Kinds DMME_CHAIN_DPMPP = 8 and DMME_CHAIN_DPMPP_CFG = 9 have entry points and a
+ * table layout of their own (dmme_chain_step / dmme_chain_update / dmme_cfg_chain_step refuse them):
+ *   step_coef float[n+1][8], per loop index: {q0, q1, k0, k1, w, clip, s, -}    (s: the guidance scale, read by the CFG kind only)
+ *   history   fp32, B * chw values in x's layout: the previous step's x0, read and rewritten in place by the thread that owns the quad.  It
+ *             is NOT read while the history is not valid, so it needs no initialisation.
+ *   state     the loop state of dmme_chain_set; its sixth word is the "history valid" flag: dmme_chain_set clears it (a chain's first
+ *             step is first order wherever it starts), the chain forms set it as they advance the state (i -= 1, t = t_table[i]; the Philox
+ *             offset stays: the solver draws nothing).
+ *   out_planes  chw-sized planes per image of model_out: 1 (eps), or 2 (an IDDPM network's (eps, v): the eps plane is used).
+ * dmme_dpmpp_step: the eager twin (row: the 8 floats of one table row in HOST memory; history_valid as an argument), bit-identical to
+ * dmme_chain_update_dpmpp, the chain form (row and flag from device memory).  dmme_dpmpp_chain_step = dmme_unet_forward (no-grad form) at
+ * t = state.t + dmme_chain_update_dpmpp; a DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan.  The CFG forms: x_2B / model_out hold 2B images
+ * (conditional half, unconditional half), e = e_u + s (e_c - e_u) as DMME_CHAIN_GDDIM_CFG forms it, x' goes to both halves, history holds
+ * B images; B and chw are those of ONE half.  dmme_cfg_dpmpp_chain_step: a DMME_ARCH_DDPM_COND plan of batch 2B; status as
+ * dmme_unet_forward_cond (nullable).  chw must be a multiple of 4. */
+enum { DMME_CHAIN_DPMPP = 8, DMME_CHAIN_DPMPP_CFG = 9 };
+DMME_API int dmme_dpmpp_step(float* x, const float* model_out, float* history, const float* row, int history_valid, int B, int64_t chw, int out_planes,
+                             void* stream);
+DMME_API int dmme_chain_update_dpmpp(float* x, const float* model_out, float* history, const float* step_coef, const int64_t* t_table, void* state, int B,
+                                     int64_t chw, int out_planes, void* stream);
+DMME_API int dmme_dpmpp_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, float* history,
+                                   const float* step_coef, const int64_t* t_table, void* state, void* stream);
+DMME_API int dmme_cfg_dpmpp_step(float* x_2B, const float* model_out, float* history, const float* row, int history_valid, int B, int64_t chw, void* stream);
+DMME_API int dmme_chain_update_cfg_dpmpp(float* x_2B, const float* model_out, float* history, const float* step_coef, const int64_t* t_table, void* state,
+                                         int B, int64_t chw, void* stream);
+DMME_API int dmme_cfg_dpmpp_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
+                                       int* status, float* history, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
