@@ -430,25 +430,51 @@ int launch_randn(float* out, int64_t numel, uint64_t seed, uint64_t offset, hipS
 int launch_dropmask(float* out, int64_t numel, float p, uint64_t seed, uint64_t offset, hipStream_t s);
 int launch_q_sample(const float* x0, const float* z, const float* sqrt_abar, const float* sqrt_1m_abar,
                     const int64_t* t, int B, int64_t chw, float* x_t, float* target, hipStream_t s);
-int launch_ddpm_step(float* x, const float* eps, const float* z, float c1, float c2, float sigma, int add_noise,
-                     int64_t numel, hipStream_t s);
-int launch_ddim_step(float* x, const float* eps, float s1, float s2, int64_t numel, hipStream_t s);
-int launch_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, hipStream_t s);
 int slerp_parts(int64_t chw);  // blocks per image of the first launch of launch_slerp: its scratch holds 3 * B * slerp_parts(chw) floats
 int launch_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, float* scratch, hipStream_t s);
 int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s);
-int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
-                        hipStream_t s, const float* grad = nullptr, const float* noise = nullptr);
-// classifier-free guidance: x / out hold 2B images (conditional half, unconditional half); kinds DMME_CHAIN_DDPM_CFG / DMME_CHAIN_GDDIM_CFG
-int launch_cfg_step(int kind, float* x, const float* out, const float* z, float c0, float c1, float c2, float scale, int add_noise, int B, int64_t chw,
-                    hipStream_t s);
-int launch_chain_update_cfg(int kind, float* x, const float* out, const float* noise, const float* coef, const int64_t* t_table, void* state, int B,
-                            int64_t chw, hipStream_t s);
-// DPM-Solver++(2M): `row` 8 host floats, coef [n+1][8]; cfg: x / out hold 2B images (planes 1), hist B; planes: chw-planes per image of `out`
-int launch_dpmpp_step(bool cfg, float* x, const float* out, float* hist, const float* row, int history_valid, int B, int64_t chw, int planes,
-                      hipStream_t s);
-int launch_chain_update_dpmpp(bool cfg, float* x, const float* out, float* hist, const float* coef, const int64_t* t_table, void* state, int B,
-                              int64_t chw, int planes, hipStream_t s);
+
+// ---- the reverse update: one description of a sampler kind (DMME_CHAIN_*, dmme_hip.h), read at compile time by the two update kernels
+// (kernels_sampler.hip) and at run time by the argument checks of their launchers and of the capturable steps (plan.hip)
+constexpr bool kind_known(int k) { return k >= DMME_CHAIN_DDPM && k <= DMME_CHAIN_DPMPP_CFG; }
+// x and the network output hold two halves (conditional, unconditional), mixed by s = row[kind_scol]; sizes are those of ONE half
+constexpr bool kind_cfg(int k) { return k == DMME_CHAIN_DDPM_CFG || k == DMME_CHAIN_GDDIM_CFG || k == DMME_CHAIN_DPMPP_CFG; }
+// the element arithmetic: sampler_update<kind_base> of a kind in [DDPM, GDDIM], or dpmpp_update
+constexpr int kind_base(int k) {
+    return k == DMME_CHAIN_DDPM_CFG ? DMME_CHAIN_DDPM : k == DMME_CHAIN_GDDIM_CFG ? DMME_CHAIN_GDDIM : k == DMME_CHAIN_DPMPP_CFG ? DMME_CHAIN_DPMPP : k;
+}
+// DPM-Solver++: a history buffer that the update reads and rewrites, and whose flag the state advance raises; nothing drawn, so the Philox offset stays
+constexpr bool kind_hist(int k) { return kind_base(k) == DMME_CHAIN_DPMPP; }
+constexpr int kind_row(int k) { return kind_hist(k) ? 8 : 4; }  // floats per table row
+constexpr int kind_scol(int k) { return kind_hist(k) ? 6 : 3; }
+constexpr bool kind_grad(int k) { return k == DMME_CHAIN_DDPM_GUIDED || k == DMME_CHAIN_DDIM_GUIDED; }  // takes d log p(y | x_t, t) / d x_t
+// chw-sized planes per image of the network output, the predicted noise in the first: 1, 2 (IDDPM: eps, v), 0 = either, given at run time
+constexpr int kind_planes(int k) { return k == DMME_CHAIN_IDDPM ? 2 : k == DMME_CHAIN_DPMPP ? 0 : 1; }
+// when a step adds noise: never (the shipped DDIM kinds, the solver), where t != 1 (the DDPM means), where c2 != 0 (the paper-form DDIM kinds)
+enum { NOISE_NEVER, NOISE_NOT_LAST, NOISE_C2 };
+constexpr int kind_noise(int k) {
+    return kind_hist(k) || k == DMME_CHAIN_DDIM || k == DMME_CHAIN_DDIM_GUIDED ? NOISE_NEVER : kind_base(k) == DMME_CHAIN_GDDIM ? NOISE_C2 : NOISE_NOT_LAST;
+}
+// not_last: t != 1 (the chain kernel), the caller's add_noise (the eager entry points)
+constexpr int kind_adds_noise(int k, float c2, int not_last) { return kind_noise(k) == NOISE_C2 ? c2 != 0.0f : kind_noise(k) == NOISE_NOT_LAST ? not_last : 0; }
+// the chain form accepts normals from memory in place of the drawn ones (tests)
+constexpr bool kind_zin(int k) { return k == DMME_CHAIN_DDPM_GUIDED || kind_base(k) == DMME_CHAIN_GDDIM || k == DMME_CHAIN_DDPM_CFG; }
+// the eager form takes any numel (and IDDPM any chw), element by element where a quad does not fit; every other form needs chw % 4 == 0
+constexpr bool kind_ragged(int k) { return k == DMME_CHAIN_DDPM || k == DMME_CHAIN_DDIM || k == DMME_CHAIN_GDDIM || k == DMME_CHAIN_IDDPM; }
+
+// what an update works on.  numel = B * chw elements of x (CFG kinds: of ONE half; x and out hold two) in n4 quads; absent operands are null
+struct SamplerOperands {
+    float* x;
+    const float* out;   // the network output
+    const float* grad;  // kind_grad
+    const float* zin;   // normals: the eager form's z, the chain form's override
+    float* hist;        // kind_hist
+    int64_t chw, numel, n4;
+    int planes;         // read where kind_planes is 0
+};
+// row: kind_row host floats; flag: add_noise, or history_valid (kind_hist).  The guided kinds have no eager form.
+int launch_sampler_eager(const char* what, int kind, const SamplerOperands& o, const float* row, int flag, hipStream_t s);
+int launch_sampler_chain(const char* what, int kind, const SamplerOperands& o, const float* coef, const int64_t* t_table, void* state, hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient
@@ -461,8 +487,6 @@ int launch_cls_head_wgrad(const float* dlog, const float* pooled, const float* r
 int launch_log_softmax_grad(const float* logits, const int64_t* y, int B, int K, int mode, float scale, float* loss, float* dlog, int* status,
                             hipStream_t s);
 int launch_image_batch(const uint8_t* data, const int64_t* idx, const uint8_t* flip, int B, int C, int H, int W, float* out, hipStream_t s);
-int launch_iddpm_step(float* x, const float* out, const float* z, float c1, float c2, float log_beta, float log_beta_tilde, int add_noise,
-                      int B, int64_t chw, hipStream_t s);
 int launch_iddpm_loss(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int B,
                       int64_t chw, float w_simple, float w_vlb, float* loss, float* d_out, float gscale, float* scratch, hipStream_t s);
 int launch_iddpm_loss_rows(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int T,

@@ -5,6 +5,8 @@
 // (mul then add, never fma); square roots come from host tables.
 #include "common.h"
 
+#include <type_traits>
+
 namespace dmme {
 
 // ------------------------------------------------------------------ Philox4x32-10
@@ -151,65 +153,218 @@ __device__ __forceinline__ float sampler_update(float x, float e, float v, float
     }
     return add_noise ? __fadd_rn(m, __fmul_rn(KIND == DMME_CHAIN_IDDPM ? iddpm_std(v, c2, c3) : c2, z)) : m;
 }
-// where element i's predicted noise lies in the network output: IDDPM's is [B][2][chw] (eps plane, then the v plane chw further on),
-// every other kind's has x's own layout
-template <int KIND>
-__device__ __forceinline__ int64_t eps_at(int64_t i, int64_t chw) {
-    return KIND == DMME_CHAIN_IDDPM ? i + (i / chw) * chw : i;
+// DPM-Solver++(2M) (Lu et al. 2022), data-prediction form: the kinds whose update carries state of its own from one step to the next, the
+// previous step's x0 prediction, in a buffer of x's layout that the thread owning a quad reads (only where the history is valid: it may hold
+// anything before, NaN included) and overwrites.  Per loop index, 8 floats:
+//   {q0 = 1/alpha_a, q1 = -sigma_a/alpha_a, k0 = sigma_p/sigma_a, k1 = -alpha_p expm1(-h), w = h / (2 h_prev), clip, s, -}
+//   x0 = q0 x + q1 e (clamped to [-1, 1] iff clip);  D = valid ? x0 + w (x0 - x0_prev) : x0;  x' = k0 x + k1 D;  history <- x0
+struct DpmppRow {
+    float q0, q1, k0, k1, w, clip, s;
+};
+__device__ __forceinline__ float dpmpp_update(float x, float e, float prev, const DpmppRow& r, bool valid, float& x0) {
+    x0 = __fadd_rn(__fmul_rn(r.q0, x), __fmul_rn(r.q1, e));
+    if (r.clip != 0.0f) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float d = valid ? __fadd_rn(x0, __fmul_rn(r.w, __fsub_rn(x0, prev))) : x0;
+    return __fadd_rn(__fmul_rn(r.k0, x), __fmul_rn(r.k1, d));
 }
 __device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-// The eager update, in place on x: one thread per quad, 16-byte accesses where the quad is whole and (IDDPM) lies inside one image, which
-// it does, aligned in both planes, exactly when chw % 4 == 0; element by element otherwise.  z is read only where add_noise.
+// ---- the layer around the arithmetic.  A kind is described once (kind_*, common.h); update_quad<KIND> is the one place that loads a quad's
+// operands, mixes the two halves of a classifier-free kind, runs the arithmetic above and stores; eager_kernel<KIND> feeds it a table row and
+// a flag from its arguments and normals from memory, chain_kernel<KIND> a row from the device table at the loop index, the flag from the loop
+// state and normals drawn in place, and ends in chain_advance, the only writer of the loop state besides chain_set_kernel.
+//
+// The replayable chain step (hipGraph-friendly sampling loops): everything that changes from one denoising step to the next lives in DEVICE
+// memory, so the launch sequence of a step is the same every time and can be replayed from one captured graph: the loop state {i,
+// t = t_table[i], Philox offset and seed, ticket, history flag}, the per-index scalars of the update (`coef[i]`) and the noise itself (drawn
+// from the same Philox stream / offsets dmme_randn would use: the chain is bit-identical to the eager loop under the same seed).
+struct ChainState {
+    long long i;
+    long long t;
+    unsigned long long offset;
+    unsigned long long seed;
+    unsigned int ticket, pad;
+    unsigned long long history_valid;  // DPM-Solver++ kinds: the history buffer holds the x0 prediction of this chain's previous step
+    unsigned long long reserved[2];
+};
+static_assert(sizeof(ChainState) == 64, "ChainState is eight 64-bit words (dmme_hip.h: dmme_chain_*)");
+
+__global__ void chain_set_kernel(ChainState* st, long long i, const long long* __restrict__ t_table, unsigned long long seed, unsigned long long offset) {
+    st->i = i;
+    st->t = t_table[i];
+    st->offset = offset;
+    st->seed = seed;
+    st->ticket = 0u;
+    st->pad = 0u;
+    st->history_valid = 0ull;  // a chain's first step is first order wherever it starts (no other kind reads the word)
+}
+int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s) {
+    hipLaunchKernelGGL(chain_set_kernel, dim3(1), dim3(1), 0, s, (ChainState*)state, (long long)i, (const long long*)t_table, (unsigned long long)seed,
+                       (unsigned long long)offset);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
+// The end of a chain kernel, after the block's __syncthreads(): every thread of this block has read the state (and is past its loads of it).
+// The block that takes the last ticket has, by construction, run after every block read the state (all others took their ticket after
+// reading it), and moves it on: i -= 1 (not below 0), t = t_table[i], offset += offset_inc, the history flag raised where asked.
+__device__ __forceinline__ void chain_advance(ChainState* st, const long long* __restrict__ t_table, long long i, unsigned long long offset_inc,
+                                              bool raise_history) {
+    if (threadIdx.x != 0) return;
+    const unsigned tk = atomicAdd(&st->ticket, 1u);
+    if (tk != gridDim.x - 1) return;
+    const long long ni = i > 0 ? i - 1 : 0;
+    st->i = ni;
+    st->t = t_table[ni];
+    if (offset_inc) st->offset += offset_inc;
+    if (raise_history) st->history_valid = 1ull;
+    atomicExch(&st->ticket, 0u);
+}
+
+struct Row {  // one table row: c0..c3 of sampler_update (a classifier-free kind's s in c3), or the DpmppRow and a spare
+    float c[8];
+};
+
+// the normals of the quad at element b: zeros where the step adds none, else those in `zin` (always given where the kernel does not draw) or,
+// without them, the draw at Philox counter `ctr`
+template <bool DRAWS>
+__device__ __forceinline__ void noise4(bool add_noise, const float* zin, int64_t b, uint64_t seed, uint64_t ctr, float (&z)[4]) {
+    z[0] = z[1] = z[2] = z[3] = 0.f;
+    if (!add_noise) return;
+    if (!DRAWS || zin) {
+        const float4 zv = load4(zin + b);
+        z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+    } else {
+        normal4(seed, ctr, z);
+    }
+}
+
+// quad q of x (a classifier-free kind: of its first half, the result into both; noise and history are indexed by the first half, so such a
+// chain at batch B draws exactly what an unguided chain at batch B does).  Every access is 16 bytes, aligned and inside one image: chw % 4 == 0.
+// flag: add_noise, or (kind_hist) the history is valid.  The mixed prediction e^ = e_u + s (e_c - e_u) is three separately rounded operations;
+// s = 1 is plain conditional sampling (Ho & Salimans' w = s - 1).  The caller has z ready, so nothing loaded here is live across a draw.
 template <int KIND>
-__global__ void __launch_bounds__(256) eager_update_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ z, float c0,
-                                                           float c1, float c2, float c3, int add_noise, int64_t chw, int64_t n4, int64_t numel) {
-    constexpr bool LEARNED = KIND == DMME_CHAIN_IDDPM;
-    const bool quads_fit = !LEARNED || chw % 4 == 0;
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void update_quad(const SamplerOperands& o, int64_t q, const Row& r, int flag, const float (&z)[4]) {
+    const int64_t b = q * 4;
+    const int planes = kind_planes(KIND) ? kind_planes(KIND) : o.planes;
+    const int64_t eo = planes == 2 ? b + (b / o.chw) * o.chw : b;  // [B][2][chw]: the eps plane, then (IDDPM's v) the plane chw further on
+    float4 xv = load4(o.x + b), ev = load4(o.out + eo), av = make_float4(0.f, 0.f, 0.f, 0.f);  // av: v, g or the previous x0, by kind
+    float *xs = reinterpret_cast<float*>(&xv), *es = reinterpret_cast<float*>(&ev), *as = reinterpret_cast<float*>(&av);
+    if constexpr (kind_cfg(KIND)) {
+        const float4 uv = load4(o.out + o.n4 * 4 + b);
+        const float* us = reinterpret_cast<const float*>(&uv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(r.c[kind_scol(KIND)], __fsub_rn(es[j], us[j])));
+    }
+    if constexpr (kind_hist(KIND)) {
+        const DpmppRow d = {r.c[0], r.c[1], r.c[2], r.c[3], r.c[4], r.c[5], r.c[6]};
+        if (flag) av = load4(o.hist + b);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xs[j] = dpmpp_update(xs[j], es[j], as[j], d, flag != 0, as[j]);
+        *reinterpret_cast<float4*>(o.hist + b) = av;
+    } else {
+        constexpr bool LEARNED = KIND == DMME_CHAIN_IDDPM;
+        if (LEARNED && flag) av = load4(o.out + eo + o.chw);
+        if (kind_grad(KIND)) av = load4(o.grad + b);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            xs[j] = sampler_update<kind_base(KIND)>(xs[j], es[j], LEARNED ? as[j] : 0.f, kind_grad(KIND) ? as[j] : 0.f, z[j], r.c[0], r.c[1], r.c[2],
+                                                    kind_cfg(KIND) ? 0.f : r.c[3], flag);
+    }
+    *reinterpret_cast<float4*>(o.x + b) = xv;
+    if (kind_cfg(KIND)) *reinterpret_cast<float4*>(o.x + o.n4 * 4 + b) = xv;
+}
+
+// The eager update, in place on x: one thread per quad.  The kinds of kind_ragged go element by element where the quad is not whole or
+// (IDDPM) does not lie inside one image, aligned in both planes, which it does exactly when chw % 4 == 0.  z is read only where add_noise.
+template <int KIND>
+__global__ void __launch_bounds__(256) eager_kernel(SamplerOperands o, Row r, int flag) {
+    const bool quads_fit = KIND != DMME_CHAIN_IDDPM || o.chw % 4 == 0;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < o.n4; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = q * 4;
-        if (b + 3 < numel && quads_fit) {
-            const int64_t eo = eps_at<KIND>(b, chw);
-            float4 xv = load4(x + b), vv = make_float4(0.f, 0.f, 0.f, 0.f), zv = vv;
-            const float4 ev = load4(out + eo);
-            if (add_noise) zv = load4(z + b);
-            if (LEARNED && add_noise) vv = load4(out + eo + chw);
-            xv.x = sampler_update<KIND>(xv.x, ev.x, vv.x, 0.f, zv.x, c0, c1, c2, c3, add_noise);
-            xv.y = sampler_update<KIND>(xv.y, ev.y, vv.y, 0.f, zv.y, c0, c1, c2, c3, add_noise);
-            xv.z = sampler_update<KIND>(xv.z, ev.z, vv.z, 0.f, zv.z, c0, c1, c2, c3, add_noise);
-            xv.w = sampler_update<KIND>(xv.w, ev.w, vv.w, 0.f, zv.w, c0, c1, c2, c3, add_noise);
-            *reinterpret_cast<float4*>(x + b) = xv;
-        } else {
-            for (int64_t i = b; i < b + 4 && i < numel; ++i) {
-                const int64_t eo = eps_at<KIND>(i, chw);
-                x[i] = sampler_update<KIND>(x[i], out[eo], LEARNED && add_noise ? out[eo + chw] : 0.f, 0.f, add_noise ? z[i] : 0.f, c0, c1, c2, c3,
-                                            add_noise);
+        if (!kind_ragged(KIND) || (b + 3 < o.numel && quads_fit)) {
+            float z[4];
+            noise4<false>(kind_noise(KIND) != NOISE_NEVER && flag, o.zin, b, 0, 0, z);
+            update_quad<KIND>(o, q, r, flag, z);
+        } else if constexpr (kind_ragged(KIND)) {
+            for (int64_t i = b; i < b + 4 && i < o.numel; ++i) {
+                const int64_t eo = KIND == DMME_CHAIN_IDDPM ? i + (i / o.chw) * o.chw : i;
+                o.x[i] = sampler_update<KIND>(o.x[i], o.out[eo], KIND == DMME_CHAIN_IDDPM && flag ? o.out[eo + o.chw] : 0.f, 0.f, flag ? o.zin[i] : 0.f,
+                                              r.c[0], r.c[1], r.c[2], r.c[3], flag);
             }
         }
     }
 }
+
+// The chain form: the row at coef[kind_row * i], the flag from the loop state (t != 1 / c2 != 0 by the kind's noise rule, or the history
+// flag), normals drawn at Philox(seed, offset + quad) unless o.zin is given (the kinds of kind_zin; tests).  The offset advances by the quads of
+// the update at every step, whether or not the step used its normals (the reference draws and discards at t == 1).
+// amdgpu_waves_per_eu(8): the draw's sin / cos / log keep the kinds that also branch on zin within a few scalar registers of the 8-wave budget;
+// told the target, the scheduler stays inside it (no spill) instead of settling for 7 waves.
 template <int KIND>
-static int launch_eager_update(float* x, const float* out, const float* z, float c0, float c1, float c2, float c3, int add_noise, int64_t chw,
-                               int64_t numel, hipStream_t s) {
-    if (numel <= 0) return DMME_OK;
-    const int64_t n4 = (numel + 3) / 4;
-    hipLaunchKernelGGL(eager_update_kernel<KIND>, dim3(grid_for(n4)), dim3(256), 0, s, x, out, z, c0, c1, c2, c3, add_noise, chw, n4, numel);
-    DMME_CHECK_LAUNCH();
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) chain_kernel(SamplerOperands o, const float* __restrict__ coef, const long long* __restrict__ t_table, ChainState* st) {
+    const long long i = st->i, t = st->t;
+    const unsigned long long off = st->offset, seed = st->seed;
+    Row r;
+#pragma unroll
+    for (int j = 0; j < kind_row(KIND); ++j) r.c[j] = coef[kind_row(KIND) * i + j];
+    const int flag = kind_hist(KIND) ? st->history_valid != 0ull : kind_adds_noise(KIND, r.c[2], t != 1);
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < o.n4; q += (int64_t)gridDim.x * blockDim.x) {
+        float z[4];
+        noise4<true>(kind_noise(KIND) != NOISE_NEVER && flag, kind_zin(KIND) ? o.zin : nullptr, q * 4, seed, off + (uint64_t)q, z);
+        update_quad<KIND>(o, q, r, flag, z);
+    }
+    __syncthreads();
+    chain_advance(st, t_table, i, kind_hist(KIND) ? 0ull : (unsigned long long)o.n4, kind_hist(KIND));
+}
+
+// the run-time kind as a compile-time one: f(std::integral_constant<int, kind>)
+template <int K = 0, class F>
+static int dispatch_kind(int kind, F&& f) {
+    if constexpr (K > DMME_CHAIN_DPMPP_CFG) {
+        set_error("unknown sampler kind %d", kind);
+        return DMME_ERR_INVALID;
+    } else {
+        return kind == K ? f(std::integral_constant<int, K>{}) : dispatch_kind<K + 1>(kind, f);
+    }
+}
+static int check_operands(const char* what, int kind, const SamplerOperands& o, bool eager) {
+    DMME_REQUIRE(kind_known(kind), DMME_ERR_INVALID, "%s: unknown sampler kind %d", what, kind);
+    DMME_REQUIRE(o.x && o.out && (o.hist || !kind_hist(kind)) && o.numel > 0 && o.chw > 0, DMME_ERR_INVALID, "%s: bad argument", what);
+    DMME_REQUIRE(kind_grad(kind) == (o.grad != nullptr), DMME_ERR_INVALID, "%s: the guided kinds (3, 4) and only they take a gradient", what);
+    DMME_REQUIRE(kind_planes(kind) || o.planes == 1 || o.planes == 2, DMME_ERR_INVALID, "%s: a network output of %d planes per image (1: eps, 2: eps and v)",
+                 what, o.planes);
+    DMME_REQUIRE((eager && kind_ragged(kind)) || o.chw % 4 == 0, DMME_ERR_UNSUPPORTED, "%s: image size %lld is not a multiple of 4", what, (long long)o.chw);
     return DMME_OK;
 }
-int launch_ddpm_step(float* x, const float* eps, const float* z, float c1, float c2, float sigma, int add_noise, int64_t numel, hipStream_t s) {
-    return launch_eager_update<DMME_CHAIN_DDPM>(x, eps, z, c1, c2, sigma, 0.f, add_noise, 0, numel, s);
+int launch_sampler_eager(const char* what, int kind, const SamplerOperands& o, const float* row, int flag, hipStream_t s) {
+    if (kind_ragged(kind) && o.numel <= 0) return DMME_OK;
+    if (int rc = check_operands(what, kind, o, true)) return rc;
+    DMME_REQUIRE(row, DMME_ERR_INVALID, "%s: null argument", what);
+    Row r = {};
+    for (int j = 0; j < kind_row(kind); ++j) r.c[j] = row[j];
+    if (!kind_hist(kind)) flag = kind_adds_noise(kind, r.c[2], flag);
+    DMME_REQUIRE(o.zin || kind_hist(kind) || !flag, DMME_ERR_INVALID, "%s: a step that adds noise needs z", what);
+    return dispatch_kind(kind, [&](auto k) -> int {
+        constexpr int K = decltype(k)::value;
+        if constexpr (kind_grad(K)) {
+            set_error("%s: the guided kinds have no eager form", what);
+            return DMME_ERR_INVALID;
+        } else {
+            hipLaunchKernelGGL(eager_kernel<K>, dim3(grid_for(o.n4)), dim3(256), 0, s, o, r, flag);
+            DMME_CHECK_LAUNCH();
+            return DMME_OK;
+        }
+    });
 }
-int launch_ddim_step(float* x, const float* eps, float s1, float s2, int64_t numel, hipStream_t s) {
-    return launch_eager_update<DMME_CHAIN_DDIM>(x, eps, nullptr, s1, s2, 0.f, 0.f, 0, 0, numel, s);
-}
-int launch_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, hipStream_t s) {
-    return launch_eager_update<DMME_CHAIN_GDDIM>(x, eps, z, k0, k1, k2, 0.f, k2 != 0.0f, 0, numel, s);  // z is read only where k2 != 0
-}
-// network output (B, 2C, H, W): channels [0, C) = eps, [C, 2C) = v (diffusion_models/iddpm.py:159)
-int launch_iddpm_step(float* x, const float* out, const float* z, float c1, float c2, float log_beta, float log_beta_tilde, int add_noise, int B,
-                      int64_t chw, hipStream_t s) {
-    return launch_eager_update<DMME_CHAIN_IDDPM>(x, out, z, c1, c2, log_beta, log_beta_tilde, add_noise, chw, (int64_t)B * chw, s);
+int launch_sampler_chain(const char* what, int kind, const SamplerOperands& o, const float* coef, const int64_t* t_table, void* state, hipStream_t s) {
+    if (int rc = check_operands(what, kind, o, false)) return rc;
+    DMME_REQUIRE(coef && t_table && state, DMME_ERR_INVALID, "%s: null argument", what);
+    return dispatch_kind(kind, [&](auto k) -> int {
+        hipLaunchKernelGGL(chain_kernel<decltype(k)::value>, dim3(grid_for(o.n4)), dim3(256), 0, s, o, coef, (const long long*)t_table, (ChainState*)state);
+        DMME_CHECK_LAUNCH();
+        return DMME_OK;
+    });
 }
 
 // ------------------------------------------------------------------ MSE loss (+ gradient)
@@ -596,326 +751,6 @@ int launch_tsampler_update(float* hist, int* count, int T, int H, const int64_t*
     return DMME_OK;
 }
 
-// ------------------------------------------------------------------ replayable chain step (hipGraph-friendly sampling loops)
-// Everything that changes from one denoising step to the next lives in DEVICE memory, so the launch sequence of a step is the
-// same every time and can be replayed from one captured graph: the loop state {i, t = t_table[i], Philox offset and seed, ticket}, the
-// per-index scalars of the update (`coef[i][0..3]`) and the noise itself (drawn here from the same Philox stream / offsets
-// dmme_randn would use: the chain is bit-identical to the eager loop under the same seed).  The block that takes the last
-// ticket has, by construction, run after every block read the state, and advances it: i -= 1, t = t_table[i], offset += quads.
-struct ChainState {
-    long long i;
-    long long t;
-    unsigned long long offset;
-    unsigned long long seed;
-    unsigned int ticket, pad;
-    unsigned long long history_valid;  // DPM-Solver++ kinds: the history buffer holds the x0 prediction of this chain's previous step
-    unsigned long long reserved[2];
-};
-static_assert(sizeof(ChainState) == 64, "ChainState is eight 64-bit words (dmme_hip.h: dmme_chain_*)");
-
-__global__ void chain_set_kernel(ChainState* st, long long i, const long long* __restrict__ t_table, unsigned long long seed, unsigned long long offset) {
-    st->i = i;
-    st->t = t_table[i];
-    st->offset = offset;
-    st->seed = seed;
-    st->ticket = 0u;
-    st->pad = 0u;
-    st->history_valid = 0ull;  // a chain's first step is first order wherever it starts (no other kind reads the word)
-}
-
-// KIND: a DMME_CHAIN_* constant; coef[i][0..3] are c0..c3 of sampler_update<KIND> at loop index i.  The kinds with a DDPM mean add noise
-// where t != 1, the paper-form DDIM kind where k2 != 0, the shipped DDIM kinds never; the offset advances by n4 at every step all the same
-// (the reference draws and discards at t == 1).  IDDPM: `out` has 2*chw values per image.
-// g: d log p(y | x_t, t) / d x_t (guided kinds); zin (nullable; DDPM_GUIDED and GDDIM): normals to use instead of the drawn ones (tests)
-template <int KIND>
-__global__ void __launch_bounds__(256) chain_update_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ coef,
-                                                           const long long* __restrict__ t_table, ChainState* st, int64_t chw, int64_t n4,
-                                                           const float* __restrict__ g, const float* __restrict__ zin) {
-    constexpr bool DRAWS = KIND != DMME_CHAIN_DDIM && KIND != DMME_CHAIN_DDIM_GUIDED;
-    constexpr bool TAKES_ZIN = KIND == DMME_CHAIN_DDPM_GUIDED || KIND == DMME_CHAIN_GDDIM;
-    const long long i = st->i, t = st->t;
-    const unsigned long long off = st->offset, seed = st->seed;
-    const float c0 = coef[4 * i], c1 = coef[4 * i + 1], c2 = coef[4 * i + 2], c3 = coef[4 * i + 3];
-    const int add_noise = KIND == DMME_CHAIN_GDDIM ? c2 != 0.0f : t != 1;
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = q * 4;
-        float4 xv = load4(x + b), vv = make_float4(0.f, 0.f, 0.f, 0.f), gv = vv;
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (DRAWS && add_noise) {
-            if (TAKES_ZIN && zin) {
-                const float4 zv = load4(zin + b);
-                z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-            } else {
-                normal4(seed, off + (uint64_t)q, z);
-            }
-        }
-        const int64_t eo = eps_at<KIND>(b, chw);  // chw % 4 == 0: a quad never straddles two images (loaded after the draw: not live across it)
-        const float4 ev = load4(out + eo);
-        if (KIND == DMME_CHAIN_IDDPM) vv = load4(out + eo + chw);
-        if (KIND == DMME_CHAIN_DDPM_GUIDED || KIND == DMME_CHAIN_DDIM_GUIDED) gv = load4(g + b);
-        float* xs = reinterpret_cast<float*>(&xv);
-        const float *es = reinterpret_cast<const float*>(&ev), *vs = reinterpret_cast<const float*>(&vv), *gs = reinterpret_cast<const float*>(&gv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xs[j] = sampler_update<KIND>(xs[j], es[j], vs[j], gs[j], z[j], c0, c1, c2, c3, add_noise);
-        *reinterpret_cast<float4*>(x + b) = xv;
-    }
-    __syncthreads();  // every thread of this block has read the state (and is past its loads of it)
-    if (threadIdx.x == 0) {
-        const unsigned tk = atomicAdd(&st->ticket, 1u);
-        if (tk == gridDim.x - 1) {  // last block: all others took their ticket after reading the state
-            const long long ni = i > 0 ? i - 1 : 0;
-            st->i = ni;
-            st->t = t_table[ni];
-            st->offset = off + (unsigned long long)n4;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
-}
-
-int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s) {
-    hipLaunchKernelGGL(chain_set_kernel, dim3(1), dim3(1), 0, s, (ChainState*)state, (long long)i, (const long long*)t_table, (unsigned long long)seed,
-                       (unsigned long long)offset);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-
-int launch_chain_update(int kind, float* x, const float* out, const float* coef, const int64_t* t_table, void* state, int B, int64_t chw,
-                        hipStream_t s, const float* grad, const float* noise) {
-    const bool guided = kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED;
-    DMME_REQUIRE(kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_GDDIM, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
-    DMME_REQUIRE(guided == (grad != nullptr), DMME_ERR_INVALID, "chain_update: the guided kinds (3, 4) and only they take a gradient");
-    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "chain_update: image size %lld is not a multiple of 4", (long long)chw);
-    const int64_t n4 = (int64_t)B * chw / 4;
-    if (n4 <= 0) return DMME_OK;
-    const dim3 g(grid_for(n4)), b(256);
-    ChainState* st = (ChainState*)state;
-    const long long* tt = (const long long*)t_table;
-    if (kind == DMME_CHAIN_DDPM)
-        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else if (kind == DMME_CHAIN_DDIM)
-        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDIM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else if (kind == DMME_CHAIN_IDDPM)
-        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_IDDPM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else if (kind == DMME_CHAIN_DDPM_GUIDED)
-        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDPM_GUIDED>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else if (kind == DMME_CHAIN_DDIM_GUIDED)
-        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_DDIM_GUIDED>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    else
-        hipLaunchKernelGGL(chain_update_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, coef, tt, st, chw, n4, grad, noise);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-
-// ------------------------------------------------------------------ classifier-free guidance (Ho & Salimans 2021)
-// x and the network output hold 2B images: the conditional half [0, B), then the unconditional half [B, 2B).  One element function for the
-// eager kernel (host scalars) and the chain kernel (device state): the mixed prediction e^ = e_u + s (e_c - e_u), three separately rounded
-// operations, then the base kind's update with e^.  s = 1 is plain conditional sampling (Ho & Salimans' w = s - 1).  The result goes to both
-// halves of x; noise is indexed by the element of the first half, so a chain at batch B draws exactly what an unguided chain at batch B does.
-template <int BASE>
-__device__ __forceinline__ float cfg_update(float x, float ec, float eu, float z, float c0, float c1, float c2, float s, int add_noise) {
-    const float e = __fadd_rn(eu, __fmul_rn(s, __fsub_rn(ec, eu)));
-    return sampler_update<BASE>(x, e, 0.f, 0.f, z, c0, c1, c2, 0.f, add_noise);
-}
-// the quad at element b of the first half (b + 3 < half, everything 16-byte aligned: chw % 4 == 0)
-template <int BASE>
-__device__ __forceinline__ void cfg_quad(float* __restrict__ x, const float* __restrict__ out, int64_t b, int64_t half, const float (&z)[4], float c0, float c1,
-                                         float c2, float s, int add_noise) {
-    float4 xv = load4(x + b);
-    const float4 cv = load4(out + b), uv = load4(out + half + b);
-    float* xs = reinterpret_cast<float*>(&xv);
-    const float *cs = reinterpret_cast<const float*>(&cv), *us = reinterpret_cast<const float*>(&uv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xs[j] = cfg_update<BASE>(xs[j], cs[j], us[j], z[j], c0, c1, c2, s, add_noise);
-    *reinterpret_cast<float4*>(x + b) = xv;
-    *reinterpret_cast<float4*>(x + half + b) = xv;
-}
-template <int BASE>
-__global__ void __launch_bounds__(256) cfg_eager_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ zin, float c0, float c1,
-                                                        float c2, float s, int add_noise, int64_t n4) {
-    const int64_t half = n4 * 4;
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (add_noise) {
-            const float4 zv = load4(zin + q * 4);
-            z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-        }
-        cfg_quad<BASE>(x, out, q * 4, half, z, c0, c1, c2, s, add_noise);
-    }
-}
-// the chain form: scalars from coef[i] (s = coef[i][3]), normals drawn at Philox(seed, offset + quad of the FIRST half) unless zin is given;
-// the last block advances the state by the quads of ONE half
-template <int BASE>
-__global__ void __launch_bounds__(256) cfg_chain_kernel(float* __restrict__ x, const float* __restrict__ out, const float* __restrict__ coef,
-                                                        const long long* __restrict__ t_table, ChainState* st, int64_t n4, const float* __restrict__ zin) {
-    const long long i = st->i, t = st->t;
-    const unsigned long long off = st->offset, seed = st->seed;
-    const float c0 = coef[4 * i], c1 = coef[4 * i + 1], c2 = coef[4 * i + 2], sc = coef[4 * i + 3];
-    const int add_noise = BASE == DMME_CHAIN_GDDIM ? c2 != 0.0f : t != 1;
-    const int64_t half = n4 * 4;
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (add_noise) {
-            if (zin) {
-                const float4 zv = load4(zin + q * 4);
-                z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-            } else {
-                normal4(seed, off + (uint64_t)q, z);
-            }
-        }
-        cfg_quad<BASE>(x, out, q * 4, half, z, c0, c1, c2, sc, add_noise);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned tk = atomicAdd(&st->ticket, 1u);
-        if (tk == gridDim.x - 1) {
-            const long long ni = i > 0 ? i - 1 : 0;
-            st->i = ni;
-            st->t = t_table[ni];
-            st->offset = off + (unsigned long long)n4;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
-}
-static int cfg_check(const char* what, int kind, const void* x, const void* out, int B, int64_t chw) {
-    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_CFG || kind == DMME_CHAIN_GDDIM_CFG, DMME_ERR_INVALID, "%s: kind %d is not a classifier-free kind (6, 7)", what, kind);
-    DMME_REQUIRE(x && out && B > 0 && chw > 0, DMME_ERR_INVALID, "%s: bad argument", what);
-    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "%s: image size %lld is not a multiple of 4", what, (long long)chw);
-    return DMME_OK;
-}
-int launch_cfg_step(int kind, float* x, const float* out, const float* z, float c0, float c1, float c2, float scale, int add_noise, int B, int64_t chw,
-                    hipStream_t s) {
-    if (int rc = cfg_check("cfg_step", kind, x, out, B, chw)) return rc;
-    if (kind == DMME_CHAIN_GDDIM_CFG) add_noise = c2 != 0.0f;
-    DMME_REQUIRE(z || !add_noise, DMME_ERR_INVALID, "cfg_step: a step that adds noise needs z");
-    const int64_t n4 = (int64_t)B * chw / 4;
-    const dim3 g(grid_for(n4)), b(256);
-    if (kind == DMME_CHAIN_DDPM_CFG)
-        hipLaunchKernelGGL(cfg_eager_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, z, c0, c1, c2, scale, add_noise, n4);
-    else
-        hipLaunchKernelGGL(cfg_eager_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, z, c0, c1, c2, scale, add_noise, n4);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-int launch_chain_update_cfg(int kind, float* x, const float* out, const float* noise, const float* coef, const int64_t* t_table, void* state, int B,
-                            int64_t chw, hipStream_t s) {
-    if (int rc = cfg_check("chain_update_cfg", kind, x, out, B, chw)) return rc;
-    DMME_REQUIRE(coef && t_table && state, DMME_ERR_INVALID, "chain_update_cfg: null argument");
-    const int64_t n4 = (int64_t)B * chw / 4;
-    const dim3 g(grid_for(n4)), b(256);
-    if (kind == DMME_CHAIN_DDPM_CFG)
-        hipLaunchKernelGGL(cfg_chain_kernel<DMME_CHAIN_DDPM>, g, b, 0, s, x, out, coef, (const long long*)t_table, (ChainState*)state, n4, noise);
-    else
-        hipLaunchKernelGGL(cfg_chain_kernel<DMME_CHAIN_GDDIM>, g, b, 0, s, x, out, coef, (const long long*)t_table, (ChainState*)state, n4, noise);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-
-// ------------------------------------------------------------------ DPM-Solver++(2M) (Lu et al. 2022), data-prediction form
-// The first kind whose update carries state of its own from one replay to the next: the previous step's x0 prediction, in a buffer of
-// x's layout that the thread owning a quad reads (only where the history is valid) and overwrites.  Per loop index, 8 floats:
-//   {q0 = 1/alpha_a, q1 = -sigma_a/alpha_a, k0 = sigma_p/sigma_a, k1 = -alpha_p expm1(-h), w = h / (2 h_prev), clip, s, -}
-//   x0 = q0 x + q1 e (clamped to [-1, 1] iff clip);  D = valid ? x0 + w (x0 - x0_prev) : x0;  x' = k0 x + k1 D;  history <- x0
-// every product and sum rounded on its own, like everything in this file.  CFG: e = e_u + s (e_c - e_u) over a 2B batch exactly as
-// cfg_update forms it, the result into both halves of x, a history of B images.
-constexpr int DPMPP_ROW = 8;
-struct DpmppRow {
-    float q0, q1, k0, k1, w, clip, s;
-};
-__device__ __forceinline__ float dpmpp_update(float x, float e, float prev, const DpmppRow& r, bool valid, float& x0) {
-    x0 = __fadd_rn(__fmul_rn(r.q0, x), __fmul_rn(r.q1, e));
-    if (r.clip != 0.0f) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float d = valid ? __fadd_rn(x0, __fmul_rn(r.w, __fsub_rn(x0, prev))) : x0;
-    return __fadd_rn(__fmul_rn(r.k0, x), __fmul_rn(r.k1, d));
-}
-// the quad at element b of x (CFG: of its first half; `half` = elements of one half).  planes: chw-sized planes per image of the network
-// output, the predicted noise in the first (2: an IDDPM network's (eps, v)); chw % 4 == 0 keeps every access 16-byte aligned and inside
-// one image.  The history is not loaded at all while it is not valid: it may hold anything, NaN included.
-template <bool CFG>
-__device__ __forceinline__ void dpmpp_quad(float* __restrict__ x, const float* __restrict__ out, float* __restrict__ hist, int64_t b, int64_t half,
-                                           int64_t chw, int planes, const DpmppRow& r, bool valid) {
-    const int64_t eo = planes == 2 ? b + (b / chw) * chw : b;
-    float4 xv = load4(x + b), ev = load4(out + eo), hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    float* es = reinterpret_cast<float*>(&ev);
-    if (CFG) {
-        const float4 uv = load4(out + half + b);
-        const float* us = reinterpret_cast<const float*>(&uv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(r.s, __fsub_rn(es[j], us[j])));
-    }
-    if (valid) hv = load4(hist + b);
-    float *xs = reinterpret_cast<float*>(&xv), *hs = reinterpret_cast<float*>(&hv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xs[j] = dpmpp_update(xs[j], es[j], hs[j], r, valid, hs[j]);
-    *reinterpret_cast<float4*>(x + b) = xv;
-    if (CFG) *reinterpret_cast<float4*>(x + half + b) = xv;
-    *reinterpret_cast<float4*>(hist + b) = hv;
-}
-template <bool CFG>
-__global__ void __launch_bounds__(256) dpmpp_eager_kernel(float* __restrict__ x, const float* __restrict__ out, float* __restrict__ hist, DpmppRow r,
-                                                          int valid, int64_t chw, int planes, int64_t n4) {
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x)
-        dpmpp_quad<CFG>(x, out, hist, q * 4, n4 * 4, chw, planes, r, valid != 0);
-}
-// the chain form: the row at coef[8 i], `valid` from the loop state.  The block with the last ticket moves the state on and raises
-// history_valid; the Philox offset stays (the solver draws nothing).
-template <bool CFG>
-__global__ void __launch_bounds__(256) dpmpp_chain_kernel(float* __restrict__ x, const float* __restrict__ out, float* __restrict__ hist,
-                                                          const float* __restrict__ coef, const long long* __restrict__ t_table, ChainState* st, int64_t chw,
-                                                          int planes, int64_t n4) {
-    const long long i = st->i;
-    const bool valid = st->history_valid != 0ull;
-    const float* c = coef + DPMPP_ROW * i;
-    const DpmppRow r = {c[0], c[1], c[2], c[3], c[4], c[5], c[6]};
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x)
-        dpmpp_quad<CFG>(x, out, hist, q * 4, n4 * 4, chw, planes, r, valid);
-    __syncthreads();  // every thread of this block has read the state
-    if (threadIdx.x == 0) {
-        const unsigned tk = atomicAdd(&st->ticket, 1u);
-        if (tk == gridDim.x - 1) {  // last block: all others took their ticket after reading the state
-            const long long ni = i > 0 ? i - 1 : 0;
-            st->i = ni;
-            st->t = t_table[ni];
-            st->history_valid = 1ull;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
-}
-static int dpmpp_check(const char* what, const void* x, const void* out, const void* hist, int B, int64_t chw, int planes) {
-    DMME_REQUIRE(x && out && hist && B > 0 && chw > 0, DMME_ERR_INVALID, "%s: bad argument", what);
-    DMME_REQUIRE(planes == 1 || planes == 2, DMME_ERR_INVALID, "%s: a network output of %d planes per image (1: eps, 2: eps and v)", what, planes);
-    DMME_REQUIRE(chw % 4 == 0, DMME_ERR_UNSUPPORTED, "%s: image size %lld is not a multiple of 4", what, (long long)chw);
-    return DMME_OK;
-}
-// row: the 8 floats of one table row, on the host.  cfg: x / out hold 2B images, history B.
-int launch_dpmpp_step(bool cfg, float* x, const float* out, float* hist, const float* row, int history_valid, int B, int64_t chw, int planes,
-                      hipStream_t s) {
-    const char* what = cfg ? "cfg_dpmpp_step" : "dpmpp_step";
-    if (int rc = dpmpp_check(what, x, out, hist, B, chw, planes)) return rc;
-    DMME_REQUIRE(row, DMME_ERR_INVALID, "%s: null argument", what);
-    const DpmppRow r = {row[0], row[1], row[2], row[3], row[4], row[5], row[6]};
-    const int64_t n4 = (int64_t)B * chw / 4;
-    const dim3 g(grid_for(n4)), b(256);
-    if (cfg)
-        hipLaunchKernelGGL(dpmpp_eager_kernel<true>, g, b, 0, s, x, out, hist, r, history_valid, chw, 1, n4);
-    else
-        hipLaunchKernelGGL(dpmpp_eager_kernel<false>, g, b, 0, s, x, out, hist, r, history_valid, chw, planes, n4);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
-int launch_chain_update_dpmpp(bool cfg, float* x, const float* out, float* hist, const float* coef, const int64_t* t_table, void* state, int B,
-                              int64_t chw, int planes, hipStream_t s) {
-    const char* what = cfg ? "chain_update_cfg_dpmpp" : "chain_update_dpmpp";
-    if (int rc = dpmpp_check(what, x, out, hist, B, chw, planes)) return rc;
-    DMME_REQUIRE(coef && t_table && state, DMME_ERR_INVALID, "%s: null argument", what);
-    const int64_t n4 = (int64_t)B * chw / 4;
-    const dim3 g(grid_for(n4)), b(256);
-    if (cfg)
-        hipLaunchKernelGGL(dpmpp_chain_kernel<true>, g, b, 0, s, x, out, hist, coef, (const long long*)t_table, (ChainState*)state, chw, 1, n4);
-    else
-        hipLaunchKernelGGL(dpmpp_chain_kernel<false>, g, b, 0, s, x, out, hist, coef, (const long long*)t_table, (ChainState*)state, chw, planes, n4);
-    DMME_CHECK_LAUNCH();
-    return DMME_OK;
-}
 
 // Label dropout of classifier-free training: out[b] = K (the null label) where u_b < p, else labels[b]; u_b = u01(word b % 4 of the quad at
 // counter offset + b / 4), the layout of a span (seed, offset, B) of the stream (dmme_hip.h).  p >= 1 drops every label (u = 1 is on the grid).

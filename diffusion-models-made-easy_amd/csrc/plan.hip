@@ -2,6 +2,7 @@
 // packed-weight layout, workspace layout, launch sequence) and the extern "C" API.
 #include "plan.h"
 
+#include <functional>
 #include <map>
 #include <mutex>
 
@@ -1551,21 +1552,37 @@ DMME_API int dmme_q_sample(const float* x0, const float* z, const float* sqrt_ab
     return launch_q_sample(x0, z, sqrt_abar, sqrt_1m_abar, t, B, chw, x_t, target, (hipStream_t)stream);
 }
 
+// ---- the reverse updates (kernels_sampler.hip): every entry point fills in the operands of its kind and calls one of two launchers
+static SamplerOperands sampler_operands(float* x, const float* out, const float* zin, int64_t B, int64_t chw, const float* grad = nullptr,
+                                        float* hist = nullptr, int planes = 1) {
+    return SamplerOperands{x, out, grad, zin, hist, chw, B * chw, (B * chw + 3) / 4, planes};
+}
+
 DMME_API int dmme_ddpm_step(float* x, const float* eps, const float* z, float inv_sqrt_alpha, float eps_coef, float sigma,
                    int add_noise, int64_t numel, void* stream) {
     DMME_REQUIRE(x && eps && (z || !add_noise), DMME_ERR_INVALID, "ddpm_step: null argument");
-    return launch_ddpm_step(x, eps, z, inv_sqrt_alpha, eps_coef, sigma, add_noise, numel, (hipStream_t)stream);
+    const float row[4] = {inv_sqrt_alpha, eps_coef, sigma, 0.f};
+    return launch_sampler_eager("ddpm_step", DMME_CHAIN_DDPM, sampler_operands(x, eps, z, 1, numel), row, add_noise, (hipStream_t)stream);
 }
 
 DMME_API int dmme_ddim_step(float* x, const float* eps, float sqrt_one_minus_abar, float sqrt_abar_prev, int64_t numel,
                    void* stream) {
     DMME_REQUIRE(x && eps, DMME_ERR_INVALID, "ddim_step: null argument");
-    return launch_ddim_step(x, eps, sqrt_one_minus_abar, sqrt_abar_prev, numel, (hipStream_t)stream);
+    const float row[4] = {sqrt_one_minus_abar, sqrt_abar_prev, 0.f, 0.f};
+    return launch_sampler_eager("ddim_step", DMME_CHAIN_DDIM, sampler_operands(x, eps, nullptr, 1, numel), row, 0, (hipStream_t)stream);
 }
 
 DMME_API int dmme_gddim_step(float* x, const float* eps, const float* z, float k0, float k1, float k2, int64_t numel, void* stream) {
     DMME_REQUIRE(x && eps && (z || k2 == 0.0f) && numel >= 0, DMME_ERR_INVALID, "gddim_step: null argument (z is needed where k2 != 0)");
-    return launch_gddim_step(x, eps, z, k0, k1, k2, numel, (hipStream_t)stream);
+    const float row[4] = {k0, k1, k2, 0.f};
+    return launch_sampler_eager("gddim_step", DMME_CHAIN_GDDIM, sampler_operands(x, eps, z, 1, numel), row, 0, (hipStream_t)stream);
+}
+
+DMME_API int dmme_iddpm_step(float* x, const float* model_out, const float* z, float inv_sqrt_alpha, float eps_coef, float log_beta,
+                             float log_beta_tilde, int add_noise, int B, int64_t chw, void* stream) {
+    DMME_REQUIRE(x && model_out && (z || !add_noise) && B > 0 && chw > 0, DMME_ERR_INVALID, "iddpm_step: bad argument");
+    const float row[4] = {inv_sqrt_alpha, eps_coef, log_beta, log_beta_tilde};
+    return launch_sampler_eager("iddpm_step", DMME_CHAIN_IDDPM, sampler_operands(x, model_out, z, B, chw), row, add_noise, (hipStream_t)stream);
 }
 
 DMME_API int dmme_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t philox_seed, uint64_t philox_offset, void* stream) {
@@ -1576,107 +1593,147 @@ DMME_API int dmme_chain_set(void* state, int64_t i, const int64_t* t_table, uint
 DMME_API int dmme_chain_update(int kind, float* x, const float* model_out, const float* step_coef, const int64_t* t_table, void* state,
                                int B, int64_t chw, void* stream) {
     DMME_REQUIRE(x && model_out && step_coef && t_table && state && B > 0 && chw > 0, DMME_ERR_INVALID, "chain_update: bad argument");
-    return launch_chain_update(kind, x, model_out, step_coef, t_table, state, B, chw, (hipStream_t)stream);
+    DMME_REQUIRE(kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_GDDIM, DMME_ERR_INVALID, "chain_update: unknown sampler kind %d", kind);
+    return launch_sampler_chain("chain_update", kind, sampler_operands(x, model_out, nullptr, B, chw), step_coef, t_table, state, (hipStream_t)stream);
 }
 
 DMME_API int dmme_chain_update_gddim(float* x, const float* model_out, const float* noise, const float* step_coef, const int64_t* t_table,
                                      void* state, int B, int64_t chw, void* stream) {
     DMME_REQUIRE(x && model_out && step_coef && t_table && state && B > 0 && chw > 0, DMME_ERR_INVALID, "chain_update_gddim: bad argument");
-    return launch_chain_update(DMME_CHAIN_GDDIM, x, model_out, step_coef, t_table, state, B, chw, (hipStream_t)stream, nullptr, noise);
+    return launch_sampler_chain("chain_update_gddim", DMME_CHAIN_GDDIM, sampler_operands(x, model_out, noise, B, chw), step_coef, t_table, state,
+                                (hipStream_t)stream);
 }
 
-DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
-                             const float* step_coef, const int64_t* t_table, void* state, void* stream) {
-    DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state, DMME_ERR_INVALID, "chain_step: null argument");
-    DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "chain_step: a class-conditional plan takes labels: call dmme_cfg_chain_step");
-    if (int rc0 = lvl_check(plan, "chain_step", (hipStream_t)stream, true)) return rc0;
-    DMME_REQUIRE(((kind >= DMME_CHAIN_DDPM && kind <= DMME_CHAIN_IDDPM) || kind == DMME_CHAIN_GDDIM) && plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
-                 "chain_step: sampler kind %d / architecture %d (guided kinds: dmme_guided_chain_step)", kind, plan->cfg.arch);
-    DMME_REQUIRE((kind == DMME_CHAIN_IDDPM) == (plan->out_channels == 2 * plan->cfg.in_channels), DMME_ERR_INVALID,
-                 "chain_step: sampler kind %d does not fit a network with %d output channels", kind, plan->out_channels);
-    // the timestep the network is evaluated at is the second word of the device-resident loop state
-    const int64_t* t_dev = (const int64_t*)state + 1;
-    int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false);
-    if (rc != DMME_OK) return rc;
-    return launch_chain_update(kind, x, model_out, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
-                               (hipStream_t)stream);
+DMME_API int dmme_chain_update_guided(int kind, float* x, const float* model_out, const float* grad, const float* noise, const float* step_coef,
+                                      const int64_t* t_table, void* state, int B, int64_t chw, void* stream) {
+    DMME_REQUIRE(x && model_out && grad && step_coef && t_table && state && B > 0 && chw > 0, DMME_ERR_INVALID, "chain_update_guided: bad argument");
+    DMME_REQUIRE(kind_grad(kind), DMME_ERR_INVALID, "chain_update_guided: kind %d is not a guided kind", kind);
+    return launch_sampler_chain("chain_update_guided", kind, sampler_operands(x, model_out, noise, B, chw, grad), step_coef, t_table, state,
+                                (hipStream_t)stream);
 }
 
-DMME_API int dmme_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, void* stream) {
-    return launch_label_dropout(labels, B, K, p, seed, offset, out, status, (hipStream_t)stream);
-}
-
+static bool kind_plain_cfg(int kind) { return kind == DMME_CHAIN_DDPM_CFG || kind == DMME_CHAIN_GDDIM_CFG; }
 DMME_API int dmme_cfg_step(int kind, float* x, const float* model_out, const float* z, float c0, float c1, float c2, float s, int add_noise, int B,
                            int64_t chw, void* stream) {
-    return launch_cfg_step(kind, x, model_out, z, c0, c1, c2, s, add_noise, B, chw, (hipStream_t)stream);
+    DMME_REQUIRE(kind_plain_cfg(kind), DMME_ERR_INVALID, "cfg_step: kind %d is not a classifier-free kind (6, 7)", kind);
+    const float row[4] = {c0, c1, c2, s};
+    return launch_sampler_eager("cfg_step", kind, sampler_operands(x, model_out, z, B, chw), row, add_noise, (hipStream_t)stream);
 }
 
 DMME_API int dmme_chain_update_cfg(int kind, float* x, const float* model_out, const float* noise, const float* step_coef, const int64_t* t_table,
                                    void* state, int B, int64_t chw, void* stream) {
-    return launch_chain_update_cfg(kind, x, model_out, noise, step_coef, t_table, state, B, chw, (hipStream_t)stream);
+    DMME_REQUIRE(kind_plain_cfg(kind), DMME_ERR_INVALID, "chain_update_cfg: kind %d is not a classifier-free kind (6, 7)", kind);
+    return launch_sampler_chain("chain_update_cfg", kind, sampler_operands(x, model_out, noise, B, chw), step_coef, t_table, state, (hipStream_t)stream);
 }
 
-// Ho & Salimans 2021 as one launch sequence: both halves in one forward at batch 2B, then the mixing update (capturable)
-DMME_API int dmme_cfg_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
-                                 int* status, int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
-    DMME_REQUIRE(plan_2B && packed && x_2B && labels_2B && model_out && workspace && step_coef && t_table && state, DMME_ERR_INVALID, "cfg_chain_step: null argument");
-    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_CFG || kind == DMME_CHAIN_GDDIM_CFG, DMME_ERR_INVALID, "cfg_chain_step: kind %d is not a classifier-free kind (6, 7)", kind);
-    DMME_REQUIRE(plan_2B->cond && plan_2B->B % 2 == 0, DMME_ERR_INVALID,
-                 "cfg_chain_step: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", plan_2B->B);
-    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
-    const int rc = unet_forward_impl(plan_2B, packed, x_2B, t_dev, 1, model_out, workspace, nullptr, stream, false, labels_2B, status);
-    if (rc != DMME_OK) return rc;
-    return launch_chain_update_cfg(kind, x_2B, model_out, nullptr, step_coef, t_table, state, plan_2B->B / 2,
-                                   (int64_t)plan_2B->cfg.in_channels * plan_2B->H * plan_2B->W, (hipStream_t)stream);
-}
-
-// ---- DPM-Solver++(2M): kinds DMME_CHAIN_DPMPP / DMME_CHAIN_DPMPP_CFG, tables of 8 floats per index, a history buffer (kernels_sampler.hip)
+// DPM-Solver++(2M): kinds DMME_CHAIN_DPMPP / DMME_CHAIN_DPMPP_CFG, tables of 8 floats per index, a history buffer
 DMME_API int dmme_dpmpp_step(float* x, const float* model_out, float* history, const float* row, int history_valid, int B, int64_t chw, int out_planes,
                              void* stream) {
-    return launch_dpmpp_step(false, x, model_out, history, row, history_valid, B, chw, out_planes, (hipStream_t)stream);
+    return launch_sampler_eager("dpmpp_step", DMME_CHAIN_DPMPP, sampler_operands(x, model_out, nullptr, B, chw, nullptr, history, out_planes), row,
+                                history_valid, (hipStream_t)stream);
 }
 
 DMME_API int dmme_chain_update_dpmpp(float* x, const float* model_out, float* history, const float* step_coef, const int64_t* t_table, void* state, int B,
                                      int64_t chw, int out_planes, void* stream) {
-    return launch_chain_update_dpmpp(false, x, model_out, history, step_coef, t_table, state, B, chw, out_planes, (hipStream_t)stream);
-}
-
-DMME_API int dmme_dpmpp_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, float* history,
-                                   const float* step_coef, const int64_t* t_table, void* state, void* stream) {
-    DMME_REQUIRE(plan && packed && x && model_out && workspace && history && step_coef && t_table && state, DMME_ERR_INVALID, "dpmpp_chain_step: null argument");
-    DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "dpmpp_chain_step: a class-conditional plan takes labels: call dmme_cfg_dpmpp_chain_step");
-    DMME_REQUIRE(plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID, "dpmpp_chain_step: architecture %d predicts no noise", plan->cfg.arch);
-    const int planes = plan->out_channels / plan->cfg.in_channels;
-    DMME_REQUIRE(plan->out_channels == planes * plan->cfg.in_channels && (planes == 1 || planes == 2), DMME_ERR_INVALID,
-                 "dpmpp_chain_step: a network with %d output channels for %d input channels", plan->out_channels, plan->cfg.in_channels);
-    if (int rc0 = lvl_check(plan, "dpmpp_chain_step", (hipStream_t)stream, true)) return rc0;
-    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
-    const int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false);
-    if (rc != DMME_OK) return rc;
-    return launch_chain_update_dpmpp(false, x, model_out, history, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
-                                     planes, (hipStream_t)stream);
+    return launch_sampler_chain("chain_update_dpmpp", DMME_CHAIN_DPMPP, sampler_operands(x, model_out, nullptr, B, chw, nullptr, history, out_planes),
+                                step_coef, t_table, state, (hipStream_t)stream);
 }
 
 DMME_API int dmme_cfg_dpmpp_step(float* x_2B, const float* model_out, float* history, const float* row, int history_valid, int B, int64_t chw, void* stream) {
-    return launch_dpmpp_step(true, x_2B, model_out, history, row, history_valid, B, chw, 1, (hipStream_t)stream);
+    return launch_sampler_eager("cfg_dpmpp_step", DMME_CHAIN_DPMPP_CFG, sampler_operands(x_2B, model_out, nullptr, B, chw, nullptr, history), row, history_valid,
+                                (hipStream_t)stream);
 }
 
 DMME_API int dmme_chain_update_cfg_dpmpp(float* x_2B, const float* model_out, float* history, const float* step_coef, const int64_t* t_table, void* state,
                                          int B, int64_t chw, void* stream) {
-    return launch_chain_update_dpmpp(true, x_2B, model_out, history, step_coef, t_table, state, B, chw, 1, (hipStream_t)stream);
+    return launch_sampler_chain("chain_update_cfg_dpmpp", DMME_CHAIN_DPMPP_CFG, sampler_operands(x_2B, model_out, nullptr, B, chw, nullptr, history), step_coef,
+                                t_table, state, (hipStream_t)stream);
+}
+
+// One capturable step of any kind: the checks of plan against kind, the network's no-grad forward at the device-resident t (the loop
+// state's second word), `between` (the guided kinds' classifier pass, which fills the gradient operand), the update.  A classifier-free kind
+// runs a class-conditional plan of batch 2B with labels (conditional half, unconditional half) and updates at B = plan batch / 2.
+// The forward looks at the level engine's status word itself, under the name unet_forward; the unconditional entry points have always
+// looked first under their own name, and still do.
+static int chain_step_common(const char* what, const dmme_plan* plan, const void* packed, float* x, const int64_t* labels, int* status, float* model_out,
+                             void* workspace, int kind, const float* grad, float* hist, const float* step_coef, const int64_t* t_table, void* state,
+                             void* stream, const std::function<int()>& between = nullptr) {
+    const bool cfg = kind_cfg(kind);
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state && (labels || !cfg) && (hist || !kind_hist(kind)),
+                 DMME_ERR_INVALID, "%s: null argument", what);
+    if (cfg)
+        DMME_REQUIRE(plan->cond && plan->B % 2 == 0, DMME_ERR_INVALID,
+                     "%s: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", what, plan->B);
+    else
+        DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "%s: a class-conditional plan takes labels: call dmme_cfg_chain_step / dmme_cfg_dpmpp_chain_step", what);
+    DMME_REQUIRE(plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID, "%s: architecture %d predicts no noise", what, plan->cfg.arch);
+    const int planes = plan->out_channels / plan->cfg.in_channels;
+    DMME_REQUIRE(plan->out_channels == planes * plan->cfg.in_channels && (kind_planes(kind) ? planes == kind_planes(kind) : planes == 1 || planes == 2),
+                 DMME_ERR_INVALID, "%s: sampler kind %d does not fit a network with %d output channels for %d input channels", what, kind, plan->out_channels,
+                 plan->cfg.in_channels);
+    if (!cfg)
+        if (int rc = lvl_check(plan, what, (hipStream_t)stream, true)) return rc;
+    const int64_t* t_dev = (const int64_t*)state + 1;
+    if (int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false, labels, status)) return rc;
+    if (between)
+        if (int rc = between()) return rc;
+    return launch_sampler_chain(what, kind, sampler_operands(x, model_out, nullptr, cfg ? plan->B / 2 : plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
+                                                             grad, hist, planes),
+                                step_coef, t_table, state, (hipStream_t)stream);
+}
+
+DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
+                             const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(kind_known(kind) && !kind_cfg(kind) && !kind_grad(kind) && !kind_hist(kind), DMME_ERR_INVALID,
+                 "chain_step: sampler kind %d (guided kinds: dmme_guided_chain_step, and so on)", kind);
+    return chain_step_common("chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, kind, nullptr, nullptr, step_coef, t_table, state, stream);
+}
+
+// Ho & Salimans 2021 as one launch sequence: both halves in one forward at batch 2B, then the mixing update
+DMME_API int dmme_cfg_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
+                                 int* status, int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(kind_plain_cfg(kind), DMME_ERR_INVALID, "cfg_chain_step: kind %d is not a classifier-free kind (6, 7)", kind);
+    return chain_step_common("cfg_chain_step", plan_2B, packed, x_2B, labels_2B, status, model_out, workspace, kind, nullptr, nullptr, step_coef, t_table, state,
+                             stream);
+}
+
+DMME_API int dmme_dpmpp_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, float* history,
+                                   const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    return chain_step_common("dpmpp_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_DPMPP, nullptr, history, step_coef, t_table,
+                             state, stream);
 }
 
 DMME_API int dmme_cfg_dpmpp_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
                                        int* status, float* history, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
-    DMME_REQUIRE(plan_2B && packed && x_2B && labels_2B && model_out && workspace && history && step_coef && t_table && state, DMME_ERR_INVALID,
-                 "cfg_dpmpp_chain_step: null argument");
-    DMME_REQUIRE(plan_2B->cond && plan_2B->B % 2 == 0, DMME_ERR_INVALID,
-                 "cfg_dpmpp_chain_step: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", plan_2B->B);
-    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
-    const int rc = unet_forward_impl(plan_2B, packed, x_2B, t_dev, 1, model_out, workspace, nullptr, stream, false, labels_2B, status);
-    if (rc != DMME_OK) return rc;
-    return launch_chain_update_dpmpp(true, x_2B, model_out, history, step_coef, t_table, state, plan_2B->B / 2,
-                                     (int64_t)plan_2B->cfg.in_channels * plan_2B->H * plan_2B->W, 1, (hipStream_t)stream);
+    return chain_step_common("cfg_dpmpp_chain_step", plan_2B, packed, x_2B, labels_2B, status, model_out, workspace, DMME_CHAIN_DPMPP_CFG, nullptr, history,
+                             step_coef, t_table, state, stream);
+}
+
+// Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM): between the forward and the update, the classifier's forward, the log-softmax
+// gradient and the input-only backward leave d log p(y | x_t, t) / d x_t in `grad`
+DMME_API int dmme_guided_chain_step(const dmme_plan* plan, const void* packed, const dmme_plan* cls, const void* cls_packed,
+                                    const void* cls_packed_bwd, float* x, float* model_out, void* workspace, void* cls_workspace,
+                                    void* cls_bwd_workspace, const int64_t* y, float* logits, float* d_logits, float* grad, int* status,
+                                    int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && cls && cls_packed && cls_packed_bwd && x && model_out && workspace && cls_workspace && cls_bwd_workspace && y &&
+                 logits && d_logits && grad && step_coef && t_table && state, DMME_ERR_INVALID, "guided_chain_step: null argument");
+    DMME_REQUIRE(kind_grad(kind), DMME_ERR_INVALID, "guided_chain_step: kind %d is not a guided kind", kind);
+    DMME_REQUIRE(plan->cfg.arch == DMME_ARCH_DDPM && !plan->cond && cls->cfg.arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
+                 "guided_chain_step: needs a DDPM UNet plan and a classifier plan (got architectures %d, %d)", plan->cfg.arch, cls->cfg.arch);
+    DMME_REQUIRE(plan->B == cls->B && plan->H == cls->H && plan->W == cls->W && plan->cfg.in_channels == cls->cfg.in_channels, DMME_ERR_INVALID,
+                 "guided_chain_step: the UNet plan (B=%d %dx%d) and the classifier plan (B=%d %dx%d) differ", plan->B, plan->H, plan->W, cls->B, cls->H, cls->W);
+    const int64_t* t_dev = (const int64_t*)state + 1;
+    return chain_step_common("guided_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, kind, grad, nullptr, step_coef, t_table, state, stream, [&] {
+        int rc = unet_forward_impl(cls, cls_packed, x, t_dev, 1, logits, cls_workspace, nullptr, stream, true);
+        if (rc == DMME_OK) rc = launch_log_softmax_grad(logits, y, cls->B, cls->out_channels, 1, 1.0f, nullptr, d_logits, status, (hipStream_t)stream);
+        if (rc == DMME_OK)
+            rc = dmme_unet_backward_input(cls, cls_packed, cls_packed_bwd, x, t_dev, 1, d_logits, cls_workspace, cls_bwd_workspace, nullptr, grad, stream);
+        return rc;
+    });
+}
+
+DMME_API int dmme_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, void* stream) {
+    return launch_label_dropout(labels, B, K, p, seed, offset, out, status, (hipStream_t)stream);
 }
 
 // The two launches of dmme_slerp hand three partial sums per (image, block) from one to the other.  The entry point takes no scratch
@@ -1711,47 +1768,10 @@ DMME_API int dmme_log_softmax_grad(const float* logits, const int64_t* y, int B,
     return launch_log_softmax_grad(logits, y, B, K, mode, scale, loss, d_logits, status, (hipStream_t)stream);
 }
 
-DMME_API int dmme_chain_update_guided(int kind, float* x, const float* model_out, const float* grad, const float* noise, const float* step_coef,
-                                      const int64_t* t_table, void* state, int B, int64_t chw, void* stream) {
-    DMME_REQUIRE(x && model_out && grad && step_coef && t_table && state && B > 0 && chw > 0, DMME_ERR_INVALID, "chain_update_guided: bad argument");
-    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED, DMME_ERR_INVALID, "chain_update_guided: kind %d is not a guided kind", kind);
-    return launch_chain_update(kind, x, model_out, step_coef, t_table, state, B, chw, (hipStream_t)stream, grad, noise);
-}
-
-// Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM) as one launch sequence with every per-step value device-resident (capturable)
-DMME_API int dmme_guided_chain_step(const dmme_plan* plan, const void* packed, const dmme_plan* cls, const void* cls_packed,
-                                    const void* cls_packed_bwd, float* x, float* model_out, void* workspace, void* cls_workspace,
-                                    void* cls_bwd_workspace, const int64_t* y, float* logits, float* d_logits, float* grad, int* status,
-                                    int kind, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
-    DMME_REQUIRE(plan && packed && cls && cls_packed && cls_packed_bwd && x && model_out && workspace && cls_workspace && cls_bwd_workspace && y &&
-                 logits && d_logits && grad && step_coef && t_table && state, DMME_ERR_INVALID, "guided_chain_step: null argument");
-    DMME_REQUIRE(kind == DMME_CHAIN_DDPM_GUIDED || kind == DMME_CHAIN_DDIM_GUIDED, DMME_ERR_INVALID, "guided_chain_step: kind %d is not a guided kind", kind);
-    DMME_REQUIRE(plan->cfg.arch == DMME_ARCH_DDPM && !plan->cond && cls->cfg.arch == DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID,
-                 "guided_chain_step: needs a DDPM UNet plan and a classifier plan (got architectures %d, %d)", plan->cfg.arch, cls->cfg.arch);
-    DMME_REQUIRE(plan->B == cls->B && plan->H == cls->H && plan->W == cls->W && plan->cfg.in_channels == cls->cfg.in_channels, DMME_ERR_INVALID,
-                 "guided_chain_step: the UNet plan (B=%d %dx%d) and the classifier plan (B=%d %dx%d) differ", plan->B, plan->H, plan->W, cls->B, cls->H, cls->W);
-    if (int rc0 = lvl_check(plan, "guided_chain_step", (hipStream_t)stream, true)) return rc0;
-    const int64_t* t_dev = (const int64_t*)state + 1;  // the loop state's second word: t
-    int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false);
-    if (rc == DMME_OK) rc = unet_forward_impl(cls, cls_packed, x, t_dev, 1, logits, cls_workspace, nullptr, stream, true);
-    if (rc == DMME_OK) rc = launch_log_softmax_grad(logits, y, cls->B, cls->out_channels, 1, 1.0f, nullptr, d_logits, status, (hipStream_t)stream);
-    if (rc == DMME_OK)
-        rc = dmme_unet_backward_input(cls, cls_packed, cls_packed_bwd, x, t_dev, 1, d_logits, cls_workspace, cls_bwd_workspace, nullptr, grad, stream);
-    if (rc != DMME_OK) return rc;
-    return launch_chain_update(kind, x, model_out, step_coef, t_table, state, plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
-                               (hipStream_t)stream, grad, nullptr);
-}
-
 DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64_t* idx, const uint8_t* flip, int B, int C, int H, int W,
                               float* out, void* stream) {
     DMME_REQUIRE(data && idx && out && n_images > 0 && B > 0 && C > 0 && H > 0 && W > 0, DMME_ERR_INVALID, "image_batch: bad argument");
     return launch_image_batch(data, idx, flip, B, C, H, W, out, (hipStream_t)stream);
-}
-
-DMME_API int dmme_iddpm_step(float* x, const float* model_out, const float* z, float inv_sqrt_alpha, float eps_coef, float log_beta,
-                             float log_beta_tilde, int add_noise, int B, int64_t chw, void* stream) {
-    DMME_REQUIRE(x && model_out && (z || !add_noise) && B > 0 && chw > 0, DMME_ERR_INVALID, "iddpm_step: bad argument");
-    return launch_iddpm_step(x, model_out, z, inv_sqrt_alpha, eps_coef, log_beta, log_beta_tilde, add_noise, B, chw, (hipStream_t)stream);
 }
 
 DMME_API int dmme_iddpm_loss(const float* model_out, const float* x_t, const float* x_0, const float* target, const int64_t* t,

@@ -40,6 +40,17 @@ class ChainTables:
         _lib.check(_lib.lib().dmme_chain_set(_lib.ptr(self.state), int(i), _lib.ptr(self.ttab), seed & 0xFFFFFFFFFFFFFFFF, int(offset), _lib.stream_ptr()), "dmme_chain_set")
 
 
+def chain_draws(kind: int, rows) -> bool:
+    """does a chain of this kind over these table rows consume normals?  The host's statement of the kernels' noise rule (csrc/common.h:
+    kind_noise): the shipped DDIM kinds and DPM-Solver++ never do, the paper-form DDIM kinds only with a non-zero k2 somewhere, every kind
+    with a DDPM mean does.  A chain that draws nothing leaves torch's generator where the eager loop leaves it."""
+    if kind in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED, _lib.CHAIN_DPMPP, _lib.CHAIN_DPMPP_CFG):
+        return False
+    if kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_GDDIM_CFG):
+        return any(r[2] != 0.0 for r in rows)
+    return True
+
+
 class ChainRunner(ChainTables):
     """One replayable denoising step on a fixed image buffer (include/dmme_hip.h: dmme_chain_*).
 
@@ -58,8 +69,7 @@ class ChainRunner(ChainTables):
         self.process, self.model, self.x = process, model, x
         self.plan = model._plan_for(B, H, W, x.device)
         self.kind, (n, rows, ttab) = spec if spec is not None else (process._chain_kind, process._chain_tables())
-        # does the update consume normals?  (the shipped DDIM kinds never do; the paper-form kind only with a non-zero k2 somewhere)
-        self.draws = self.kind not in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED) and (self.kind != _lib.CHAIN_GDDIM or any(r[2] != 0.0 for r in rows))
+        self.draws = chain_draws(self.kind, rows)
         self.n_steps = n
         super().__init__(rows, ttab, x.device)
         self.out = torch.empty((B, model.out_channels, H, W), dtype=torch.float32, device=x.device)
@@ -131,10 +141,7 @@ class ChainRunner(ChainTables):
 
     def run(self, first: int, count: int):
         """`count` steps from loop index `first` downwards, drawing from torch's CUDA generator like the eager loop"""
-        if not self.draws:  # a chain that draws nothing: torch's generator stays where the eager loop leaves it
-            seed, off = 0, 0
-        else:
-            seed, off = philox_reserve(self.x.device, self.noise_numel * count)
+        seed, off = philox_reserve(self.x.device, self.noise_numel * count) if self.draws else (0, 0)
         self.set(first, seed, off)
         for _ in range(count):
             self.step()
@@ -239,7 +246,8 @@ class DDPM(nn.Module):
         if runner is None:
             return None
         runner.x.copy_(x_t)
-        # (the paper-form DDIM kind at eta = 0 and the DPM-Solver++ kind reserve nothing, like their eager steps; every other kind keeps reserving one span per call)
+        # (the paper-form DDIM kind at eta = 0 and the DPM-Solver++ kind reserve nothing, like their eager steps; every other kind keeps reserving one span per call,
+        # the shipped DDIM kinds included, which draw nothing either)
         seed, off = (0, 0) if runner.kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_DPMPP) and not runner.draws else philox_reserve(x_t.device, x_t.numel())
         runner.set(index, seed, off)
         with torch.no_grad():

@@ -87,7 +87,6 @@ class DPMChainRunner(ChainRunner):
 
     def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         super().__init__(process, x, use_graph, spec)
-        self.draws = False  # the solver is deterministic: torch's generator stays where the eager loop leaves it
         self.hist = torch.empty_like(x)
 
     def _carried(self):

@@ -52,7 +52,6 @@ class CFGChainRunner(ChainRunner):
             raise ValueError("CFGChainRunner: the image buffer holds 2B images")
         super().__init__(process, x, use_graph, (kind, tables))
         self.dpmpp = _BASE_KIND.get(kind, kind) == _lib.CHAIN_DPMPP
-        self.draws = not self.dpmpp and (_BASE_KIND.get(kind, kind) == _lib.CHAIN_DDPM or any(r[2] != 0.0 for r in tables[1]))
         self.images = x.shape[0] // 2 if self.batched else x.shape[0]
         self.hist = torch.empty_like(x[:self.images]) if self.dpmpp else None
         self.noise_numel = self.images * x[0].numel()  # the normals of ONE half: what an unguided chain at batch B draws

@@ -81,6 +81,50 @@ def test_chain_update_bit_exact_vs_eager_kernels_and_state_advance(kind):
             assert ttab[i] == 1  # the next update runs the t == 1 branch
 
 
+@pytest.mark.parametrize("shape", [(3, 3, 16, 16), (1, 3, 4, 4)])  # 576 quads: three blocks take tickets; 12 quads: one partial block
+@pytest.mark.parametrize("kind", range(10))  # DMME_CHAIN_DDPM .. DMME_CHAIN_DPMPP_CFG
+def test_state_advance_of_every_kind(kind, shape):
+    """The loop state after each of three updates from index 2 of a 3-row table, through the chain-update entry point of every kind
+    (shapes are those of ONE half for the classifier-free kinds): i = 1, 0, 0 (clamped), t = t_table[i], the Philox offset moved by
+    B*chw/4 per update (not at all by the DPM-Solver++ kinds, which draw nothing), seed kept, ticket back to 0, the sixth word 0 except
+    for the DPM-Solver++ kinds, which find it 0 and leave it 1, the reserved words untouched."""
+    from dmme_amd import _lib
+
+    lib = _lib.lib()
+    cfg, dpmpp, guided = kind in (_lib.CHAIN_DDPM_CFG, _lib.CHAIN_GDDIM_CFG, _lib.CHAIN_DPMPP_CFG), kind in (_lib.CHAIN_DPMPP, _lib.CHAIN_DPMPP_CFG), kind in (3, 4)
+    B, C, H, W = shape
+    chw, halves, planes = C * H * W, 2 if cfg else 1, 2 if kind == _lib.CHAIN_IDDPM else 1
+    x = synth.normal(1, (halves * B, C, H, W)).cuda()
+    out = synth.normal(2, (halves * B, planes * C, H, W)).cuda()
+    extra = synth.normal(3, shape).cuda()  # the guided kinds' gradient, the DPM-Solver++ kinds' history
+    row = [1.1, -0.4, 0.7, 0.3, 0.5, 0.0, 1.5, 0.0] if dpmpp else [0.9, 0.3, 0.2, 0.5]  # (c2 != 0: the paper-form kinds draw)
+    coef = torch.tensor([[v * (1.0 + 0.1 * i) for v in row] for i in range(3)], dtype=torch.float32).reshape(-1).cuda()
+    ttab = [7, 1, 5]  # distinct; index 1 is the t == 1 step of the kinds with a DDPM mean
+    tt = torch.tensor(ttab, dtype=torch.int64).cuda()
+    seed, off, reserved = 0xC0FFEE, 1000, [0x1111111111111111, -0x2222222222222222]
+    state = torch.tensor([0] * 6 + reserved, dtype=torch.int64).cuda()
+    _lib.check(lib.dmme_chain_set(_lib.ptr(state), 2, _lib.ptr(tt), seed, off, _lib.stream_ptr()))
+    assert state.cpu().tolist() == [2, ttab[2], off, seed, 0, 0] + reserved
+    tail = (_lib.ptr(coef), _lib.ptr(tt), _lib.ptr(state), B, chw)
+    for step, i in enumerate((1, 0, 0), 1):
+        if kind == _lib.CHAIN_DPMPP:
+            rc = lib.dmme_chain_update_dpmpp(_lib.ptr(x), _lib.ptr(out), _lib.ptr(extra), *tail, 1, _lib.stream_ptr())
+        elif kind == _lib.CHAIN_DPMPP_CFG:
+            rc = lib.dmme_chain_update_cfg_dpmpp(_lib.ptr(x), _lib.ptr(out), _lib.ptr(extra), *tail, _lib.stream_ptr())
+        elif cfg:
+            rc = lib.dmme_chain_update_cfg(kind, _lib.ptr(x), _lib.ptr(out), None, *tail, _lib.stream_ptr())
+        elif guided:
+            rc = lib.dmme_chain_update_guided(kind, _lib.ptr(x), _lib.ptr(out), _lib.ptr(extra), None, *tail, _lib.stream_ptr())
+        elif kind == _lib.CHAIN_GDDIM:
+            rc = lib.dmme_chain_update_gddim(_lib.ptr(x), _lib.ptr(out), None, *tail, _lib.stream_ptr())
+        else:
+            rc = lib.dmme_chain_update(kind, _lib.ptr(x), _lib.ptr(out), *tail, _lib.stream_ptr())
+        _lib.check(rc)
+        torch.cuda.synchronize()
+        want = [i, ttab[i], off + (0 if dpmpp else step * (B * chw // 4)), seed, 0, 1 if dpmpp else 0] + reserved
+        assert state.cpu().tolist() == want, f"kind {kind}: state after update {step}"
+
+
 # ------------------------------------------------------------------------------------------ the eager kernels' ragged tail
 GUARD = 1.0e30  # what lies behind x's last element, before and after the call
 
