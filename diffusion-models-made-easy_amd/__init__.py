@@ -11,6 +11,7 @@ from .common.norm import denorm, norm  # noqa: F401
 from . import models, diffusion_models, equations, lit_modules, lr_scheduler, data_modules  # noqa: F401
 from .data_modules import CIFAR10  # noqa: F401
 from .diffusion_models import DDPM, DDIM, IDDPM, GeneralizedDDIM, DPMSolverPP  # noqa: F401
+from .diffusion_models import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401
 from .lit_modules import LitDDPM, LitDDIM, LitIDDPM, LitClassifierFreeDDPM  # noqa: F401
 from .models.ddpm import UNet  # noqa: F401
 from .models.cond import ConditionalUNet  # noqa: F401
@@ -19,4 +20,5 @@ from .guidance import EncoderClassifier, ClassifierGuidedDDPM, ClassifierGuidedD
 from .guidance import ClassifierFreeDDPM, ClassifierFreeDDIM, ClassifierFreeDPMSolver  # noqa: F401
 
 __all__ = ["gaussian", "gaussian_like", "uniform_int", "pad", "denorm", "norm", "UNet", "DDPM", "DDIM", "LitDDPM", "LitDDIM", "IDDPM", "LitIDDPM", "CIFAR10", "GeneralizedDDIM",
-           "ConditionalUNet", "ClassifierFreeDDPM", "ClassifierFreeDDIM", "LitClassifierFreeDDPM", "DPMSolverPP", "ClassifierFreeDPMSolver"]
+           "ConditionalUNet", "ClassifierFreeDDPM", "ClassifierFreeDDIM", "LitClassifierFreeDDPM", "DPMSolverPP", "ClassifierFreeDPMSolver",
+           "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows"]

@@ -19,6 +19,7 @@ F32, BF16, BF16X3, F16 = 0, 1, 2, 3  # BF16X3: fp32 buffers, three-pass bf16 MFM
 CHAIN_DDPM, CHAIN_DDIM, CHAIN_IDDPM, CHAIN_DDPM_GUIDED, CHAIN_DDIM_GUIDED, CHAIN_GDDIM = 0, 1, 2, 3, 4, 5
 CHAIN_DDPM_CFG, CHAIN_GDDIM_CFG = 6, 7  # classifier-free guidance: both halves of a 2B batch mixed, then the DDPM / paper-form DDIM update
 CHAIN_DPMPP, CHAIN_DPMPP_CFG = 8, 9  # DPM-Solver++(2M): tables of 8 floats per index, a history buffer, entry points of their own
+CHAIN_REPAINT = 10  # RePaint / SDEdit: tables of 8 floats per index, the known image and its mask, three normal streams per step
 ARCH_DDPM, ARCH_IDDPM, ARCH_CLASSIFIER, ARCH_DDPM_COND = 0, 1, 2, 3
 DTYPES = {"fp32": F32, "float32": F32, "32": F32, "bf16": BF16, "bfloat16": BF16, "16": BF16, "bf16-mixed": BF16, "16-mixed": BF16,
           "bf16x3": BF16X3, "fp16": F16, "float16": F16, "half": F16, "fp16r32": F16R32}
@@ -102,6 +103,9 @@ PROTOTYPES = {
     "dmme_cfg_dpmpp_step": (_i, [_vp, _vp, _vp, C.POINTER(_f), _i, _i, _i64, _vp]),
     "dmme_chain_update_cfg_dpmpp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "dmme_cfg_dpmpp_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_repaint_step": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i64, _i, _vp]),
+    "dmme_chain_update_repaint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp]),
+    "dmme_repaint_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmme_unet_plan_num_ops": (_i, [_vp]),
     "dmme_unet_plan_level_info": (_i, [_vp, C.c_char_p, _i]),
     "dmme_unet_plan_check": (_i, [_vp]),

@@ -436,7 +436,7 @@ int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t se
 
 // ---- the reverse update: one description of a sampler kind (DMME_CHAIN_*, dmme_hip.h), read at compile time by the two update kernels
 // (kernels_sampler.hip) and at run time by the argument checks of their launchers and of the capturable steps (plan.hip)
-constexpr bool kind_known(int k) { return k >= DMME_CHAIN_DDPM && k <= DMME_CHAIN_DPMPP_CFG; }
+constexpr bool kind_known(int k) { return k >= DMME_CHAIN_DDPM && k <= DMME_CHAIN_REPAINT; }
 // x and the network output hold two halves (conditional, unconditional), mixed by s = row[kind_scol]; sizes are those of ONE half
 constexpr bool kind_cfg(int k) { return k == DMME_CHAIN_DDPM_CFG || k == DMME_CHAIN_GDDIM_CFG || k == DMME_CHAIN_DPMPP_CFG; }
 // the element arithmetic: sampler_update<kind_base> of a kind in [DDPM, GDDIM], or dpmpp_update
@@ -445,20 +445,30 @@ constexpr int kind_base(int k) {
 }
 // DPM-Solver++: a history buffer that the update reads and rewrites, and whose flag the state advance raises; nothing drawn, so the Philox offset stays
 constexpr bool kind_hist(int k) { return kind_base(k) == DMME_CHAIN_DPMPP; }
-constexpr int kind_row(int k) { return kind_hist(k) ? 8 : 4; }  // floats per table row
+// RePaint / SDEdit: the update also reads the known image and its mask, and one row carries a reverse step, the known pixels' noising and
+// the forward jump that follows (dmme_hip.h: dmme_repaint_step)
+constexpr bool kind_paint(int k) { return k == DMME_CHAIN_REPAINT; }
+constexpr int kind_row(int k) { return kind_hist(k) || kind_paint(k) ? 8 : 4; }  // floats per table row
 constexpr int kind_scol(int k) { return kind_hist(k) ? 6 : 3; }
 constexpr bool kind_grad(int k) { return k == DMME_CHAIN_DDPM_GUIDED || k == DMME_CHAIN_DDIM_GUIDED; }  // takes d log p(y | x_t, t) / d x_t
 // chw-sized planes per image of the network output, the predicted noise in the first: 1, 2 (IDDPM: eps, v), 0 = either, given at run time
-constexpr int kind_planes(int k) { return k == DMME_CHAIN_IDDPM ? 2 : k == DMME_CHAIN_DPMPP ? 0 : 1; }
-// when a step adds noise: never (the shipped DDIM kinds, the solver), where t != 1 (the DDPM means), where c2 != 0 (the paper-form DDIM kinds)
-enum { NOISE_NEVER, NOISE_NOT_LAST, NOISE_C2 };
+constexpr int kind_planes(int k) { return k == DMME_CHAIN_IDDPM ? 2 : k == DMME_CHAIN_DPMPP || kind_paint(k) ? 0 : 1; }
+// when a step adds noise: never (the shipped DDIM kinds, the solver), where t != 1 (the DDPM means), where c2 != 0 (the paper-form DDIM kinds),
+// or stream by stream where the row's coefficient of that stream is not zero (RePaint: c2, ks, r1)
+enum { NOISE_NEVER, NOISE_NOT_LAST, NOISE_C2, NOISE_ROW };
 constexpr int kind_noise(int k) {
-    return kind_hist(k) || k == DMME_CHAIN_DDIM || k == DMME_CHAIN_DDIM_GUIDED ? NOISE_NEVER : kind_base(k) == DMME_CHAIN_GDDIM ? NOISE_C2 : NOISE_NOT_LAST;
+    return kind_paint(k) ? NOISE_ROW : kind_hist(k) || k == DMME_CHAIN_DDIM || k == DMME_CHAIN_DDIM_GUIDED ? NOISE_NEVER : kind_base(k) == DMME_CHAIN_GDDIM ? NOISE_C2 : NOISE_NOT_LAST;
 }
 // not_last: t != 1 (the chain kernel), the caller's add_noise (the eager entry points)
 constexpr int kind_adds_noise(int k, float c2, int not_last) { return kind_noise(k) == NOISE_C2 ? c2 != 0.0f : kind_noise(k) == NOISE_NOT_LAST ? not_last : 0; }
+// NOISE_ROW: the step's flag is a mask, bit s set where the row uses normal stream s
+constexpr int paint_streams_used(float c2, float ks, float r1) { return (c2 != 0.0f ? 1 : 0) | (ks != 0.0f ? 2 : 0) | (r1 != 0.0f ? 4 : 0); }
+// normal streams of numel values each that one step owns: stream s of quad q sits at Philox counter offset + s n4 + q, and a chain's offset
+// moves by kind_streams n4 per step whether or not the step used them
+constexpr int kind_streams(int k) { return kind_paint(k) ? 3 : 1; }
+constexpr bool kind_draws(int k, int flag, int s) { return kind_paint(k) ? ((flag >> s) & 1) != 0 : kind_noise(k) != NOISE_NEVER && flag != 0; }
 // the chain form accepts normals from memory in place of the drawn ones (tests)
-constexpr bool kind_zin(int k) { return k == DMME_CHAIN_DDPM_GUIDED || kind_base(k) == DMME_CHAIN_GDDIM || k == DMME_CHAIN_DDPM_CFG; }
+constexpr bool kind_zin(int k) { return k == DMME_CHAIN_DDPM_GUIDED || kind_base(k) == DMME_CHAIN_GDDIM || k == DMME_CHAIN_DDPM_CFG || kind_paint(k); }
 // the eager form takes any numel (and IDDPM any chw), element by element where a quad does not fit; every other form needs chw % 4 == 0
 constexpr bool kind_ragged(int k) { return k == DMME_CHAIN_DDPM || k == DMME_CHAIN_DDIM || k == DMME_CHAIN_GDDIM || k == DMME_CHAIN_IDDPM; }
 
@@ -467,12 +477,14 @@ struct SamplerOperands {
     float* x;
     const float* out;   // the network output
     const float* grad;  // kind_grad
-    const float* zin;   // normals: the eager form's z, the chain form's override
+    const float* zin;   // normals, [kind_streams][numel]: the eager form's z, the chain form's override
     float* hist;        // kind_hist
+    const float* known; // kind_paint: the image whose pixels are kept, and how much of each (1: known, 0: generated), both in x's layout
+    const float* mask;
     int64_t chw, numel, n4;
     int planes;         // read where kind_planes is 0
 };
-// row: kind_row host floats; flag: add_noise, or history_valid (kind_hist).  The guided kinds have no eager form.
+// row: kind_row host floats; flag: add_noise, or history_valid (kind_hist); ignored where the row decides (NOISE_C2, NOISE_ROW).  The guided kinds have no eager form.
 int launch_sampler_eager(const char* what, int kind, const SamplerOperands& o, const float* row, int flag, hipStream_t s);
 int launch_sampler_chain(const char* what, int kind, const SamplerOperands& o, const float* coef, const int64_t* t_table, void* state, hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);

@@ -167,6 +167,21 @@ __device__ __forceinline__ float dpmpp_update(float x, float e, float prev, cons
     const float d = valid ? __fadd_rn(x0, __fmul_rn(r.w, __fsub_rn(x0, prev))) : x0;
     return __fadd_rn(__fmul_rn(r.k0, x), __fmul_rn(r.k1, d));
 }
+// RePaint (Lugmayr et al. 2022) / SDEdit: one row is a reverse step a -> b, the known image noised to level b, the two blended by the mask,
+// and the forward jump b -> c that the walk takes next, folded into one Gaussian.  Per loop index, 8 floats:
+//   {c0 = 1/sqrt(alpha), c1 = beta/sqrt(1-abar_a), c2 = sqrt(beta), ka = sqrt(abar_b), ks = sqrt(1-abar_b), r0 = sqrt(abar_c/abar_b), r1 = sqrt(1-abar_c/abar_b), -}
+//   u = c0 (x - c1 e) [+ c2 z0];  k = ka x0 [+ ks z1];  y = m k + (1 - m) u;  x' = y, or r0 y + r1 z2: each bracket only where its bit of `used` is set
+struct PaintRow {
+    float c0, c1, c2, ka, ks, r0, r1;
+};
+__device__ __forceinline__ float paint_update(float x, float e, float x0, float m, float z0, float z1, float z2, const PaintRow& r, int used) {
+    float u = ddpm_mean(x, e, r.c0, r.c1);
+    if (used & 1) u = __fadd_rn(u, __fmul_rn(r.c2, z0));
+    float k = __fmul_rn(r.ka, x0);
+    if (used & 2) k = __fadd_rn(k, __fmul_rn(r.ks, z1));
+    const float y = __fadd_rn(__fmul_rn(m, k), __fmul_rn(__fsub_rn(1.0f, m), u));
+    return used & 4 ? __fadd_rn(__fmul_rn(r.r0, y), __fmul_rn(r.r1, z2)) : y;
+}
 __device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // ---- the layer around the arithmetic.  A kind is described once (kind_*, common.h); update_quad<KIND> is the one place that loads a quad's
@@ -221,7 +236,7 @@ __device__ __forceinline__ void chain_advance(ChainState* st, const long long* _
     atomicExch(&st->ticket, 0u);
 }
 
-struct Row {  // one table row: c0..c3 of sampler_update (a classifier-free kind's s in c3), or the DpmppRow and a spare
+struct Row {  // one table row: c0..c3 of sampler_update (a classifier-free kind's s in c3), or the DpmppRow / PaintRow and a spare
     float c[8];
 };
 
@@ -239,12 +254,29 @@ __device__ __forceinline__ void noise4(bool add_noise, const float* zin, int64_t
     }
 }
 
+// the normals of quad q for every stream of the kind, z[4 s ..] from stream s: memory holds the streams one after another, numel values each
+// (the block one dmme_randn of kind_streams * numel values at `off` writes), and the draw of stream s sits at counter off + s n4 + q.
+// A single-stream kind calls noise4 the way it always did: through the loop at one trip the same values cost chain_kernel<2> and <7> one more
+// scalar spill each (-Rpass-analysis=kernel-resource-usage).
+template <int KIND, bool DRAWS>
+__device__ __forceinline__ void step_noise(const SamplerOperands& o, int flag, const float* zin, int64_t q, uint64_t seed, uint64_t off,
+                                           float (&z)[4 * kind_streams(KIND)]) {
+    if constexpr (kind_streams(KIND) == 1) {
+        noise4<DRAWS>(kind_draws(KIND, flag, 0), zin, q * 4, seed, off + (uint64_t)q, z);
+    } else {
+#pragma unroll
+        for (int s = 0; s < kind_streams(KIND); ++s)
+            noise4<DRAWS>(kind_draws(KIND, flag, s), zin ? zin + s * o.numel : nullptr, q * 4, seed, off + (uint64_t)s * (uint64_t)o.n4 + (uint64_t)q,
+                          *reinterpret_cast<float(*)[4]>(z + 4 * s));
+    }
+}
+
 // quad q of x (a classifier-free kind: of its first half, the result into both; noise and history are indexed by the first half, so such a
 // chain at batch B draws exactly what an unguided chain at batch B does).  Every access is 16 bytes, aligned and inside one image: chw % 4 == 0.
-// flag: add_noise, or (kind_hist) the history is valid.  The mixed prediction e^ = e_u + s (e_c - e_u) is three separately rounded operations;
+// flag: add_noise, (kind_hist) the history is valid, or (kind_paint) the streams the row uses.  The mixed prediction e^ = e_u + s (e_c - e_u) is three separately rounded operations;
 // s = 1 is plain conditional sampling (Ho & Salimans' w = s - 1).  The caller has z ready, so nothing loaded here is live across a draw.
 template <int KIND>
-__device__ __forceinline__ void update_quad(const SamplerOperands& o, int64_t q, const Row& r, int flag, const float (&z)[4]) {
+__device__ __forceinline__ void update_quad(const SamplerOperands& o, int64_t q, const Row& r, int flag, const float (&z)[4 * kind_streams(KIND)]) {
     const int64_t b = q * 4;
     const int planes = kind_planes(KIND) ? kind_planes(KIND) : o.planes;
     const int64_t eo = planes == 2 ? b + (b / o.chw) * o.chw : b;  // [B][2][chw]: the eps plane, then (IDDPM's v) the plane chw further on
@@ -262,6 +294,13 @@ __device__ __forceinline__ void update_quad(const SamplerOperands& o, int64_t q,
 #pragma unroll
         for (int j = 0; j < 4; ++j) xs[j] = dpmpp_update(xs[j], es[j], as[j], d, flag != 0, as[j]);
         *reinterpret_cast<float4*>(o.hist + b) = av;
+    } else if constexpr (kind_paint(KIND)) {
+        const PaintRow p = {r.c[0], r.c[1], r.c[2], r.c[3], r.c[4], r.c[5], r.c[6]};
+        const float4 mv = load4(o.mask + b);
+        av = load4(o.known + b);
+        const float* ms = reinterpret_cast<const float*>(&mv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xs[j] = paint_update(xs[j], es[j], as[j], ms[j], z[j], z[4 + j], z[8 + j], p, flag);
     } else {
         constexpr bool LEARNED = KIND == DMME_CHAIN_IDDPM;
         if (LEARNED && flag) av = load4(o.out + eo + o.chw);
@@ -283,8 +322,8 @@ __global__ void __launch_bounds__(256) eager_kernel(SamplerOperands o, Row r, in
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < o.n4; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = q * 4;
         if (!kind_ragged(KIND) || (b + 3 < o.numel && quads_fit)) {
-            float z[4];
-            noise4<false>(kind_noise(KIND) != NOISE_NEVER && flag, o.zin, b, 0, 0, z);
+            float z[4 * kind_streams(KIND)];
+            step_noise<KIND, false>(o, flag, o.zin, q, 0, 0, z);
             update_quad<KIND>(o, q, r, flag, z);
         } else if constexpr (kind_ragged(KIND)) {
             for (int64_t i = b; i < b + 4 && i < o.numel; ++i) {
@@ -296,9 +335,10 @@ __global__ void __launch_bounds__(256) eager_kernel(SamplerOperands o, Row r, in
     }
 }
 
-// The chain form: the row at coef[kind_row * i], the flag from the loop state (t != 1 / c2 != 0 by the kind's noise rule, or the history
-// flag), normals drawn at Philox(seed, offset + quad) unless o.zin is given (the kinds of kind_zin; tests).  The offset advances by the quads of
-// the update at every step, whether or not the step used its normals (the reference draws and discards at t == 1).
+// The chain form: the row at coef[kind_row * i], the flag from the loop state (t != 1 / c2 != 0 / the row's streams by the kind's noise rule,
+// or the history flag), normals drawn at Philox(seed, offset + stream * n4 + quad) unless o.zin is given (the kinds of kind_zin; tests).  The
+// offset advances by the quads of the update times the kind's streams at every step, whether or not the step used its normals (the reference
+// draws and discards at t == 1).  Every draw of a quad comes before its first load: nothing loaded is live across the sin / cos / log.
 // amdgpu_waves_per_eu(8): the draw's sin / cos / log keep the kinds that also branch on zin within a few scalar registers of the 8-wave budget;
 // told the target, the scheduler stays inside it (no spill) instead of settling for 7 waves.
 template <int KIND>
@@ -308,20 +348,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) c
     Row r;
 #pragma unroll
     for (int j = 0; j < kind_row(KIND); ++j) r.c[j] = coef[kind_row(KIND) * i + j];
-    const int flag = kind_hist(KIND) ? st->history_valid != 0ull : kind_adds_noise(KIND, r.c[2], t != 1);
+    const int flag = kind_hist(KIND) ? st->history_valid != 0ull : kind_paint(KIND) ? paint_streams_used(r.c[2], r.c[4], r.c[6]) : kind_adds_noise(KIND, r.c[2], t != 1);
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < o.n4; q += (int64_t)gridDim.x * blockDim.x) {
-        float z[4];
-        noise4<true>(kind_noise(KIND) != NOISE_NEVER && flag, kind_zin(KIND) ? o.zin : nullptr, q * 4, seed, off + (uint64_t)q, z);
+        float z[4 * kind_streams(KIND)];
+        step_noise<KIND, true>(o, flag, kind_zin(KIND) ? o.zin : nullptr, q, seed, off, z);
         update_quad<KIND>(o, q, r, flag, z);
     }
     __syncthreads();
-    chain_advance(st, t_table, i, kind_hist(KIND) ? 0ull : (unsigned long long)o.n4, kind_hist(KIND));
+    chain_advance(st, t_table, i, kind_hist(KIND) ? 0ull : (unsigned long long)o.n4 * kind_streams(KIND), kind_hist(KIND));
 }
 
 // the run-time kind as a compile-time one: f(std::integral_constant<int, kind>)
 template <int K = 0, class F>
 static int dispatch_kind(int kind, F&& f) {
-    if constexpr (K > DMME_CHAIN_DPMPP_CFG) {
+    if constexpr (K > DMME_CHAIN_REPAINT) {
         set_error("unknown sampler kind %d", kind);
         return DMME_ERR_INVALID;
     } else {
@@ -330,7 +370,8 @@ static int dispatch_kind(int kind, F&& f) {
 }
 static int check_operands(const char* what, int kind, const SamplerOperands& o, bool eager) {
     DMME_REQUIRE(kind_known(kind), DMME_ERR_INVALID, "%s: unknown sampler kind %d", what, kind);
-    DMME_REQUIRE(o.x && o.out && (o.hist || !kind_hist(kind)) && o.numel > 0 && o.chw > 0, DMME_ERR_INVALID, "%s: bad argument", what);
+    DMME_REQUIRE(o.x && o.out && (o.hist || !kind_hist(kind)) && ((o.known && o.mask) || !kind_paint(kind)) && o.numel > 0 && o.chw > 0, DMME_ERR_INVALID,
+                 "%s: bad argument", what);
     DMME_REQUIRE(kind_grad(kind) == (o.grad != nullptr), DMME_ERR_INVALID, "%s: the guided kinds (3, 4) and only they take a gradient", what);
     DMME_REQUIRE(kind_planes(kind) || o.planes == 1 || o.planes == 2, DMME_ERR_INVALID, "%s: a network output of %d planes per image (1: eps, 2: eps and v)",
                  what, o.planes);
@@ -343,7 +384,7 @@ int launch_sampler_eager(const char* what, int kind, const SamplerOperands& o, c
     DMME_REQUIRE(row, DMME_ERR_INVALID, "%s: null argument", what);
     Row r = {};
     for (int j = 0; j < kind_row(kind); ++j) r.c[j] = row[j];
-    if (!kind_hist(kind)) flag = kind_adds_noise(kind, r.c[2], flag);
+    if (!kind_hist(kind)) flag = kind_paint(kind) ? paint_streams_used(r.c[2], r.c[4], r.c[6]) : kind_adds_noise(kind, r.c[2], flag);
     DMME_REQUIRE(o.zin || kind_hist(kind) || !flag, DMME_ERR_INVALID, "%s: a step that adds noise needs z", what);
     return dispatch_kind(kind, [&](auto k) -> int {
         constexpr int K = decltype(k)::value;

@@ -1285,7 +1285,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 111; }  // 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 112; }  // 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1554,8 +1554,8 @@ DMME_API int dmme_q_sample(const float* x0, const float* z, const float* sqrt_ab
 
 // ---- the reverse updates (kernels_sampler.hip): every entry point fills in the operands of its kind and calls one of two launchers
 static SamplerOperands sampler_operands(float* x, const float* out, const float* zin, int64_t B, int64_t chw, const float* grad = nullptr,
-                                        float* hist = nullptr, int planes = 1) {
-    return SamplerOperands{x, out, grad, zin, hist, chw, B * chw, (B * chw + 3) / 4, planes};
+                                        float* hist = nullptr, int planes = 1, const float* known = nullptr, const float* mask = nullptr) {
+    return SamplerOperands{x, out, grad, zin, hist, known, mask, chw, B * chw, (B * chw + 3) / 4, planes};
 }
 
 DMME_API int dmme_ddpm_step(float* x, const float* eps, const float* z, float inv_sqrt_alpha, float eps_coef, float sigma,
@@ -1650,6 +1650,19 @@ DMME_API int dmme_chain_update_cfg_dpmpp(float* x_2B, const float* model_out, fl
                                 t_table, state, (hipStream_t)stream);
 }
 
+// RePaint / SDEdit: kind DMME_CHAIN_REPAINT, tables of 8 floats per index, the known image and its mask, three normal streams per step
+DMME_API int dmme_repaint_step(float* x, const float* model_out, const float* known, const float* mask, const float* z3, const float* row, int B,
+                               int64_t chw, int out_planes, void* stream) {
+    return launch_sampler_eager("repaint_step", DMME_CHAIN_REPAINT, sampler_operands(x, model_out, z3, B, chw, nullptr, nullptr, out_planes, known, mask), row, 0,
+                                (hipStream_t)stream);
+}
+
+DMME_API int dmme_chain_update_repaint(float* x, const float* model_out, const float* known, const float* mask, const float* noise,
+                                       const float* step_coef, const int64_t* t_table, void* state, int B, int64_t chw, int out_planes, void* stream) {
+    return launch_sampler_chain("chain_update_repaint", DMME_CHAIN_REPAINT, sampler_operands(x, model_out, noise, B, chw, nullptr, nullptr, out_planes, known, mask),
+                                step_coef, t_table, state, (hipStream_t)stream);
+}
+
 // One capturable step of any kind: the checks of plan against kind, the network's no-grad forward at the device-resident t (the loop
 // state's second word), `between` (the guided kinds' classifier pass, which fills the gradient operand), the update.  A classifier-free kind
 // runs a class-conditional plan of batch 2B with labels (conditional half, unconditional half) and updates at B = plan batch / 2.
@@ -1657,9 +1670,10 @@ DMME_API int dmme_chain_update_cfg_dpmpp(float* x_2B, const float* model_out, fl
 // looked first under their own name, and still do.
 static int chain_step_common(const char* what, const dmme_plan* plan, const void* packed, float* x, const int64_t* labels, int* status, float* model_out,
                              void* workspace, int kind, const float* grad, float* hist, const float* step_coef, const int64_t* t_table, void* state,
-                             void* stream, const std::function<int()>& between = nullptr) {
+                             void* stream, const std::function<int()>& between = nullptr, const float* known = nullptr, const float* mask = nullptr) {
     const bool cfg = kind_cfg(kind);
-    DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state && (labels || !cfg) && (hist || !kind_hist(kind)),
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state && (labels || !cfg) && (hist || !kind_hist(kind)) &&
+                     ((known && mask) || !kind_paint(kind)),
                  DMME_ERR_INVALID, "%s: null argument", what);
     if (cfg)
         DMME_REQUIRE(plan->cond && plan->B % 2 == 0, DMME_ERR_INVALID,
@@ -1678,13 +1692,13 @@ static int chain_step_common(const char* what, const dmme_plan* plan, const void
     if (between)
         if (int rc = between()) return rc;
     return launch_sampler_chain(what, kind, sampler_operands(x, model_out, nullptr, cfg ? plan->B / 2 : plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
-                                                             grad, hist, planes),
+                                                             grad, hist, planes, known, mask),
                                 step_coef, t_table, state, (hipStream_t)stream);
 }
 
 DMME_API int dmme_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, int kind,
                              const float* step_coef, const int64_t* t_table, void* state, void* stream) {
-    DMME_REQUIRE(kind_known(kind) && !kind_cfg(kind) && !kind_grad(kind) && !kind_hist(kind), DMME_ERR_INVALID,
+    DMME_REQUIRE(kind_known(kind) && !kind_cfg(kind) && !kind_grad(kind) && !kind_hist(kind) && !kind_paint(kind), DMME_ERR_INVALID,
                  "chain_step: sampler kind %d (guided kinds: dmme_guided_chain_step, and so on)", kind);
     return chain_step_common("chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, kind, nullptr, nullptr, step_coef, t_table, state, stream);
 }
@@ -1707,6 +1721,12 @@ DMME_API int dmme_cfg_dpmpp_chain_step(const dmme_plan* plan_2B, const void* pac
                                        int* status, float* history, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
     return chain_step_common("cfg_dpmpp_chain_step", plan_2B, packed, x_2B, labels_2B, status, model_out, workspace, DMME_CHAIN_DPMPP_CFG, nullptr, history,
                              step_coef, t_table, state, stream);
+}
+
+DMME_API int dmme_repaint_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* known,
+                                     const float* mask, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    return chain_step_common("repaint_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_REPAINT, nullptr, nullptr, step_coef, t_table,
+                             state, stream, nullptr, known, mask);
 }
 
 // Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM): between the forward and the update, the classifier's forward, the log-softmax

@@ -2,3 +2,4 @@ from .ddpm import DDPM  # noqa: F401
 from .ddim import DDIM, GeneralizedDDIM  # noqa: F401
 from .iddpm import IDDPM  # noqa: F401
 from .dpm_solver import DPMSolverPP  # noqa: F401
+from .repaint import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401

@@ -43,7 +43,7 @@ class ChainTables:
 def chain_draws(kind: int, rows) -> bool:
     """does a chain of this kind over these table rows consume normals?  The host's statement of the kernels' noise rule (csrc/common.h:
     kind_noise): the shipped DDIM kinds and DPM-Solver++ never do, the paper-form DDIM kinds only with a non-zero k2 somewhere, every kind
-    with a DDPM mean does.  A chain that draws nothing leaves torch's generator where the eager loop leaves it."""
+    with a DDPM mean does, and so does RePaint (three streams per step).  A chain that draws nothing leaves torch's generator where the eager loop leaves it."""
     if kind in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED, _lib.CHAIN_DPMPP, _lib.CHAIN_DPMPP_CFG):
         return False
     if kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_GDDIM_CFG):
@@ -177,6 +177,20 @@ class DDPM(nn.Module):
         self._c1, self._c2, self._sigma = sampling_coefficients(beta, alpha, alpha_bar)
         self._all_t: Optional[Tensor] = None
         self._runner: Optional[ChainRunner] = None
+
+    def _use_alpha_bar(self, alpha_bar) -> None:
+        """a (T+1) alpha_bar table in place of the linear schedule's (samplers built over another process's schedule): the buffers and
+        DDPM's host scalars follow it"""
+        T = self.timesteps
+        ab = torch.as_tensor(alpha_bar).detach().reshape(-1).to(dtype=torch.float32, device="cpu")
+        if ab.numel() != T + 1 or float(ab[0]) != 1.0 or not bool(((ab[1:] > 0) & (ab[1:] < 1)).all()) or not bool((ab[1:] < ab[:-1]).all()):
+            raise ValueError(f"alpha_bar: {T + 1} decreasing values, 1 at t = 0 and inside (0, 1) elsewhere")
+        ab = ab.reshape(-1, 1, 1, 1)
+        alpha = torch.cat([torch.ones_like(ab[:1]), ab[1:] / ab[:-1]])
+        for name, v in (("beta", 1 - alpha), ("alpha", alpha), ("alpha_bar", ab), ("_sqrt_alpha_bar", torch.sqrt(ab).reshape(-1).contiguous()),
+                        ("_sqrt_one_minus_alpha_bar", torch.sqrt(1 - ab).reshape(-1).contiguous())):
+            self.register_buffer(name, v, persistent=False)
+        self._c1, self._c2, self._sigma = sampling_coefficients(self.beta, self.alpha, self.alpha_bar)
 
     # ------------------------------------------------------------------ device-resident loop (replayable step)
     _chain_kind = _lib.CHAIN_DDPM

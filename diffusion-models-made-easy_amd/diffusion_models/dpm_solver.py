@@ -23,7 +23,6 @@ from torch import Tensor, nn
 from .. import _lib
 from ..common.noise import gaussian
 from ..equations.ddim import linear_tau, quadratic_tau
-from ..equations.ddpm import sampling_coefficients
 from .ddim import DDIM
 from .ddpm import DDPM, ChainRunner, _scalar_index
 
@@ -127,15 +126,7 @@ class DPMSolverPP(DDIM):
         if int(sub_timesteps) != sub_timesteps or not 1 <= sub_timesteps <= timesteps:
             raise ValueError(f"sub_timesteps = {sub_timesteps!r} outside 1..{timesteps}")
         if alpha_bar is not None:
-            ab = torch.as_tensor(alpha_bar).detach().reshape(-1).to(dtype=torch.float32, device="cpu")
-            if ab.numel() != timesteps + 1 or float(ab[0]) != 1.0 or not bool(((ab[1:] > 0) & (ab[1:] < 1)).all()) or not bool((ab[1:] < ab[:-1]).all()):
-                raise ValueError(f"alpha_bar: {timesteps + 1} decreasing values, 1 at t = 0 and inside (0, 1) elsewhere")
-            ab = ab.reshape(-1, 1, 1, 1)
-            alpha = torch.cat([torch.ones_like(ab[:1]), ab[1:] / ab[:-1]])
-            for name, v in (("beta", 1 - alpha), ("alpha", alpha), ("alpha_bar", ab), ("_sqrt_alpha_bar", torch.sqrt(ab).reshape(-1).contiguous()),
-                            ("_sqrt_one_minus_alpha_bar", torch.sqrt(1 - ab).reshape(-1).contiguous())):
-                self.register_buffer(name, v, persistent=False)
-            self._c1, self._c2, self._sigma = sampling_coefficients(self.beta, self.alpha, self.alpha_bar)  # DDPM's host scalars follow the table
+            self._use_alpha_bar(alpha_bar)
         self.sub_timesteps, self.tau_schedule, self.order, self.clip_x0 = int(sub_timesteps), kind, int(order), bool(clip_x0)
         ab64 = self.alpha_bar.reshape(-1).to(torch.float64).cpu().numpy()
         grid = solver_grid(ab64, self.sub_timesteps, kind)

@@ -1,0 +1,262 @@
+"""RePaint inpainting (Lugmayr et al. 2022) and SDEdit image editing (Meng et al. 2022) over any unconditionally trained noise predictor
+of the package, as device-resident chains.
+
+Grid 0 = tau_0 < tau_1 < ... < tau_n = T (`solver_grid(alpha_bar, sub_timesteps, "linear")`); a level k is a sample at noise level
+tau_k, level 0 a clean image.  RePaint walks the levels n -> 0, jumping back up `jump_length` levels `resamples - 1` times from every
+`jump_length`-th level (`repaint_levels`).  Every downward transition a -> b = a - 1 is one network evaluation and one table row:
+
+    u  = c0 (x - c1 eps) [+ c2 z0]        the reverse step of the pixels to generate      (DDPM's, sigma_t^2 = beta_t)
+    k  = ka x0 [+ ks z1]                  the known pixels noised to level b
+    y  = m k + (1 - m) u                  m: 1 = known pixel, 0 = generate
+    x' = y, or r0 y + r1 z2               the walk's next upward run b -> c, folded
+
+The fold: the upward transitions that follow a downward one use no network, and forward noising composes, so the run b -> c is ONE
+Gaussian q(x_c | x_b) = N(sqrt(abar_c / abar_b) x_b, (1 - abar_c / abar_b) I) with one normal per element.  It has the distribution of
+the `jump_length` single sqrt(1 - beta) x + sqrt(beta) z steps of the paper's Algorithm 1, not their draws.  So every replay of the
+captured step is one forward pass plus one update, and no step runs a network pass whose result is thrown away.
+
+The host computes the rows in float64 and rounds them to fp32 (include/dmme_hip.h: dmme_repaint_step); the walk is a table of timesteps
+that goes up and down, which the replayed step's `t = t_table[i]` never minded.  SDEdit is the plain walk k -> 0 from a noised guide."""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor, nn
+
+from .. import _lib
+from ..common.noise import gaussian, gaussian_like, philox_reserve
+from .ddpm import DDPM, ChainRunner
+from .dpm_solver import solver_grid
+
+ROW = 8  # floats per table row: c0, c1, c2, ka, ks, r0, r1, -
+STREAMS = 3  # normal streams a step owns: z0 (reverse step), z1 (known pixels), z2 (jump)
+
+
+def repaint_levels(n: int, jump_length: int = 10, resamples: int = 10) -> List[int]:
+    """the level walk n, n - 1, ..., 0 with its jumps back up: from each level l = 1, 1 + j, 1 + 2j, ... whose jump stays inside the grid
+    (l + j <= n) the walk climbs j levels, resamples - 1 times.  j = 1 is the paper's Algorithm 1 (every step t >= 2 taken U = resamples
+    times); n = 250, j = r = 10 the published schedule in 1-based levels.  n + (r - 1) j floor((n - 1) / j) downward transitions."""
+    n, j, r = int(n), int(jump_length), int(resamples)
+    if n < 1 or j < 1 or r < 1:
+        raise ValueError(f"repaint_levels: n = {n}, jump_length = {j}, resamples = {r} must all be at least 1")
+    left = {l: r - 1 for l in range(1, n - j + 1, j)}
+    k, walk = n, [n]
+    while k >= 1:
+        k -= 1
+        walk.append(k)
+        if left.get(k, 0) > 0:
+            left[k] -= 1
+            for _ in range(j):
+                k += 1
+                walk.append(k)
+    return walk
+
+
+def repaint_rows(alpha_bar, grid: Sequence[int], walk: Sequence[int], reverse=None) -> Tuple[np.ndarray, List[int]]:
+    """(float64 rows [n_rows + 1][8], t_table [n_rows + 1]) of a level walk: one row {c0, c1, c2, ka, ks, r0, r1, 0} per downward
+    transition a -> b with the upward run b -> c behind it folded in; the k-th transition sits at loop index n_rows - k, t_table there is
+    tau_a.  Row 0 is never stepped from.  `reverse`: per-timestep (1/sqrt(alpha_t), beta_t/sqrt(1-abar_t), sqrt(beta_t)) of a process
+    whose grid is every timestep, taken in place of the float64 values so that the reverse half carries DDPM's bits."""
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
+    walk = [int(v) for v in walk]
+    steps, p, last = [], 0, len(walk) - 1
+    while p < last:
+        a, b = walk[p], walk[p + 1]
+        if b != a - 1 or b < 0:
+            raise ValueError(f"repaint_rows: the walk goes {a} -> {b} where a step down by one level was due")
+        p += 1
+        c = b
+        while p < last and walk[p + 1] == walk[p] + 1:
+            p, c = p + 1, c + 1
+        steps.append((a, b, c))
+    n_rows = len(steps)
+    rows = np.zeros((n_rows + 1, ROW), dtype=np.float64)
+    rows[0, :7] = (1.0, 0.0, 0.0, 1.0, 0.0, 1.0, 0.0)
+    ttab = [0] * (n_rows + 1)
+    for k, (a, b, c) in enumerate(steps):
+        i = n_rows - k
+        ab_a, ab_b, ab_c = ab[grid[a]], ab[grid[b]], ab[grid[c]]
+        alpha = ab_a / ab_b
+        beta = 1.0 - alpha
+        if reverse is None:
+            c0, c1, c2 = 1.0 / np.sqrt(alpha), beta / np.sqrt(1.0 - ab_a), np.sqrt(beta)
+        else:
+            c0, c1, c2 = (float(col[grid[a]]) for col in reverse)
+        r0, r1 = (1.0, 0.0) if c == b else (np.sqrt(ab_c / ab_b), np.sqrt(1.0 - ab_c / ab_b))
+        rows[i, :7] = (c0, c1, c2 if b > 0 else 0.0, np.sqrt(ab_b), np.sqrt(1.0 - ab_b), r0, r1)
+        ttab[i] = int(grid[a])
+    return rows, ttab
+
+
+def _row_arg(row):
+    return (C.c_float * ROW)(*row)
+
+
+def _row_draws(row) -> bool:
+    return row[2] != 0.0 or row[4] != 0.0 or row[6] != 0.0
+
+
+class PaintChainRunner(ChainRunner):
+    """ChainRunner whose captured step is dmme_repaint_chain_step: tables of 8 floats per index, the known image and its mask in fixed
+    buffers beside x (read only: a chain fills them once), three normal streams per step"""
+
+    def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
+        super().__init__(process, x, use_graph, spec)
+        self.known = torch.zeros_like(x)
+        self.mask = torch.zeros_like(x)
+        self.noise_numel = STREAMS * x.numel()
+
+    def _launch(self, packed):
+        _lib.check(
+            _lib.lib().dmme_repaint_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace),
+                                               _lib.ptr(self.known), _lib.ptr(self.mask), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
+                                               _lib.stream_ptr()),
+            "dmme_repaint_chain_step",
+        )
+        self.plan.overwritten()
+
+    def paint(self, x: Tensor, known: Tensor, mask: Tensor, first: int) -> Tensor:
+        """the chain from loop index `first` down to 0 on copies of the three images; a new tensor"""
+        self.x.copy_(x)
+        self.known.copy_(known)
+        self.mask.copy_(mask)
+        return self.run(first, first).clone()
+
+
+class RePaint(DDPM):
+    r"""RePaint / SDEdit over any unconditional noise-prediction network of the package (an IDDPM network's learned variance is not used:
+    the reverse step's variance is beta).
+
+    `sub_timesteps`: levels of the grid (`sub_timesteps = timesteps`: every timestep, and the reverse half is DDPM's update bit for bit);
+    `jump_length`, `resamples`: the walk of `repaint_levels`.  `alpha_bar`: a (T+1) table in place of the linear schedule's
+    (`from_process` takes it from a DDPM / IDDPM instance)."""
+
+    _chain_kind = _lib.CHAIN_REPAINT
+    _runner_class = PaintChainRunner
+
+    def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 250, jump_length: int = 10, resamples: int = 10, start: float = 0.0001,
+                 end: float = 0.02, alpha_bar: Optional[Tensor] = None) -> None:
+        super().__init__(model, timesteps, start, end)
+        for name, v in (("jump_length", jump_length), ("resamples", resamples)):
+            if isinstance(v, bool) or int(v) != v or v < 1:
+                raise ValueError(f"{name} = {v!r}; an integer of at least 1")
+        if isinstance(sub_timesteps, bool) or int(sub_timesteps) != sub_timesteps or not 1 <= sub_timesteps <= timesteps:
+            raise ValueError(f"sub_timesteps = {sub_timesteps!r} outside 1..{timesteps}")
+        if alpha_bar is not None:
+            self._use_alpha_bar(alpha_bar)
+        self.sub_timesteps, self.jump_length, self.resamples = int(sub_timesteps), int(jump_length), int(resamples)
+        ab64 = self.alpha_bar.reshape(-1).to(torch.float64).cpu().numpy()
+        grid = solver_grid(ab64, self.sub_timesteps, "linear")
+        self.n_levels = len(grid) - 1
+        self.register_buffer("tau", torch.tensor(grid, dtype=torch.int64), persistent=False)
+        self._tau_host, self._ab64 = grid, ab64
+        self._walk = repaint_levels(self.n_levels, self.jump_length, self.resamples)
+        self._tables = self._make_tables(self._walk)
+        self._plain_tables = self._make_tables(list(range(self.n_levels, -1, -1)))  # SDEdit's: loop index = level
+        self.n_rows = self._tables[0]
+
+    @classmethod
+    def from_process(cls, p: DDPM, **kw):
+        """RePaint over `p`'s network and noise schedule (an IDDPM's cosine schedule, for one)"""
+        return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
+
+    def _make_tables(self, walk):
+        full = self.n_levels == self.timesteps
+        rows, ttab = repaint_rows(self._ab64, self._tau_host, walk, (self._c1, self._c2, self._sigma) if full else None)
+        return len(ttab) - 1, [tuple(float(np.float32(v)) for v in r) for r in rows], ttab
+
+    def _chain_tables(self):
+        n, rows, ttab = self._tables
+        return n, list(rows), list(ttab)
+
+    # ------------------------------------------------------------------ arguments
+    def _image(self, x: Tensor, what: str) -> Tensor:
+        if not (isinstance(x, Tensor) and x.dim() == 4 and x.is_floating_point()):
+            raise ValueError(f"{what}: a floating-point image batch (B, C, H, W)")
+        return x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous()
+
+    @staticmethod
+    def _mask(mask: Optional[Tensor], like: Tensor) -> Tensor:
+        """(B|1, C|1, H, W) with values in [0, 1] -> contiguous fp32 of `like`'s shape; None: nothing is known"""
+        if mask is None:
+            return torch.zeros_like(like)
+        m = torch.as_tensor(mask).detach().to(device=like.device, dtype=torch.float32)
+        B, Cc, H, W = like.shape
+        if m.dim() != 4 or m.shape[0] not in (1, B) or m.shape[1] not in (1, Cc) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"mask: shape {tuple(m.shape)} does not broadcast from (B|1, C|1, H, W) to {tuple(like.shape)}")
+        if not bool(((m >= 0) & (m <= 1)).all()):
+            raise ValueError("mask: values must lie in [0, 1] (1: known pixel, 0: generate)")
+        return m.expand(B, Cc, H, W).contiguous()
+
+    def _paint_runner(self, slot: str, shape, dev, tables=None) -> Optional[PaintChainRunner]:
+        if tables is None:
+            return self._buffered_runner(slot, shape, dev)
+        return self._buffered_runner(slot, shape, dev, spec=lambda: (_lib.CHAIN_REPAINT, tables), buf=slot + "_buf")
+
+    # ------------------------------------------------------------------ chains
+    def _eager_chain(self, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None) -> Tensor:
+        """the host loop over dmme_repaint_step, in place on x: normals from dmme_randn at the offsets the captured chain's state walks
+        through, so the two agree bit for bit under the same seed"""
+        n, rows, ttab = tables if tables is not None else self._tables
+        first = n if first is None else int(first)
+        lib, numel = _lib.lib(), x.numel()
+        seed, off = philox_reserve(x.device, STREAMS * numel * first)
+        tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
+        z3 = torch.empty(STREAMS * numel, dtype=torch.float32, device=x.device)
+        for k, i in enumerate(range(first, 0, -1)):
+            eps = self.model(x, tt[i]).detach().to(torch.float32).contiguous()
+            draws = _row_draws(rows[i])
+            if draws:
+                _lib.check(lib.dmme_randn(_lib.ptr(z3), z3.numel(), seed, off + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
+            _lib.check(lib.dmme_repaint_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(z3 if draws else None), _row_arg(rows[i]),
+                                             x.shape[0], x[0].numel(), eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_repaint_step")
+        return x
+
+    def _chain(self, slot: str, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None) -> Tensor:
+        first = (tables if tables is not None else self._tables)[0] if first is None else first
+        runner = self._paint_runner(slot, x.shape, x.device, tables)
+        if runner is None:
+            return self._eager_chain(x, known, mask, tables, first)
+        return runner.paint(x, known, mask, first)
+
+    @torch.no_grad()
+    def inpaint(self, x0: Tensor, mask: Tensor) -> Tensor:
+        r"""the image batch whose pixels equal `x0` where `mask` is 1 (bit for bit) and are generated, in harmony with them, where it is 0:
+        x_T ~ N(0, I), then the whole RePaint walk through the captured step.  mask: (B|1, C|1, H, W), values in [0, 1]."""
+        known = self._image(x0, "inpaint")
+        m = self._mask(mask, known)
+        return self._chain("_runner", gaussian(known.shape, device=known.device), known, m)
+
+    @torch.no_grad()
+    def edit(self, x_guide: Tensor, strength: float, mask: Optional[Tensor] = None) -> Tensor:
+        r"""SDEdit: the guide noised to level k = max(1, round(strength n)) and denoised by the plain walk k -> 0 (no resampling,
+        whatever `resamples` is).  strength in (0, 1]: 1 forgets the guide, small values stay close to it.  With a mask the pixels where
+        it is 1 are kept exactly (SDEdit's masked variant)."""
+        strength = float(strength)
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"strength = {strength!r} outside (0, 1]")
+        guide = self._image(x_guide, "edit")
+        m = self._mask(mask, guide)
+        k = self.edit_level(strength)
+        t = torch.full((guide.shape[0],), self._tau_host[k], dtype=torch.int64, device=guide.device)
+        x_k = self._noised(guide, t, gaussian_like(guide), target=False)[2]
+        return self._chain("_edit_runner", x_k, guide, m, self._plain_tables, k)
+
+    def edit_level(self, strength: float) -> int:
+        """the level SDEdit starts from"""
+        return min(self.n_levels, max(1, int(round(float(strength) * self.n_levels))))
+
+    @torch.no_grad()
+    def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
+        """`inpaint` with nothing known: the walk from pure noise"""
+        zeros = torch.zeros(tuple(img_size), dtype=torch.float32, device=self.beta.device)
+        return self._chain("_runner", gaussian(img_size, device=zeros.device), zeros, zeros)
+
+    def sampling_step(self, *a, **kw):
+        raise NotImplementedError("RePaint runs whole chains: inpaint / edit / generate")
+
+    denoise_once = sampling_step

@@ -20,6 +20,8 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/iddpm/cifar10.yaml --sample-steps K    (Improved DDPM: K << T strided steps)
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3,5 --guidance-scale 2.5   (classifier-free guidance)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dpm++ --sample-steps 20   (DPM-Solver++(2M); any of the four configs)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
 """
 
 from __future__ import annotations
@@ -231,6 +233,67 @@ def _dpm_solver(module, args):
     return DPMSolverPP.from_process(old, **kw)
 
 
+PAINT_SAMPLERS = ("repaint", "sdedit")
+
+
+def _check_paint_args(args) -> None:
+    """what goes with --sampler repaint / sdedit and what does not; exits with a message (before anything touches the GPU)"""
+    given = [f for f, v in (("--image", args.image), ("--mask", args.mask), ("--strength", args.strength), ("--jump-length", args.jump_length),
+                            ("--resamples", args.resamples)) if v is not None]
+    if args.sampler not in PAINT_SAMPLERS:
+        if given:
+            raise SystemExit(f"{', '.join(given)} belong{'s' if len(given) == 1 else ''} to --sampler repaint / sdedit")
+        return
+    name = f"--sampler {args.sampler}"
+    if args.command != "sample":
+        raise SystemExit(f"{name} belongs to `sample`: it conditions a trained network on pixels, training is the config's own")
+    for flag, v in (("--eta", args.eta), ("--steps", args.steps), ("--labels", args.labels), ("--guidance-scale", args.guidance_scale)):
+        if v is not None:
+            raise SystemExit(f"{flag} does not go with {name}: it runs whole chains of an unconditional network (--sample-steps K sets the grid)")
+    if args.image is None:
+        raise SystemExit(f"{name} needs --image X.npy (float32 in [-1, 1], (B, C, H, W) or (C, H, W))")
+    if args.sample_steps is not None and args.sample_steps < 1:
+        raise SystemExit("--sample-steps must be at least 1")
+    if args.sampler == "repaint":
+        if args.mask is None:
+            raise SystemExit("--sampler repaint needs --mask M.npy (1: keep the image's pixel, 0: generate it)")
+        if args.strength is not None:
+            raise SystemExit("--strength belongs to --sampler sdedit")
+        for flag, v in (("--jump-length", args.jump_length), ("--resamples", args.resamples)):
+            if v is not None and v < 1:
+                raise SystemExit(f"{flag} must be at least 1")
+    else:
+        walk = [f for f, v in (("--jump-length", args.jump_length), ("--resamples", args.resamples)) if v is not None]
+        if walk:
+            raise SystemExit(f"{', '.join(walk)} belong{'s' if len(walk) == 1 else ''} to --sampler repaint: SDEdit walks straight down")
+        if args.strength is None or not 0.0 < args.strength <= 1.0:
+            raise SystemExit("--sampler sdedit needs --strength S in (0, 1]: the share of the noise levels the guide is pushed up")
+
+
+def _load_npy(path: str, what: str) -> torch.Tensor:
+    """a float image array (B, C, H, W) or (C, H, W) from a .npy file, as a 4-D fp32 tensor"""
+    import numpy as np
+
+    try:
+        arr = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as exc:
+        raise SystemExit(f"{what} {path}: {exc}")
+    if arr.ndim == 3:
+        arr = arr[None]
+    if arr.ndim != 4 or not np.issubdtype(arr.dtype, np.floating):
+        raise SystemExit(f"{what} {path}: a float array shaped (B, C, H, W) or (C, H, W), got {arr.dtype} {arr.shape}")
+    return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+
+
+def _paint_process(module, args):
+    """RePaint / SDEdit over the network and the noise schedule of the process the YAML built"""
+    from .diffusion_models import RePaint
+
+    old = module.diffusion_model
+    sub = min(250, old.timesteps) if args.sample_steps is None else args.sample_steps
+    return RePaint.from_process(old, sub_timesteps=sub, jump_length=args.jump_length or 10, resamples=args.resamples or 10)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="dmme_amd.trainer")
     ap.add_argument("command", choices=["fit", "sample"])
@@ -245,9 +308,16 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
-    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++"],
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table; "
-                         "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20)")
+                         "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20); "
+                         "'repaint' inpaints --image where --mask is 0, 'sdedit' edits --image at --strength (any unconditional config; --sample-steps: grid levels, default 250)")
+    ap.add_argument("--image", default=None, help="sample --sampler repaint / sdedit: .npy, float32 in [-1, 1], (B, C, H, W) or (C, H, W)")
+    ap.add_argument("--mask", default=None, help="sample --sampler repaint (needed) / sdedit (optional): .npy broadcastable to the image, 1 = keep the pixel, 0 = generate")
+    ap.add_argument("--strength", type=float, default=None, help="sample --sampler sdedit: in (0, 1], the share of the noise levels the guide is pushed up before it is denoised")
+    ap.add_argument("--jump-length", type=int, default=None, help="sample --sampler repaint: levels a resampling jump climbs (default 10)")
+    ap.add_argument("--resamples", type=int, default=None, help="sample --sampler repaint: times each stretch of --jump-length levels is walked (default 10)")
+    ap.add_argument("--save", default=None, help="sample: write the images to this .npy file (float32, (B, C, H, W))")
     ap.add_argument("--eta", type=float, default=None, help="sample --sampler ddim-paper: 0 (default) deterministic ... 1 DDPM's posterior variance")
     ap.add_argument("--solver-order", type=int, default=None, choices=[1, 2], help="sample --sampler dpm++: 2 (default) multistep second order, 1 first order")
     ap.add_argument("--tau-schedule", default=None, choices=["linear", "quadratic", "logsnr"], help="sample --sampler dpm++: the timestep grid (default logsnr)")
@@ -260,12 +330,20 @@ def main(argv=None):
                          "sample --sampler dpm++: the solver's steps")
     args = ap.parse_args(argv)
     _check_solver_args(args)
+    _check_paint_args(args)
+    if args.save is not None and args.command != "sample":
+        raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
 
     from . import _lib
     from . import distributed as D
 
     conf = parse_config(args.config)
-    if args.sample_steps is not None and args.sampler != "dpm++":
+    if args.sampler in PAINT_SAMPLERS:
+        if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+            raise SystemExit(f"--sampler {args.sampler} needs an unconditional config: guided inpainting / editing is not implemented")
+        image = _load_npy(args.image, "--image")
+        mask = None if args.mask is None else _load_npy(args.mask, "--mask")
+    elif args.sample_steps is not None and args.sampler != "dpm++":
         from .lit_modules import LitIDDPM
 
         cls = _resolve(conf["model_spec"]["class_path"])
@@ -303,12 +381,18 @@ def main(argv=None):
             module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta or 0.0).cuda()
         elif args.sampler == "dpm++":
             module.diffusion_model = _dpm_solver(module, args).cuda()
+        elif args.sampler in PAINT_SAMPLERS:
+            module.diffusion_model = _paint_process(module, args).cuda()
         module.eval()
         dm = module.diffusion_model
         t0 = time.perf_counter()
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)
-        if getattr(module, "conditional", False):
+        if args.sampler == "repaint":
+            imgs = dm.inpaint(image, mask)
+        elif args.sampler == "sdedit":
+            imgs = dm.edit(image, args.strength, mask)
+        elif getattr(module, "conditional", False):
             if args.steps is not None or args.sampler == "ddim-paper" or (args.sample_steps is not None and args.sampler != "dpm++"):
                 raise SystemExit("class-conditional configs sample whole chains: --labels / --guidance-scale only")
             if args.guidance_scale is not None:
@@ -333,6 +417,10 @@ def main(argv=None):
             for k in range(args.steps):
                 imgs = module(imgs, first - k)
         torch.cuda.synchronize()
+        if args.save is not None:
+            import numpy as np
+
+            np.save(args.save, imgs.detach().to(torch.float32).cpu().numpy())
         print(json.dumps({"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3),
                           "finite": bool(torch.isfinite(imgs).all())}))
         return 0

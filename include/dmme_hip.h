@@ -517,6 +517,41 @@ DMME_API int dmme_chain_update_cfg_dpmpp(float* x_2B, const float* model_out, fl
 DMME_API int dmme_cfg_dpmpp_chain_step(const dmme_plan* plan_2B, const void* packed, float* x_2B, const int64_t* labels_2B, float* model_out, void* workspace,
                                        int* status, float* history, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
+/* ---- RePaint inpainting (Lugmayr et al. 2022) and SDEdit image editing (Meng et al. 2022): conditioning an unconditional network on pixels ----
+ * Grid 0 = tau_0 < tau_1 < ... < tau_n = T; a level k is a sample at noise level tau_k.  RePaint walks the levels n -> 0 with jumps back
+ * up; every downward transition a -> b = a - 1 is one network evaluation and one table row.  The upward transitions that follow it (b -> c,
+ * c = b or b + jump length) use no network and forward noising composes, so the row carries them FOLDED into one Gaussian,
+ *     q(x_c | x_b) = N(sqrt(abar_c / abar_b) x_b, (1 - abar_c / abar_b) I)         (abar at tau_c, tau_b)
+ * which has the distribution of the single sqrt(1 - beta) x + sqrt(beta) z steps it replaces, not their draws.  A plain walk n -> 0 (no
+ * jump in any row) is the SDEdit chain.  Kind DMME_CHAIN_REPAINT = 10 has entry points and a table layout of its own (dmme_chain_step and
+ * dmme_chain_update refuse it):
+ *   step_coef float[n_rows+1][8], per loop index (i runs n_rows .. 1, one row per downward transition; alpha = abar_a / abar_b, beta = 1 - alpha):
+ *             {c0 = 1/sqrt(alpha), c1 = beta/sqrt(1 - abar_a), c2 = sqrt(beta) (0 where b = 0), ka = sqrt(abar_b), ks = sqrt(1 - abar_b),
+ *              r0 = sqrt(abar_c / abar_b), r1 = sqrt(1 - abar_c / abar_b) (exactly 1, 0 where c = b), -}
+ *   t_table   int64[n_rows+1]: t_table[i] = tau_a, what the network is evaluated at; t_table[0] = 0
+ *   known, mask   fp32, B * chw values each in x's layout, read only: the image whose pixels are kept and m in [0, 1] (1: known, 0: generate)
+ *   the update, every product, sum and difference rounded to fp32 on its own (no fma):
+ *     u  = c0 (x - c1 e);      u = u + c2 z0          only where c2 != 0        the reverse step of the unknown pixels
+ *     k  = ka x0;              k = k + ks z1          only where ks != 0        the known pixels at level b
+ *     y  = m k + (1 - m) u
+ *     x' = y;                  x' = r0 y + r1 z2      only where r1 != 0        the folded jump b -> c
+ *   normals   a step owns THREE streams of B*chw normals: stream s of quad q is the draw at Philox counter offset + s * (B*chw/4) + q, so
+ *             dmme_randn(z3, 3*B*chw, seed, offset) writes exactly the [3][B*chw] block the eager form reads.  Which streams a step uses is
+ *             decided by its row (c2, ks, r1), not by t; a stream whose coefficient is zero is neither drawn nor read.  The chain form moves
+ *             the offset by 3 * B*chw/4 per step whatever the row used.
+ *   out_planes  as for DPM-Solver++: 1 (eps), or 2 (an IDDPM network's (eps, v): the eps plane is used).
+ * dmme_repaint_step: the eager twin (row: 8 floats in HOST memory; z3: the [3][B*chw] block, nullable only where the row uses no stream),
+ * bit-identical to dmme_chain_update_repaint, the chain form (row from device memory, normals drawn in the kernel; noise: nullable, a
+ * [3][B*chw] block used in place of the drawn normals - tests).  dmme_repaint_chain_step = dmme_unet_forward (no-grad form) at t = state.t +
+ * dmme_chain_update_repaint; an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan.  chw must be a multiple of 4. */
+enum { DMME_CHAIN_REPAINT = 10 };
+DMME_API int dmme_repaint_step(float* x, const float* model_out, const float* known, const float* mask, const float* z3, const float* row, int B,
+                               int64_t chw, int out_planes, void* stream);
+DMME_API int dmme_chain_update_repaint(float* x, const float* model_out, const float* known, const float* mask, const float* noise,
+                                       const float* step_coef, const int64_t* t_table, void* state, int B, int64_t chw, int out_planes, void* stream);
+DMME_API int dmme_repaint_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* known,
+                                     const float* mask, const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
 
