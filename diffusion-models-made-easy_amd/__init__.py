@@ -8,7 +8,10 @@ __version__ = "0.1.0"
 from . import _lib  # noqa: F401
 from .common.noise import gaussian, gaussian_like, uniform_int, pad  # noqa: F401
 from .common.norm import denorm, norm  # noqa: F401
-from . import models, diffusion_models, equations, lit_modules, lr_scheduler, data_modules  # noqa: F401
+from .common.vis import make_history, save_png  # noqa: F401
+from . import models, diffusion_models, equations, lit_modules, lr_scheduler, data_modules, callbacks  # noqa: F401
+from .diffusion_models import HistoryRecorder, history_ordinals  # noqa: F401
+from .callbacks import GenerateImage  # noqa: F401
 from .data_modules import CIFAR10  # noqa: F401
 from .diffusion_models import DDPM, DDIM, IDDPM, GeneralizedDDIM, DPMSolverPP  # noqa: F401
 from .diffusion_models import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401
@@ -21,4 +24,4 @@ from .guidance import ClassifierFreeDDPM, ClassifierFreeDDIM, ClassifierFreeDPMS
 
 __all__ = ["gaussian", "gaussian_like", "uniform_int", "pad", "denorm", "norm", "UNet", "DDPM", "DDIM", "LitDDPM", "LitDDIM", "IDDPM", "LitIDDPM", "CIFAR10", "GeneralizedDDIM",
            "ConditionalUNet", "ClassifierFreeDDPM", "ClassifierFreeDDIM", "LitClassifierFreeDDPM", "DPMSolverPP", "ClassifierFreeDPMSolver",
-           "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows"]
+           "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows", "make_history", "save_png", "HistoryRecorder", "history_ordinals", "GenerateImage"]

@@ -499,6 +499,8 @@ int launch_cls_head_wgrad(const float* dlog, const float* pooled, const float* r
 int launch_log_softmax_grad(const float* logits, const int64_t* y, int B, int K, int mode, float scale, float* loss, float* dlog, int* status,
                             hipStream_t s);
 int launch_image_batch(const uint8_t* data, const int64_t* idx, const uint8_t* flip, int B, int C, int H, int W, float* out, hipStream_t s);
+int launch_grid_tile(const float* x, int B, int C, int H, int W, int cell0, int cell_stride, int xmaps, int ymaps, int pad, int out_kind, int raw,
+                     void* canvas, hipStream_t s);
 int launch_iddpm_loss(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int B,
                       int64_t chw, float w_simple, float w_vlb, float* loss, float* d_out, float gscale, float* scratch, hipStream_t s);
 int launch_iddpm_loss_rows(const float* out, const float* x_t, const float* x_0, const float* target, const int64_t* t, const float* coef, int T,

@@ -946,4 +946,57 @@ int launch_image_batch(const uint8_t* data, const int64_t* idx, const uint8_t* f
     return DMME_OK;
 }
 
+// ------------------------------------------------------------------ output side: an image batch into the cells of a grid canvas
+// canvas[cg][row*(H+pad)+pad+y][col*(W+pad)+pad+x] = value(x[b][c][y][x]) with cell = cell0 + b*cell_stride, row = cell / xmaps,
+// col = cell % xmaps: torchvision's make_grid layout (a single channel written to all three).  value: the reference's denorm,
+// clip((x + 1) / 2, 0, 1) (src/dmme/common/norm.py:9-11), or x itself where `raw`; as fp32 or as save_image's byte
+// (uint8) clamp(v * 255 + 0.5, 0, 255).  Separately rounded adds and multiplies: both forms match numpy float32 bit for bit.  Image
+// pixels only: the padding keeps what the canvas held.  One thread per source pixel; canvas rows have no alignment to rely on
+// (width xmaps*(W+pad)+pad), so the stores are scalar.
+template <typename OUT>
+__global__ void __launch_bounds__(256) grid_tile_kernel(const float* __restrict__ x, int C, int H, int W, int64_t total, int cell0, int cell_stride,
+                                                        int xmaps, int pad, int raw, int64_t gw, int64_t plane, OUT* __restrict__ canvas) {
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+        const int px = (int)(q % W);
+        int64_t r = q / W;
+        const int py = (int)(r % H);
+        r /= H;
+        const int c = (int)(r % C), b = (int)(r / C);
+        float v = x[q];
+        if (!raw) {
+            v = __fmul_rn(__fadd_rn(v, 1.0f), 0.5f);
+            v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+        }
+        OUT o;
+        if constexpr (sizeof(OUT) == 1) {
+            const float s = __fadd_rn(__fmul_rn(v, 255.0f), 0.5f);
+            o = (OUT)(s >= 255.0f ? 255.0f : (s > 0.0f ? s : 0.0f));  // (a NaN becomes 0)
+        } else {
+            o = v;
+        }
+        const int64_t cell = cell0 + (int64_t)b * cell_stride;
+        const int64_t at = ((cell / xmaps) * (H + pad) + pad + py) * gw + (cell % xmaps) * (int64_t)(W + pad) + pad + px;
+        if (C == 1) {
+            canvas[at] = o;
+            canvas[plane + at] = o;
+            canvas[2 * plane + at] = o;
+        } else {
+            canvas[c * plane + at] = o;
+        }
+    }
+}
+int launch_grid_tile(const float* x, int B, int C, int H, int W, int cell0, int cell_stride, int xmaps, int ymaps, int pad, int out_kind, int raw,
+                     void* canvas, hipStream_t s) {
+    const int64_t total = (int64_t)B * C * H * W;
+    const int64_t gw = (int64_t)xmaps * (W + pad) + pad, plane = ((int64_t)ymaps * (H + pad) + pad) * gw;
+    if (out_kind == 1)
+        hipLaunchKernelGGL(grid_tile_kernel<uint8_t>, dim3(grid_for(total)), dim3(256), 0, s, x, C, H, W, total, cell0, cell_stride, xmaps, pad, raw, gw, plane,
+                           (uint8_t*)canvas);
+    else
+        hipLaunchKernelGGL(grid_tile_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, x, C, H, W, total, cell0, cell_stride, xmaps, pad, raw, gw, plane,
+                           (float*)canvas);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
 }  // namespace dmme

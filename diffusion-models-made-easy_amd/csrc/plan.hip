@@ -1285,7 +1285,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 112; }  // 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 113; }  // 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1792,6 +1792,18 @@ DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64
                               float* out, void* stream) {
     DMME_REQUIRE(data && idx && out && n_images > 0 && B > 0 && C > 0 && H > 0 && W > 0, DMME_ERR_INVALID, "image_batch: bad argument");
     return launch_image_batch(data, idx, flip, B, C, H, W, out, (hipStream_t)stream);
+}
+
+DMME_API int dmme_grid_tile(const float* x, int B, int C, int H, int W, int cell0, int cell_stride, int xmaps, int ymaps, int pad, int out_kind, int raw,
+                            void* canvas, void* stream) {
+    DMME_REQUIRE(x && canvas, DMME_ERR_INVALID, "grid_tile: null pointer");
+    DMME_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && xmaps > 0 && ymaps > 0 && pad >= 0, DMME_ERR_INVALID,
+                 "grid_tile: %d images of %d x %d x %d into %d x %d cells, padding %d", B, C, H, W, ymaps, xmaps, pad);
+    DMME_REQUIRE(cell0 >= 0 && cell_stride >= 1 && cell0 + (int64_t)(B - 1) * cell_stride < (int64_t)xmaps * ymaps, DMME_ERR_INVALID,
+                 "grid_tile: cells %d + b * %d of %d images do not fit a grid of %d x %d", cell0, cell_stride, B, ymaps, xmaps);
+    DMME_REQUIRE(out_kind == 0 || out_kind == 1, DMME_ERR_INVALID, "grid_tile: out_kind %d (0: float32, 1: uint8)", out_kind);
+    DMME_REQUIRE(raw == 0 || raw == 1, DMME_ERR_INVALID, "grid_tile: raw %d (0: denorm, 1: the values as they are)", raw);
+    return launch_grid_tile(x, B, C, H, W, cell0, cell_stride, xmaps, ymaps, pad, out_kind, raw, canvas, (hipStream_t)stream);
 }
 
 DMME_API int dmme_iddpm_loss(const float* model_out, const float* x_t, const float* x_0, const float* target, const int64_t* t,

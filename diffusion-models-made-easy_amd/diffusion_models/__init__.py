@@ -1,4 +1,4 @@
-from .ddpm import DDPM  # noqa: F401
+from .ddpm import DDPM, HistoryRecorder, history_ordinals  # noqa: F401
 from .ddim import DDIM, GeneralizedDDIM  # noqa: F401
 from .iddpm import IDDPM  # noqa: F401
 from .dpm_solver import DPMSolverPP  # noqa: F401

@@ -74,14 +74,14 @@ class DDIM(DDPM):
         return self._tau_dev[i]
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
-        """S-step strided chain (reference: diffusion_models/ddim.py:79-99)"""
-        return self._decode_chain(gaussian(img_size, device=self.beta.device), self.sub_timesteps)
+    def generate(self, img_size: Tuple[int, int, int, int], history=None) -> Tensor:
+        """S-step strided chain (reference: diffusion_models/ddim.py:79-99); `history`: a HistoryRecorder for its frames"""
+        return self._decode_chain(gaussian(img_size, device=self.beta.device), self.sub_timesteps, history)
 
-    def _decode_chain(self, x: Tensor, start: int) -> Tensor:
+    def _decode_chain(self, x: Tensor, start: int, history=None) -> Tensor:
         """`start` reverse steps from loop index `start`, in place on x or through the captured step"""
         runner = self._buffered_runner("_runner", x.shape, x.device)
-        return self._run_chain(runner, x, start, start, lambda i: self._ddim_update(x, self.model(x, self.tau_tensor(i, x.device)), i))
+        return self._run_chain(runner, x, start, start, lambda i: self._ddim_update(x, self.model(x, self.tau_tensor(i, x.device)), i), history)
 
 
 class GeneralizedDDIM(DDIM):
@@ -169,14 +169,16 @@ class GeneralizedDDIM(DDIM):
         return self._buffered_runner("_enc_runner", shape, dev, spec=lambda: (_lib.CHAIN_GDDIM, self._encode_tables()), buf="_enc_buf")
 
     @torch.no_grad()
-    def decode(self, x: Tensor, start: Optional[int] = None) -> Tensor:
+    def decode(self, x: Tensor, start: Optional[int] = None, history=None) -> Tensor:
         r"""x_0 from x_{tau_start} (start = S by default): `start` reverse steps; draws noise where eta > 0"""
         S = self.sub_timesteps
         start = S if start is None else int(start)
         if not 0 <= start <= S:
             raise ValueError(f"decode: start {start} outside 0..{S}")
         x = x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
-        return x if start == 0 else self._decode_chain(x, start)
+        if start == 0 and history is not None:
+            raise ValueError("decode: start = 0 runs no chain to record")
+        return x if start == 0 else self._decode_chain(x, start, history)
 
     @torch.no_grad()
     def encode(self, x0: Tensor, upto: Optional[int] = None) -> Tensor:
@@ -192,9 +194,9 @@ class GeneralizedDDIM(DDIM):
         return self._run_chain(self._encode_runner(x.shape, x.device), x, S, upto, step)
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
+    def generate(self, img_size: Tuple[int, int, int, int], history=None) -> Tensor:
         """S-step chain from pure noise; with eta = 0 nothing but x_T is drawn, with eta > 0 one span of normals per step"""
-        return self.decode(gaussian(img_size, device=self.beta.device))
+        return self.decode(gaussian(img_size, device=self.beta.device), history=history)
 
     @torch.no_grad()
     def interpolate(self, xa: Tensor, xb: Tensor, weights) -> Tensor:

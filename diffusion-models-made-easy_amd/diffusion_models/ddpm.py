@@ -14,6 +14,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
+from ..common import vis
 from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..equations.ddpm import linear_schedule, sampling_coefficients
 
@@ -49,6 +50,55 @@ def chain_draws(kind: int, rows) -> bool:
     if kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_GDDIM_CFG):
         return any(r[2] != 0.0 for r in rows)
     return True
+
+
+def history_ordinals(count: int, vis_length: int):
+    """the step ordinals after which a chain of `count` steps keeps a frame (0: before the first step), `vis_length` of them where the
+    chain is long enough.  With count = T this is the reference's `save_t` and its final append (callbacks/generate.py:73-84): a frame
+    in front of the step from t = int(T / (L-1) * i) is a frame after T - t steps.  Ordinals, not timesteps: RePaint's index is not monotone."""
+    count, L = int(count), int(vis_length)
+    if count < 0 or L < 1:
+        raise ValueError(f"history_ordinals: count = {count} steps, vis_length = {L}")
+    return sorted({count - int(count / (L - 1) * i) for i in range(L - 1, 0, -1)} | {count})
+
+
+class HistoryRecorder:
+    """The frames of one chain as a grid on the device: a canvas allocated and zeroed once, and per kept frame ONE dmme_grid_tile launch
+    (denorm + placement, as float32 or as uint8) on the chain's stream - no allocation, no synchronisation, no copy to the host while
+    the chain runs.  Image b of frame k sits in row b, column k (cell k + b * len(ordinals)), which is what `make_history` builds from
+    the list of denormed frames the reference's callback collects; with a single ordinal the images are laid out as `make_history`
+    lays out a single history.  `canvas` is read after the chain; a later chain overwrites every cell.  `recorded`: frames of the last chain."""
+
+    def __init__(self, n_images: int, C: int, H: int, W: int, ordinals, out_kind: int = 0, device="cuda"):
+        self.ordinals = sorted({int(s) for s in ordinals})
+        if n_images < 1 or not self.ordinals or self.ordinals[0] < 0:
+            raise ValueError(f"HistoryRecorder: {n_images} images, ordinals {self.ordinals}")
+        self.n_images, self.image = int(n_images), (int(C), int(H), int(W))
+        L = self.stride = len(self.ordinals)
+        if L == 1:
+            self.xmaps = min(vis.history_nrow(self.n_images), self.n_images)
+            self.ymaps = -(-self.n_images // self.xmaps)
+        else:
+            self.xmaps, self.ymaps = L, self.n_images
+        self.pad = 0 if L * self.n_images == 1 else vis.PAD  # (make_grid returns a batch of one image unpadded)
+        self.canvas = vis.new_canvas(*self.image, self.xmaps, self.ymaps, self.pad, out_kind, device)
+        self._slot = {s: k for k, s in enumerate(self.ordinals)}
+        self.recorded = 0
+
+    def begin(self, x: Tensor, count: int) -> None:
+        """a chain of `count` steps on the buffer `x` starts: refuses what would leave a cell unwritten or write outside the canvas"""
+        if tuple(x.shape[1:]) != self.image or x.shape[0] < self.n_images or x.device != self.canvas.device:
+            raise ValueError(f"HistoryRecorder: built for {self.n_images} images of {self.image} on {self.canvas.device}, the chain runs on {tuple(x.shape)} on {x.device}")
+        if self.ordinals[-1] > count:
+            raise ValueError(f"HistoryRecorder: ordinal {self.ordinals[-1]} in a chain of {count} steps")
+        self.recorded = 0
+
+    def at(self, s: int, x: Tensor) -> None:
+        """`s` steps are done and `x` holds their result: keep its first n_images images if that frame is wanted"""
+        k = self._slot.get(s)
+        if k is not None:
+            vis.grid_tile(x[: self.n_images], self.canvas, k, self.stride, self.xmaps, self.ymaps, self.pad)
+            self.recorded += 1
 
 
 class ChainRunner(ChainTables):
@@ -139,12 +189,21 @@ class ChainRunner(ChainTables):
         self.plan.overwritten()
         return self.x
 
-    def run(self, first: int, count: int):
-        """`count` steps from loop index `first` downwards, drawing from torch's CUDA generator like the eager loop"""
+    def run(self, first: int, count: int, recorder: Optional[HistoryRecorder] = None):
+        """`count` steps from loop index `first` downwards, drawing from torch's CUDA generator like the eager loop.  `recorder`: the
+        frames it wants (keyed on the number of steps done) go to its canvas, one launch each on this stream between two replays."""
+        if recorder is not None:
+            recorder.begin(self.x, count)
         seed, off = philox_reserve(self.x.device, self.noise_numel * count) if self.draws else (0, 0)
         self.set(first, seed, off)
-        for _ in range(count):
-            self.step()
+        if recorder is None:
+            for _ in range(count):
+                self.step()
+        else:
+            for s in range(count):
+                recorder.at(s, self.x)
+                self.step()
+            recorder.at(count, self.x)
         # replayed graphs do not pass through the C entry points that look at the level engine's status word: one synchronisation
         # per chain (the caller reads the images next anyway), then the check - a chain never returns numbers from a launch that
         # gave up on a hand-off (DmmeError instead)
@@ -201,6 +260,11 @@ class DDPM(nn.Module):
         rows = [(self._c1[t], self._c2[t] if t > 0 else 0.0, self._sigma[t], 0.0) for t in range(T + 1)]  # index 0 is never stepped from
         return T, rows, list(range(T + 1))
 
+    def chain_length(self) -> int:
+        """steps of the chain `generate` runs (DDPM: T; the strided samplers: their sub-steps; RePaint: its walk's downward steps):
+        what `history_ordinals` spreads a recorder's frames over"""
+        return int(self._chain_tables()[0])
+
     def timestep_tensor(self, t: int, device) -> Tensor:
         """shape-(1,) device view holding t: indexes a resident arange instead of building `torch.tensor([t])` (a host-to-device
         copy per step in the reference, lit_modules/ddpm.py:77)"""
@@ -241,14 +305,21 @@ class DDPM(nn.Module):
             setattr(self, buf, b)
         return self.chain_runner(b, slot=slot, spec=spec)
 
-    def _run_chain(self, runner: Optional[ChainRunner], x: Tensor, first: int, count: int, step) -> Tensor:
+    def _run_chain(self, runner: Optional[ChainRunner], x: Tensor, first: int, count: int, step, history: Optional[HistoryRecorder] = None) -> Tensor:
         """`count` steps from loop index `first` downwards: x into the runner's buffer, one captured step (UNet + noise + update +
-        state advance) replayed, a clone of the result; without a runner the eager `step(index)`, in place on x, index by index"""
+        state advance) replayed, a clone of the result; without a runner the eager `step(index)`, in place on x, index by index.
+        `history`: a recorder for the chain's frames, on the same step ordinals either way"""
         if runner is not None:
             runner.x.copy_(x)
-            return runner.run(first, count).clone()
-        for i in range(first, first - count, -1):
+            return runner.run(first, count, history).clone()
+        if history is not None:
+            history.begin(x, count)
+        for s, i in enumerate(range(first, first - count, -1)):
+            if history is not None:
+                history.at(s, x)
             step(i)
+        if history is not None:
+            history.at(count, x)
         return x
 
     def _once_via_runner(self, x_t: Tensor, index: int) -> Optional[Tensor]:
@@ -328,12 +399,12 @@ class DDPM(nn.Module):
         return self._reverse_update(x, eps, t, None)
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
-        """run the full T-step chain from pure noise (reference: diffusion_models/ddpm.py:113-133)"""
+    def generate(self, img_size: Tuple[int, int, int, int], history: Optional[HistoryRecorder] = None) -> Tensor:
+        """run the full T-step chain from pure noise (reference: diffusion_models/ddpm.py:113-133); `history`: a recorder for its frames"""
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
         runner, T = self._buffered_runner("_runner", img_size, dev), self.timesteps
-        return self._run_chain(runner, x_t, T, T, lambda t: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(t, dev)), t, None))
+        return self._run_chain(runner, x_t, T, T, lambda t: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(t, dev)), t, None), history)
 
     def forward(self, x: Tensor, t: Tensor) -> Tensor:
         return self.model(x, t)

@@ -205,31 +205,40 @@ class DPMSolverPP(DDIM):
             eps = self.model(out, self.tau_tensor(i, out.device))
         return self._dpm_update(out, eps, i, torch.empty_like(out), False)
 
-    def _eager_chain(self, x: Tensor, start: int) -> Tensor:
+    def _eager_chain(self, x: Tensor, start: int, recorder=None) -> Tensor:
         """the host loop, bit-identical to the captured chain: the same update on the same scalars, the history valid after the first step"""
         hist = torch.empty_like(x)
+        if recorder is not None:
+            recorder.begin(x, start)
         for k, i in enumerate(range(start, 0, -1)):
+            if recorder is not None:
+                recorder.at(k, x)
             self._dpm_update(x, self.model(x, self.tau_tensor(i, x.device)), i, hist, k > 0)
+        if recorder is not None:
+            recorder.at(start, x)
         return x
 
-    def _decode_chain(self, x: Tensor, start: int) -> Tensor:
+    def _decode_chain(self, x: Tensor, start: int, recorder=None) -> Tensor:
         runner = self._buffered_runner("_runner", x.shape, x.device)
         if runner is None:
-            return self._eager_chain(x, start)
+            return self._eager_chain(x, start, recorder)
         runner.x.copy_(x)
-        return runner.run(start, start).clone()
+        return runner.run(start, start, recorder).clone()
 
     @torch.no_grad()
-    def decode(self, x: Tensor, start: Optional[int] = None) -> Tensor:
-        r"""x_0 from x_{tau_start} (start = n_steps by default): `start` solver steps, the first of them first order"""
+    def decode(self, x: Tensor, start: Optional[int] = None, history=None) -> Tensor:
+        r"""x_0 from x_{tau_start} (start = n_steps by default): `start` solver steps, the first of them first order.  `history`: a
+        HistoryRecorder for the chain's frames (not the x0 history of `sampling_step`)"""
         n = self.n_steps
         start = n if start is None else int(start)
         if not 0 <= start <= n:
             raise ValueError(f"decode: start {start} outside 0..{n}")
         x = x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
-        return x if start == 0 else self._decode_chain(x, start)
+        if start == 0 and history is not None:
+            raise ValueError("decode: start = 0 runs no chain to record")
+        return x if start == 0 else self._decode_chain(x, start, history)
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
-        """the n_steps chain from pure noise; nothing but x_T is drawn"""
-        return self.decode(gaussian(img_size, device=self.beta.device))
+    def generate(self, img_size: Tuple[int, int, int, int], history=None) -> Tensor:
+        """the n_steps chain from pure noise; nothing but x_T is drawn.  `history`: a HistoryRecorder for the chain's frames"""
+        return self.decode(gaussian(img_size, device=self.beta.device), history=history)

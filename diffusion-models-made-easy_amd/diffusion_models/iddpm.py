@@ -175,16 +175,17 @@ class IDDPM(DDPM):
         return self.chain_runner(x, use_graph, slot=f"_runner_k{K}", spec=lambda: (_lib.CHAIN_IDDPM, self._respaced_tables(K)))
 
     @torch.no_grad()
-    def generate(self, img_size, sample_steps: Optional[int] = None) -> Tensor:
+    def generate(self, img_size, sample_steps: Optional[int] = None, history=None) -> Tensor:
         """the full T-step chain from pure noise, or with `sample_steps` = K the strided chain over K << T timesteps with the learned
-        variance (Nichol & Dhariwal 2021, section 4): K network evaluations instead of T, graph-replayed like the full chain"""
+        variance (Nichol & Dhariwal 2021, section 4): K network evaluations instead of T, graph-replayed like the full chain.
+        `history`: a HistoryRecorder for the chain's frames"""
         if sample_steps is None:
-            return super().generate(img_size)
+            return super().generate(img_size, history=history)
         K, rows, ttab = self._respaced_tables(int(sample_steps))
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
         runner = self._buffered_runner(f"_runner_k{K}", img_size, dev, spec=lambda: (_lib.CHAIN_IDDPM, (K, rows, ttab)))  # (on the full chain's buffer)
-        return self._run_chain(runner, x_t, K, K, lambda k: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(ttab[k], dev)), ttab[k], None, rows[k]))
+        return self._run_chain(runner, x_t, K, K, lambda k: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(ttab[k], dev)), ttab[k], None, rows[k]), history)
 
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()

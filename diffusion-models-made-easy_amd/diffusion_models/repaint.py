@@ -119,12 +119,12 @@ class PaintChainRunner(ChainRunner):
         )
         self.plan.overwritten()
 
-    def paint(self, x: Tensor, known: Tensor, mask: Tensor, first: int) -> Tensor:
+    def paint(self, x: Tensor, known: Tensor, mask: Tensor, first: int, recorder=None) -> Tensor:
         """the chain from loop index `first` down to 0 on copies of the three images; a new tensor"""
         self.x.copy_(x)
         self.known.copy_(known)
         self.mask.copy_(mask)
-        return self.run(first, first).clone()
+        return self.run(first, first, recorder).clone()
 
 
 class RePaint(DDPM):
@@ -198,44 +198,51 @@ class RePaint(DDPM):
         return self._buffered_runner(slot, shape, dev, spec=lambda: (_lib.CHAIN_REPAINT, tables), buf=slot + "_buf")
 
     # ------------------------------------------------------------------ chains
-    def _eager_chain(self, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None) -> Tensor:
+    def _eager_chain(self, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None, history=None) -> Tensor:
         """the host loop over dmme_repaint_step, in place on x: normals from dmme_randn at the offsets the captured chain's state walks
         through, so the two agree bit for bit under the same seed"""
         n, rows, ttab = tables if tables is not None else self._tables
         first = n if first is None else int(first)
         lib, numel = _lib.lib(), x.numel()
+        if history is not None:
+            history.begin(x, first)
         seed, off = philox_reserve(x.device, STREAMS * numel * first)
         tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
         z3 = torch.empty(STREAMS * numel, dtype=torch.float32, device=x.device)
         for k, i in enumerate(range(first, 0, -1)):
+            if history is not None:
+                history.at(k, x)
             eps = self.model(x, tt[i]).detach().to(torch.float32).contiguous()
             draws = _row_draws(rows[i])
             if draws:
                 _lib.check(lib.dmme_randn(_lib.ptr(z3), z3.numel(), seed, off + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
             _lib.check(lib.dmme_repaint_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(z3 if draws else None), _row_arg(rows[i]),
                                              x.shape[0], x[0].numel(), eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_repaint_step")
+        if history is not None:
+            history.at(first, x)
         return x
 
-    def _chain(self, slot: str, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None) -> Tensor:
+    def _chain(self, slot: str, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None, history=None) -> Tensor:
         first = (tables if tables is not None else self._tables)[0] if first is None else first
         runner = self._paint_runner(slot, x.shape, x.device, tables)
         if runner is None:
-            return self._eager_chain(x, known, mask, tables, first)
-        return runner.paint(x, known, mask, first)
+            return self._eager_chain(x, known, mask, tables, first, history)
+        return runner.paint(x, known, mask, first, history)
 
     @torch.no_grad()
-    def inpaint(self, x0: Tensor, mask: Tensor) -> Tensor:
+    def inpaint(self, x0: Tensor, mask: Tensor, history=None) -> Tensor:
         r"""the image batch whose pixels equal `x0` where `mask` is 1 (bit for bit) and are generated, in harmony with them, where it is 0:
-        x_T ~ N(0, I), then the whole RePaint walk through the captured step.  mask: (B|1, C|1, H, W), values in [0, 1]."""
+        x_T ~ N(0, I), then the whole RePaint walk through the captured step.  mask: (B|1, C|1, H, W), values in [0, 1].
+        `history`: a HistoryRecorder for the walk's frames, keyed on the step ordinal (`n_rows` steps: the level is not monotone)."""
         known = self._image(x0, "inpaint")
         m = self._mask(mask, known)
-        return self._chain("_runner", gaussian(known.shape, device=known.device), known, m)
+        return self._chain("_runner", gaussian(known.shape, device=known.device), known, m, history=history)
 
     @torch.no_grad()
-    def edit(self, x_guide: Tensor, strength: float, mask: Optional[Tensor] = None) -> Tensor:
+    def edit(self, x_guide: Tensor, strength: float, mask: Optional[Tensor] = None, history=None) -> Tensor:
         r"""SDEdit: the guide noised to level k = max(1, round(strength n)) and denoised by the plain walk k -> 0 (no resampling,
         whatever `resamples` is).  strength in (0, 1]: 1 forgets the guide, small values stay close to it.  With a mask the pixels where
-        it is 1 are kept exactly (SDEdit's masked variant)."""
+        it is 1 are kept exactly (SDEdit's masked variant).  `history`: a HistoryRecorder for the frames of the `edit_level(strength)` steps."""
         strength = float(strength)
         if not 0.0 < strength <= 1.0:
             raise ValueError(f"strength = {strength!r} outside (0, 1]")
@@ -244,17 +251,17 @@ class RePaint(DDPM):
         k = self.edit_level(strength)
         t = torch.full((guide.shape[0],), self._tau_host[k], dtype=torch.int64, device=guide.device)
         x_k = self._noised(guide, t, gaussian_like(guide), target=False)[2]
-        return self._chain("_edit_runner", x_k, guide, m, self._plain_tables, k)
+        return self._chain("_edit_runner", x_k, guide, m, self._plain_tables, k, history)
 
     def edit_level(self, strength: float) -> int:
         """the level SDEdit starts from"""
         return min(self.n_levels, max(1, int(round(float(strength) * self.n_levels))))
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int]) -> Tensor:
+    def generate(self, img_size: Tuple[int, int, int, int], history=None) -> Tensor:
         """`inpaint` with nothing known: the walk from pure noise"""
         zeros = torch.zeros(tuple(img_size), dtype=torch.float32, device=self.beta.device)
-        return self._chain("_runner", gaussian(img_size, device=zeros.device), zeros, zeros)
+        return self._chain("_runner", gaussian(img_size, device=zeros.device), zeros, zeros, history=history)
 
     def sampling_step(self, *a, **kw):
         raise NotImplementedError("RePaint runs whole chains: inpaint / edit / generate")

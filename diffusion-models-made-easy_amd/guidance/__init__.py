@@ -224,7 +224,7 @@ class _Guided:
         x = x_t.detach().to(torch.float32).clone().contiguous()
         return self._eager_update(x, eps, g, index, noise)
 
-    def _guided_generate(self, img_size, y, n_steps: int) -> Tensor:
+    def _guided_generate(self, img_size, y, n_steps: int, history=None) -> Tensor:
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
         labels = _labels(y, img_size[0], self.classifier.num_classes, dev)
@@ -232,7 +232,7 @@ class _Guided:
         runner.x.copy_(x_t)
         runner.y.copy_(labels)
         runner.status.zero_()
-        out = runner.run(n_steps, n_steps).clone()
+        out = runner.run(n_steps, n_steps, history).clone()
         _check_status(runner.status, "generate")
         return out
 
@@ -260,9 +260,9 @@ class ClassifierGuidedDDPM(_Guided, DDPM):
         return self._guided_step(x_t, step, self.timestep_tensor(step, x_t.device), y, noise)
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
-        """the T-step guided chain from pure noise, one captured graph per step"""
-        return self._guided_generate(img_size, y, self.timesteps)
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the T-step guided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        return self._guided_generate(img_size, y, self.timesteps, history)
 
 
 class ClassifierGuidedDDIM(_Guided, DDIM):
@@ -288,6 +288,6 @@ class ClassifierGuidedDDIM(_Guided, DDIM):
         return self._guided_step(x_tau_i, idx, self.tau_tensor(idx, x_tau_i.device), y, None)
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
-        """the S-step guided strided chain, one captured graph per step"""
-        return self._guided_generate(img_size, y, self.sub_timesteps)
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the S-step guided strided chain, one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        return self._guided_generate(img_size, y, self.sub_timesteps, history)

@@ -189,7 +189,7 @@ class _ClassifierFree:
                                             x[0].numel(), _lib.stream_ptr()), "dmme_cfg_step")
         return x[:B]
 
-    def _cfg_generate(self, img_size, y, n_steps: int) -> Tensor:
+    def _cfg_generate(self, img_size, y, n_steps: int, history=None) -> Tensor:
         dev = self.beta.device
         model = self.model
         B = int(img_size[0])
@@ -203,7 +203,7 @@ class _ClassifierFree:
         if batched:
             runner.x[B:].copy_(x_t)
             runner.y[B:].fill_(model.null_label)
-        out = runner.run(n_steps, n_steps)[:B].clone()
+        out = runner.run(n_steps, n_steps, history)[:B].clone()  # (a recorder keeps the first B images of the 2B the buffer holds)
         model.check_labels()
         return out
 
@@ -240,9 +240,9 @@ class ClassifierFreeDDPM(_ClassifierFree, DDPM):
     denoise_once = _needs_labels("denoise_once")
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
-        """the T-step guided chain from pure noise, one captured graph per step"""
-        return self._cfg_generate(img_size, y, self.timesteps)
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the T-step guided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        return self._cfg_generate(img_size, y, self.timesteps, history)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
         return self.model(x, t, y)
@@ -278,9 +278,9 @@ class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
     denoise_once, encode, decode, interpolate = (_needs_labels(n) for n in ("denoise_once", "encode", "decode", "interpolate"))
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
-        """the S-step guided strided chain from pure noise, one captured graph per step"""
-        return self._cfg_generate(img_size, y, self.sub_timesteps)
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the S-step guided strided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        return self._cfg_generate(img_size, y, self.sub_timesteps, history)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
         return self.model(x, t, y)
@@ -331,9 +331,9 @@ class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
         return x.clone()
 
     @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y) -> Tensor:
-        """the n_steps guided chain from pure noise, one captured graph per step"""
-        return self._cfg_generate(img_size, y, self.n_steps)
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the n_steps guided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        return self._cfg_generate(img_size, y, self.n_steps, history)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
         return self.model(x, t, y)

@@ -59,7 +59,20 @@ def train_step(module, optimizer, scheduler, x0, clip=None, reduce=True, exchang
     return loss
 
 
-def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=None, ckpt_path=None, save_path=None):
+def write_preview(module, callback, directory: str, step: int) -> str:
+    """`directory`/step_<step>.png: the callback's history grid (callbacks.GenerateImage.grid: one recorded chain of the module's
+    current weights, uint8 on the device, one copy to the host at the end)"""
+    from .common.vis import save_png
+
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, f"step_{step}.png")
+    save_png(path, callback.grid(module, out_kind=1))
+    return path
+
+
+def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=None, ckpt_path=None, save_path=None, preview=None):
+    """`preview`: (GenerateImage, directory, N) - rank 0 writes a history grid every N optimiser steps (steps, not the callback's
+    epochs: synthetic-data runs have no epochs); None: nothing changes"""
     dev = next(module.parameters()).device
     module.train()
     opts, scheds = module.configure_optimizers()
@@ -95,6 +108,8 @@ def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=N
             if conditional:
                 y = batch[1]
         loss = train_step(module, opt, sched, x0, clip, y=y)
+        if preview is not None and (step + 1) % preview[2] == 0 and D.env_rank_world()[0] == 0:
+            print(json.dumps({"step": step + 1, "preview": write_preview(module, preview[0], preview[1], step + 1)}), flush=True)
         if (step + 1) % log_every == 0 or step + 1 == max_steps:
             torch.cuda.synchronize()
             if hasattr(model, "check_engine"):

@@ -13,6 +13,7 @@ checkpoint callbacks, ...):
   data.init_args.batch_size                         -> synthetic batches of that size (default), or with `--data config`
                                                        the YAML's data module (dmme.CIFAR10: HBM-resident uint8 set, GPU flip + norm)
   trainer.max_steps, gradient_clip_val, precision, log_every_n_steps, devices
+  trainer.callbacks: dmme.callbacks.GenerateImage   -> dmme_amd.GenerateImage (what `fit --preview-dir` samples)
   seed_everything
 
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml [--max-steps N] [--batch-size B]
@@ -22,6 +23,8 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dpm++ --sample-steps 20   (DPM-Solver++(2M); any of the four configs)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
+  python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml --preview-dir DIR --preview-every N   (a history grid DIR/step_<n>.png every N optimiser steps)
 """
 
 from __future__ import annotations
@@ -165,6 +168,25 @@ def _instantiate(spec: Any):
     return spec
 
 
+def _callbacks(specs) -> list:
+    """the entries of trainer.callbacks this package has a counterpart for (`dmme.callbacks.GenerateImage`), instantiated; Lightning's
+    own (ModelCheckpoint: --save-checkpoint, LearningRateMonitor) are not"""
+    return [_instantiate(s) for s in specs or [] if isinstance(s, dict) and str(s.get("class_path", "")).startswith("dmme.")]
+
+
+def preview_callback(conf: Dict[str, Any], module, image_size=None):
+    """the GenerateImage the previews of `fit` come from: the YAML's entry when there is one, else one built from the model (its
+    channels, the data module's image size, the process's timesteps) and the callback's defaults"""
+    from .callbacks import GenerateImage
+
+    for cb in conf.get("callbacks") or []:
+        if isinstance(cb, GenerateImage):
+            return cb
+    dm = module.diffusion_model
+    hw = image_size or conf["image_size"]
+    return GenerateImage((dm.model.in_channels, hw, hw), dm.timesteps)
+
+
 def parse_config(path: str) -> Dict[str, Any]:
     with open(path) as f:
         cfg = yaml.safe_load(f)
@@ -190,6 +212,7 @@ def parse_config(path: str) -> Dict[str, Any]:
         "devices": trainer.get("devices", 1),
         "seed": cfg.get("seed_everything", 1337),
         "ckpt_path": cfg.get("ckpt_path"),
+        "callbacks": _callbacks(trainer.get("callbacks")),
     }
 
 
@@ -318,6 +341,12 @@ def main(argv=None):
     ap.add_argument("--jump-length", type=int, default=None, help="sample --sampler repaint: levels a resampling jump climbs (default 10)")
     ap.add_argument("--resamples", type=int, default=None, help="sample --sampler repaint: times each stretch of --jump-length levels is walked (default 10)")
     ap.add_argument("--save", default=None, help="sample: write the images to this .npy file (float32, (B, C, H, W))")
+    ap.add_argument("--grid", default=None, help="sample: write the images to this PNG file as a grid (every sampler; goes with --save)")
+    ap.add_argument("--vis-length", type=int, default=1,
+                    help="sample --grid: 1 (default) the final images in rows; L > 1 the denoising history, one row per image and up to L frames of its chain per row")
+    ap.add_argument("--preview-dir", default=None, help="fit: write history grids of freshly sampled images to DIR/step_<n>.png (rank 0; the samples draw from the run's random stream)")
+    ap.add_argument("--preview-every", type=int, default=None,
+                    help="fit --preview-dir: every N optimiser steps - steps, not the epochs of the YAML's GenerateImage entry: synthetic-data runs have no epochs")
     ap.add_argument("--eta", type=float, default=None, help="sample --sampler ddim-paper: 0 (default) deterministic ... 1 DDPM's posterior variance")
     ap.add_argument("--solver-order", type=int, default=None, choices=[1, 2], help="sample --sampler dpm++: 2 (default) multistep second order, 1 first order")
     ap.add_argument("--tau-schedule", default=None, choices=["linear", "quadratic", "logsnr"], help="sample --sampler dpm++: the timestep grid (default logsnr)")
@@ -333,6 +362,16 @@ def main(argv=None):
     _check_paint_args(args)
     if args.save is not None and args.command != "sample":
         raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
+    if args.command != "sample" and (args.grid is not None or args.vis_length != 1):
+        raise SystemExit("--grid / --vis-length belong to `sample` (fit: --preview-dir)")
+    if args.vis_length < 1 or (args.vis_length != 1 and args.grid is None):
+        raise SystemExit("--vis-length L >= 1 goes with --grid OUT.png")
+    if args.grid is not None and args.steps is not None:
+        raise SystemExit("--grid records whole chains: --steps does not go with it")
+    if (args.preview_dir is None) != (args.preview_every is None) or (args.preview_dir is not None and args.command != "fit"):
+        raise SystemExit("fit --preview-dir DIR --preview-every N go together")
+    if args.preview_every is not None and args.preview_every < 1:
+        raise SystemExit("--preview-every must be at least 1")
 
     from . import _lib
     from . import distributed as D
@@ -388,10 +427,22 @@ def main(argv=None):
         t0 = time.perf_counter()
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)
+        rec = None
+        if args.grid is not None:
+            from .diffusion_models import HistoryRecorder, history_ordinals
+
+            if args.sampler == "sdedit":
+                count = dm.edit_level(args.strength)
+            elif args.sample_steps is not None and args.sampler == "config":
+                count = dm._respaced_tables(args.sample_steps)[0]  # (Improved DDPM's strided chain)
+            else:
+                count = dm.chain_length()
+            rec_shape = tuple(image.shape) if args.sampler in PAINT_SAMPLERS else shape
+            rec = HistoryRecorder(rec_shape[0], *rec_shape[1:], history_ordinals(count, args.vis_length), out_kind=1)
         if args.sampler == "repaint":
-            imgs = dm.inpaint(image, mask)
+            imgs = dm.inpaint(image, mask, history=rec)
         elif args.sampler == "sdedit":
-            imgs = dm.edit(image, args.strength, mask)
+            imgs = dm.edit(image, args.strength, mask, history=rec)
         elif getattr(module, "conditional", False):
             if args.steps is not None or args.sampler == "ddim-paper" or (args.sample_steps is not None and args.sampler != "dpm++"):
                 raise SystemExit("class-conditional configs sample whole chains: --labels / --guidance-scale only")
@@ -400,15 +451,15 @@ def main(argv=None):
             labels = [int(v) for v in args.labels.split(",")] if args.labels else [dm.model.null_label]
             if len(labels) == 1:
                 labels = labels * args.num_images
-            imgs = module.generate(shape, labels)
+            imgs = dm.generate(shape, labels, history=rec)
         elif args.labels is not None or args.guidance_scale is not None:
             raise SystemExit("--labels / --guidance-scale need a class-conditional config (LitClassifierFreeDDPM)")
         elif args.sampler == "dpm++":
-            imgs = dm.generate(shape)
+            imgs = dm.generate(shape, history=rec)
         elif args.sample_steps is not None:
-            imgs = module.generate(shape, sample_steps=args.sample_steps)
+            imgs = dm.generate(shape, sample_steps=args.sample_steps, history=rec)
         elif args.steps is None:
-            imgs = module.generate(shape)
+            imgs = dm.generate(shape, history=rec)
         else:
             import dmme_amd
 
@@ -421,6 +472,10 @@ def main(argv=None):
             import numpy as np
 
             np.save(args.save, imgs.detach().to(torch.float32).cpu().numpy())
+        if rec is not None:
+            from .common.vis import save_png
+
+            save_png(args.grid, rec.canvas)
         print(json.dumps({"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3),
                           "finite": bool(torch.isfinite(imgs).all())}))
         return 0
@@ -439,8 +494,11 @@ def main(argv=None):
             dm.synthetic = True
         dm.setup("fit")
         loader = dm.train_dataloader()
+    preview = None
+    if args.preview_dir is not None:
+        preview = (preview_callback(conf, module, args.image_size), args.preview_dir, args.preview_every)
     fit(module, batch_size=B, max_steps=steps, clip=conf["gradient_clip_val"], log_every=conf["log_every_n_steps"], loader=loader,
-        ckpt_path=ckpt_path, save_path=args.save_checkpoint)
+        ckpt_path=ckpt_path, save_path=args.save_checkpoint, preview=preview)
     return 0
 
 

@@ -393,6 +393,21 @@ DMME_API int dmme_mse_loss(const float* eps, const float* target, int64_t numel,
 DMME_API int dmme_image_batch(const uint8_t* data, int64_t n_images, const int64_t* idx, const uint8_t* flip, int B, int C, int H, int W,
                      float* out, void* stream);
 
+/* ---- output side: an image batch into the cells of a grid canvas -----------------------------------------------------
+ * What the reference's GenerateImage callback does on the host per kept frame (callbacks/generate.py:80: denorm(x_t.clone()))
+ * and torchvision's make_grid(padding = pad, pad_value = 0) does once at the end (common/vis.py:25-28), as one launch per frame:
+ *   canvas: (Cg, ymaps*(H+pad)+pad, xmaps*(W+pad)+pad), Cg = 3 where C == 1 (the channel is written three times), else C;
+ *   image b of x (B, C, H, W; fp32, contiguous) goes to cell k = cell0 + b*cell_stride, at row k / xmaps, column k % xmaps, its
+ *   top-left pixel at (row*(H+pad)+pad, col*(W+pad)+pad).
+ * value: raw = 0: v = clip((x + 1) / 2, 0, 1), the reference's denorm (common/norm.py:9-11); raw = 1: v = x (frames denormed already).
+ * out_kind 0: canvas is fp32 and receives v; out_kind 1: canvas is uint8 and receives (uint8) clamp(v*255 + 0.5, 0, 255), truncated
+ * (torchvision's save_image).  Every add and multiply is rounded on its own, so both forms equal numpy float32 bit for bit.
+ * Only image pixels are written: the padding keeps what the canvas held (zero it once).  Any H, W; pad >= 0 (pad = 0, one cell: a
+ * copy).  DMME_ERR_INVALID: a null pointer, a non-positive size, a cell outside 0 .. xmaps*ymaps-1, cell_stride < 1, out_kind or raw
+ * outside {0, 1}. */
+DMME_API int dmme_grid_tile(const float* x, int B, int C, int H, int W, int cell0, int cell_stride, int xmaps, int ymaps, int pad, int out_kind,
+                   int raw, void* canvas, void* stream);
+
 /* ---- one replayable denoising step ---------------------------------------------------------------------
  * The reference's sampling loops run on the host: `for t in range(T, 0, -1)` around `sampling_step`
  * (diffusion_models/ddpm.py:130, ddim.py:96, iddpm.py), `LitDDPM.forward` builds `torch.tensor([t])` - a host-to-device copy -
