@@ -130,6 +130,7 @@ PROTOTYPES = {
     "dmme_grad_unpack_bf16": (_i, [_vp, _i64, _vp, _vp]),
     "dmme_unet_debug_read": (_i, [_vp, _vp, C.c_char_p, _vp, _i64, C.POINTER(_i64), _vp]),
     "dmme_unet_debug_read_grad": (_i, [_vp, _vp, C.c_char_p, _vp, _i64, C.POINTER(_i64), _vp]),
+    "dmme_unet_debug_read_norm_stats": (_i, [_vp, _vp, C.c_char_p, _vp, _i64, C.POINTER(_i64), _vp]),
     "dmme_dropout_masks": (_i, [_vp, _u64, _u64, _vp, _vp]),
     "dmme_randn": (_i, [_vp, _i64, _u64, _u64, _vp]),
     "dmme_q_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),

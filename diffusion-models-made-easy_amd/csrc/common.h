@@ -209,6 +209,10 @@ struct ConvArgs {
     // partials, [N][gn_tiles][Cout/gn_cg][2], written by the LDS-staged epilogue; merged by gn_finalize_parts
     float* gn_part;
     int gn_cg, gn_tiles;
+    // fp32 tensors: 1 - the epilogue's per-thread moments are raw sums (s2 - s1 * mean) instead of sums about the thread's first value.
+    // Set by precision="fp16r32" plans only: their fp32 level keeps the arithmetic (and with it the fp16 rounding sequence of every level
+    // below) that the mode's 1e-3 figures were measured with; statistics at the 1e-6 level are far inside that budget.
+    int gn_raw_moments;
     // diagnostic (null: off): per-phase cycle stamps of a few workgroups, [slot][64] (dmme_debug_set_stamps)
     long long* stamps;
     // split-K scratch (null: off): fp32 partial outputs [ksplit][N*Hout*Wout][Cout] of layers with too few output tiles to fill

@@ -586,6 +586,11 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, int co0, 
     // fused GroupNorm partials: every thread owns ONE 16-byte channel vector (NT % VPR == 0), so it keeps
     // running sum / sum of squares of the values it stores (two halves of the vector separately)
     float s1a = 0.f, s2a = 0.f, s1b = 0.f, s2b = 0.f;
+    // fp32 tensors: the sums run about the thread's first value.  With |group mean| several standard deviations, raw s2 - s1 * mean loses
+    // (mean / std)^2 of fp32's precision (rstd 7e-7 .. 1e-6 off at |mean| / std = 8; tests/test_gpu_block_forward.py); the pivot is
+    // within a few standard deviations of every value the thread holds.  (16-bit tensors: 8-bit / 11-bit values, exact squares.
+    // ConvArgs::gn_raw_moments: the pivot stays 0, which is the raw sums bit for bit.)
+    float piv = 0.f;
     f32x2 q1a = {0.f, 0.f}, q2a = {0.f, 0.f}, q1b = {0.f, 0.f}, q2b = {0.f, 0.f};  // (bf16: the same sums as pairs of adjacent channels)
     int cnt_items = 0;
     auto item = [&](int it, const uint4* pv) __attribute__((always_inline)) {
@@ -603,10 +608,12 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, int co0, 
                 v += rv;
             }
             *reinterpret_cast<f32x4*>(dst + off) = v;
+            if (cnt_items == 1 && !a.gn_raw_moments) piv = v[0];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                s1a += v[e];
-                s2a = fmaf(v[e], v[e], s2a);
+                const float d = v[e] - piv;
+                s1a += d;
+                s2a = fmaf(d, d, s2a);
             }
         } else {
             // 16-bit tensors: pairs (the two halves of an output dword = adjacent channels) through packed fp32 instructions - residual
@@ -678,6 +685,7 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, int co0, 
             cntA *= 2.f;
         }
         float meanA = s1a / cntA, m2A = s2a - s1a * meanA;
+        if constexpr (sizeof(T) == 4) meanA += piv;  // (M2 does not move with the pivot)
         float meanB = s1b / cntB, m2B = s2b - s1b * meanB;
         // Lanes VPR apart in a wave own the same channel vector (every thread stored the same number of items): merge them
         // pairwise with shuffles - equal counts make Chan's formula mean = (m1 + m2) / 2, M2 = M2a + M2b + (m1 - m2)^2 n / 2 -

@@ -88,22 +88,37 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T* __restrict__ s
         gstat[tid] = acc * inv_cnt;
     }
     __syncthreads();
-    // ---- pass 2: centred second moment ----
+    // ---- pass 2: centred second moment, and the first moment of the same differences: what pass 1's long fp32 sums lost of the mean
+    // (|mean| >> std: ~1e-6 of a standard deviation at 64x64 maps) comes back as sum (x - m) / cnt ----
+    float r1[EPV];
 #pragma unroll
     for (int j = 0; j < EPV; ++j) {
         const float m = gstat[(c0 + j) / cg];
-        float s = 0.f;
+        float s = 0.f, r = 0.f;
 #pragma unroll
         for (int sw = 0; sw < GN_MAX_SWEEPS; ++sw) {
             if (sw < nsweeps) {
                 const float d = v[sw][j] - m;
                 s = fmaf(d, d, s);
+                r += d;
             }
         }
         e[j] = s;
+        r1[j] = r;
     }
 #pragma unroll
     for (int j = 0; j < EPV; ++j) red[tid * EPV + j] = e[j];
+    __syncthreads();
+    float m2 = 0.f;
+    if (tid < groups) {
+        for (int c = tid * cg; c < (tid + 1) * cg; ++c) {
+            const int sl = c / EPV, j = c % EPV;
+            for (int pr = 0; pr < ppw; ++pr) m2 += red[(pr * VPP + sl) * EPV + j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < EPV; ++j) red[tid * EPV + j] = r1[j];
     __syncthreads();
     if (tid < groups) {
         float acc = 0.f;
@@ -111,9 +126,10 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T* __restrict__ s
             const int sl = c / EPV, j = c % EPV;
             for (int pr = 0; pr < ppw; ++pr) acc += red[(pr * VPP + sl) * EPV + j];
         }
+        const float corr = acc * inv_cnt;
         float* o = partial + (((int64_t)n * nchunks + chunk) * groups + tid) * 2;
-        o[0] = gstat[tid];
-        o[1] = acc;
+        o[0] = gstat[tid] + corr;
+        o[1] = m2 - acc * corr;  // (about the corrected mean)
     }
 }
 
@@ -125,16 +141,20 @@ __global__ void __launch_bounds__(256) gn_finalize_kernel(const float* __restric
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N * groups) return;
     const int n = i / groups, g = i % groups, cg = C / groups;
+    // the chunk means are merged about the first one: every update of a running mean of magnitude |mean| >> std rounds it by half a unit
+    // in ITS last place (64 chunks of a 64x64 map: 1e-6 of a standard deviation at |mean| / std = 8); the differences are std-sized
+    const float piv = partial[(((int64_t)n * nchunks) * groups + g) * 2];
     float na = 0.f, mean = 0.f, m2 = 0.f;
     const float m = (float)chunk_cnt;
     for (int k = 0; k < nchunks; ++k) {
         const float* p = partial + (((int64_t)n * nchunks + k) * groups + g) * 2;
-        const float delta = p[0] - mean;
+        const float delta = (p[0] - piv) - mean;
         const float tot = na + m;
         mean += delta * (m / tot);
         m2 += p[1] + delta * delta * (na * m / tot);
         na = tot;
     }
+    mean += piv;
     const float rstd = 1.0f / sqrtf(m2 / na + eps);
     if (mean_rstd) {
         mean_rstd[(int64_t)i * 2] = mean;

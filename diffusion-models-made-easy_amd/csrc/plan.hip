@@ -719,6 +719,7 @@ void fill_conv(const dmme_plan* P, const Op& o, const char* packed, const float*
             }
         }
     }
+    a.gn_raw_moments = P->mix ? 1 : 0;
     if (o.dst == -2) {
         a.dst = y;
         a.out_nchw = 1;
@@ -1534,6 +1535,24 @@ DMME_API int dmme_unet_debug_read_grad(const dmme_plan* plan, const void* bwd_wo
     if (numel_out) *numel_out = n;
     return launch_nhwc_to_nchw(plan->dtype, (const char*)bwd_workspace + plan->gt_off[it->second], plan->B, t.C, t.H * t.W, dst,
                                (hipStream_t)stream);
+}
+
+// {mean, rstd} rows of a GroupNorm as the forward left them for the backward (Op::gn_mr), by the norm's state_dict prefix
+DMME_API int dmme_unet_debug_read_norm_stats(const dmme_plan* plan, const void* workspace, const char* name, float* dst,
+                                             int64_t numel_cap, int64_t* numel_out, void* stream) {
+    DMME_REQUIRE(plan && workspace && name && dst, DMME_ERR_INVALID, "debug_read_norm_stats: null argument");
+    const std::string key = std::string(name) + ".weight";
+    for (const Op& o : plan->ops) {
+        if (o.kind != OP_GN || o.gn_gamma < 0 || plan->params[o.gn_gamma].name != key) continue;
+        const int64_t n = (int64_t)plan->B * plan->cfg.num_groups * 2;
+        DMME_REQUIRE(n <= numel_cap, DMME_ERR_INVALID, "debug_read_norm_stats: destination too small (%lld > %lld)", (long long)n,
+                     (long long)numel_cap);
+        DMME_CHECK_HIP(hipMemcpyAsync(dst, (const char*)workspace + o.gn_mr, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (numel_out) *numel_out = n;
+        return DMME_OK;
+    }
+    set_error("debug_read_norm_stats: no GroupNorm named '%s'", name);
+    return DMME_ERR_INVALID;
 }
 
 DMME_API int dmme_dropout_masks(const dmme_plan* plan, uint64_t seed, uint64_t offset, float* masks, void* stream) {

@@ -579,6 +579,18 @@ class UNet(nn.Module):
         _lib.check(plan.lib.dmme_unet_debug_read(plan.h, _lib.ptr(plan.workspace), name.encode(), _lib.ptr(buf), cap, C.byref(n), _lib.stream_ptr()), "dmme_unet_debug_read")
         return buf[: n.value].clone()
 
+    def debug_norm_stats(self, name: str) -> Tensor:
+        """the {mean, rstd} rows (B, num_groups, 2) the last forward kept for the backward of the GroupNorm `name` ("<block>.conv1.0",
+        "<block>.conv2.0", "<block>.attention.norm", "output_conv.0"); needs a forward with autograd (parity tests;
+        include/dmme_hip.h: dmme_unet_debug_read_norm_stats)."""
+        plan = self._last_plan
+        G = int(self._cfg.num_groups)
+        buf = torch.empty(plan.B * G * 2, dtype=torch.float32, device=plan.workspace.device)
+        n = C.c_int64()
+        _lib.check(plan.lib.dmme_unet_debug_read_norm_stats(plan.h, _lib.ptr(plan.workspace), name.encode(), _lib.ptr(buf), buf.numel(), C.byref(n),
+                                                            _lib.stream_ptr()), "dmme_unet_debug_read_norm_stats")
+        return buf[: n.value].view(plan.B, G, 2).clone()
+
     def debug_gradient(self, name: str) -> Tensor:
         """fp32 NCHW copy of d loss / d(output of module `name`) from the last backward of the last forward's plan (parity tests;
         include/dmme_hip.h: dmme_unet_debug_read_grad)."""

@@ -309,6 +309,12 @@ DMME_API int dmme_unet_debug_read(const dmme_plan* plan, const void* workspace, 
  * with DMME_ERR_INVALID: the time-MLP backward overwrites d(temb) in place. */
 DMME_API int dmme_unet_debug_read_grad(const dmme_plan* plan, const void* bwd_workspace, const char* name, float* dst,
                          int64_t numel_cap, int64_t* numel_out, void* stream);
+/* The GroupNorm statistics a forward that a backward may follow (dmme_unet_forward) left in the workspace for it: the {mean, rstd}
+ * rows [B][num_groups][2] of the norm `name`, named by its state_dict prefix ("down_layers.3.conv1.0", "<block>.conv2.0" /
+ * "<block>.norm", "<block>.attention.norm", "output_conv.0"), whichever kernel produced them (a norm launch, a conv epilogue, the
+ * consuming conv's merge of the producers' partials, the level engine).  Unknown names fail with DMME_ERR_INVALID. */
+DMME_API int dmme_unet_debug_read_norm_stats(const dmme_plan* plan, const void* workspace, const char* name, float* dst,
+                         int64_t numel_cap, int64_t* numel_out, void* stream);
 
 /* ---- the device random stream (dmme_dropout_masks, dmme_randn, the noise of dmme_chain_update) -----------------------
  * Philox4x32-10 (Salmon et al., SC'11).  A draw is a span (seed, offset, numel); the offset counts quads of 4 values.

@@ -208,6 +208,31 @@ def gen_unet_full(out):
         out[f"full_actdigest::{k}"] = synth.digest(v)
 
 
+def gen_unet_peaked(out):
+    """the default UNet with a sharp softmax in every attention block (tests/stress_weights.py: peaked): output rows and per-module
+    digests of the imported reference at B = 2, per-image timesteps"""
+    from tests.stress_weights import peaked
+
+    cfg, seed, a = O.UNetConfig(), 23, 3.0
+    net, sd = ref_unet(cfg, seed)
+    net.load_state_dict(peaked(sd, cfg, a), strict=True)
+    net.eval()
+    out["peaked_seed"] = np.int64(seed)
+    out["peaked_a"] = np.float64(a)
+    out["peaked_xseed"] = np.int64(11)
+    x = synth.normal(11, (2, 3, 32, 32))
+    t = torch.tensor([13, 900])
+    acts, hs = hook_outputs(net)
+    with torch.no_grad():
+        y = net(x, t)
+    for h in hs:
+        h.remove()
+    out["peaked_t"] = t.numpy()
+    out["peaked_y"] = y.numpy()
+    for k, v in acts.items():
+        out[f"peaked_actdigest::{k}"] = synth.digest(v)
+
+
 def gen_layers(out):
     """Stand-alone reference modules at real channel counts (digests)."""
     cfg = O.UNetConfig()
@@ -535,6 +560,7 @@ def main():
     groups = {
         "unet_tiny": gen_unet_tiny,
         "unet_full": gen_unet_full,
+        "unet_peaked": gen_unet_peaked,
         "layers": gen_layers,
         "schedules": gen_schedules,
         "train_tiny": gen_train,

@@ -20,7 +20,7 @@ Error measure: relative L2 ||g - g_ref|| / ||g_ref|| per tensor, worst per role;
 """
 
 import time
-from typing import Dict, List, Tuple
+from typing import Dict
 
 import pytest
 import torch
@@ -29,6 +29,7 @@ import torch.nn.functional as F
 from oracle import iddpm as OI
 from oracle import synth
 from oracle import unet as O
+from tests.block_local import _rounder, _shapes, _walk, _wround
 
 torch.set_num_threads(min(16, torch.get_num_threads()))
 
@@ -61,52 +62,6 @@ BOUNDS = {
     "fp16": {"exact_w": 2e-4, "exact_b": 1e-6, "inner_w": 1e-3, "inner_b": 1e-3, "gn": 1.2e-3, "dgrad": 1e-3, "time": 4e-4},
     "fp32": {"exact_w": 4e-6, "exact_b": 4e-7, "inner_w": 4e-6, "inner_b": 4e-6, "gn": 4e-6, "dgrad": 4e-6, "time": 4e-6},
 }
-
-
-def _rounder(precision):
-    """straight-through rounding to the 16-bit type (identity for fp32): forward value rounded, gradient passed unchanged"""
-    if precision == "fp32":
-        return lambda t: t
-    dt = torch.bfloat16 if precision == "bf16" else torch.float16
-
-    def q(t):
-        return t + (t.to(dt).to(t.dtype) - t).detach()
-
-    return q
-
-
-def _wround(precision):
-    if precision == "fp32":
-        return lambda w: w.double()
-    dt = torch.bfloat16 if precision == "bf16" else torch.float16
-    return lambda w: w.to(dt).double()
-
-
-def _walk(g) -> Tuple[List[Tuple[object, List[str]]], str]:
-    """(node, names of its input tensors) in forward order, as oracle.unet.unet_forward walks the graph; the last tensor's name"""
-    seq, prev, skips = [], "input_conv", ["input_conv"]
-    for n in g.down:
-        seq.append((n, [prev]))
-        prev = n.prefix
-        skips.append(prev)
-    for n in g.mid:
-        seq.append((n, [prev]))
-        prev = n.prefix
-    for n in g.up:
-        seq.append((n, [prev, skips.pop()] if n.kind == "res" else [prev]))
-        prev = n.prefix
-    return seq, prev
-
-
-def _shapes(g, B, H):
-    """name -> (B, C, H, W) of every named tensor"""
-    out = {"input_conv": (B, g.base, H, H)}
-    seq, _ = _walk(g)
-    for n, ins in seq:
-        h = out[ins[0]][2]
-        h = h // 2 if n.kind == "down" else 2 * h if n.kind == "up" else h
-        out[n.prefix] = (B, n.c_out, h, h)
-    return out
 
 
 def block_reference(arch, cfg, sd, precision, x_in, t, acts, dys, gy, masks):
