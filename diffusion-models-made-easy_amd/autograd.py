@@ -60,6 +60,40 @@ def mse_loss_apply(eps: Tensor, target: Tensor) -> Tensor:
     return _MSEFunction.apply(eps, target)
 
 
+class _WeightedMSEFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out: Tensor, target: Tensor, w_table: Tensor, t: Tensor):
+        o = out.detach().to(torch.float32).contiguous()
+        tg = target.detach().to(torch.float32).contiguous()
+        B = o.size(0)
+        loss = torch.empty(1, dtype=torch.float32, device=o.device)
+        scratch = torch.empty(64 * B, dtype=torch.float32, device=o.device)
+        d_out = torch.empty_like(o) if out.requires_grad else None
+        _lib.check(_lib.lib().dmme_mse_loss_rows(_lib.ptr(o), _lib.ptr(tg), _lib.ptr(w_table), _lib.ptr(t), B, o[0].numel(), _lib.ptr(loss), _lib.ptr(d_out), 1.0,
+                                                 _lib.ptr(scratch), _lib.stream_ptr()), "dmme_mse_loss_rows")
+        ctx.d_out = d_out
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor):
+        d = ctx.d_out
+        ctx.d_out = None
+        return (d * grad_out if d is not None else None), None, None, None
+
+
+def weighted_mse_loss_apply(out: Tensor, target: Tensor, w_table: Tensor, t: Tensor) -> Tensor:
+    """mean over all elements of w_table[t_b] (out - target)^2: the MSE with a weight per image's timestep (min-SNR-gamma), with a HIP
+    gradient (dmme_mse_loss_rows).  w_table: fp32, indexed by t; t: one timestep per image, each inside the table (checked here only
+    for host tensors: a device t is the caller's, as drawn by `training_step`)."""
+    dev = out.device
+    w = w_table.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if t.numel() != out.shape[0] or target.shape != out.shape:
+        raise ValueError(f"weighted_mse_loss_apply: output {tuple(out.shape)}, target {tuple(target.shape)}, {t.numel()} timesteps")
+    if not t.is_cuda and t.numel() and not (0 <= int(t.min()) and int(t.max()) < w.numel()):
+        raise ValueError(f"weighted_mse_loss_apply: a timestep outside the weight table's 0..{w.numel() - 1}")
+    return _WeightedMSEFunction.apply(out, target, w, t.detach().reshape(-1).to(device=dev, dtype=torch.int64).contiguous())
+
+
 class _IDDPMLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model_out: Tensor, x_t: Tensor, x_0: Tensor, target: Tensor, t: Tensor, coef: Tensor, w_simple: float, w_vlb: float):

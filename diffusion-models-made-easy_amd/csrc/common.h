@@ -434,6 +434,9 @@ int launch_randn(float* out, int64_t numel, uint64_t seed, uint64_t offset, hipS
 int launch_dropmask(float* out, int64_t numel, float p, uint64_t seed, uint64_t offset, hipStream_t s);
 int launch_q_sample(const float* x0, const float* z, const float* sqrt_abar, const float* sqrt_1m_abar,
                     const int64_t* t, int B, int64_t chw, float* x_t, float* target, hipStream_t s);
+// prediction.hip: an x0 / v network's output into an eps prediction, in place (dmme_pred_to_eps)
+int launch_pred_to_eps(int pred, float* model_out, const float* x, const float* ab, int T, const int64_t* t, int t_len, int B, int64_t chw,
+                       hipStream_t s);
 int slerp_parts(int64_t chw);  // blocks per image of the first launch of launch_slerp: its scratch holds 3 * B * slerp_parts(chw) floats
 int launch_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, float* scratch, hipStream_t s);
 int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s);

@@ -263,6 +263,10 @@ struct dmme_plan {
     // the workspace the last forward wrote WITHOUT the tensors only a backward pass reads (dmme_unet_forward_nograd, dmme_chain_step):
     // dmme_unet_backward refuses it instead of differentiating stale activations (null: the last forward kept everything)
     mutable const void* nograd_ws = nullptr;
+    // what the network predicts (dmme_unet_plan_set_prediction; host-only): DMME_PRED_X0 / DMME_PRED_V make the capturable chain steps
+    // launch dmme_pred_to_eps over the plan's batch right behind the forward, with this device table [pred_T + 1][2] (the caller's)
+    int pred = DMME_PRED_EPS, pred_T = 0;
+    const float* pred_ab = nullptr;
 };
 
 namespace dmme {

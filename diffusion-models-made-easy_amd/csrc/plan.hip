@@ -1286,7 +1286,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 113; }  // 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 114; }  // 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1708,6 +1708,12 @@ static int chain_step_common(const char* what, const dmme_plan* plan, const void
         if (int rc = lvl_check(plan, what, (hipStream_t)stream, true)) return rc;
     const int64_t* t_dev = (const int64_t*)state + 1;
     if (int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false, labels, status)) return rc;
+    // an x0 / v network: its output becomes an eps prediction here, over the plan's whole batch (a classifier-free plan's 2B images: the
+    // affine map commutes with the guidance mix), and everything behind this line is the eps code
+    if (plan->pred != DMME_PRED_EPS)
+        if (int rc = launch_pred_to_eps(plan->pred, model_out, x, plan->pred_ab, plan->pred_T, t_dev, 1, plan->B,
+                                        (int64_t)plan->cfg.in_channels * plan->H * plan->W, (hipStream_t)stream))
+            return rc;
     if (between)
         if (int rc = between()) return rc;
     return launch_sampler_chain(what, kind, sampler_operands(x, model_out, nullptr, cfg ? plan->B / 2 : plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,

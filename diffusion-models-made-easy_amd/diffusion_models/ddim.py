@@ -22,8 +22,9 @@ from .ddpm import DDPM, ChainRunner, _scalar_index
 class DDIM(DDPM):
     tau: Tensor
 
-    def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic") -> None:
-        super().__init__(model, timesteps)  # start/end are not forwarded, as in the reference (:39)
+    def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", *, prediction: str = "eps",
+                 loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)  # start/end are not forwarded, as in the reference (:39)
         self.sub_timesteps = sub_timesteps
         kind = tau_schedule.lower()
         if kind == "linear":
@@ -48,7 +49,7 @@ class DDIM(DDPM):
     def sampling_step(self, x_tau_i: Tensor, i: Tensor) -> Tensor:
         r"""x_{tau_{i-1}} from x_{tau_i} (reference: diffusion_models/ddim.py:55-77); i has shape (1,)."""
         idx = _scalar_index(i, "an index")
-        eps = self.model(x_tau_i, self.tau[idx].reshape(1))
+        eps = self._eps(x_tau_i, self.tau[idx].reshape(1))
         x = x_tau_i.detach().to(torch.float32).clone()
         return self._ddim_update(x, eps, idx)
 
@@ -64,7 +65,7 @@ class DDIM(DDPM):
         done = self._once_via_runner(x, i)
         if done is not None:
             return done
-        eps = self.model(x, self.tau_tensor(i, x.device))
+        eps = self._eps(x, self.tau_tensor(i, x.device))
         out = x.detach().to(torch.float32).clone()
         return self._ddim_update(out, eps, i)
 
@@ -81,7 +82,7 @@ class DDIM(DDPM):
     def _decode_chain(self, x: Tensor, start: int, history=None) -> Tensor:
         """`start` reverse steps from loop index `start`, in place on x or through the captured step"""
         runner = self._buffered_runner("_runner", x.shape, x.device)
-        return self._run_chain(runner, x, start, start, lambda i: self._ddim_update(x, self.model(x, self.tau_tensor(i, x.device)), i), history)
+        return self._run_chain(runner, x, start, start, lambda i: self._ddim_update(x, self._eps(x, self.tau_tensor(i, x.device)), i), history)
 
 
 class GeneralizedDDIM(DDIM):
@@ -92,12 +93,14 @@ class GeneralizedDDIM(DDIM):
     float64 and rounded to fp32 (include/dmme_hip.h: dmme_gddim_step).  eta = 0 is the deterministic sampler, eta = 1 has DDPM's
     posterior variance.  `encode` runs the eta = 0 step forwards (x_0 -> x_T), `decode` / `generate` backwards, `interpolate`
     slerps two encoded latents and decodes them.  The chains replay one captured step like every other sampler here; the encoding
-    chain is the same device loop over reversed tables.  Noise-prediction networks only (an IDDPM network's learned variance is not used)."""
+    chain is the same device loop over reversed tables.  The update runs on a noise prediction (an IDDPM network's learned variance is not
+    used); an x0 / v network (`prediction=`) is converted to one behind its forward, as in every process."""
 
     _chain_kind = _lib.CHAIN_GDDIM
 
-    def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", eta: float = 0.0) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule)
+    def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", eta: float = 0.0, *,
+                 prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         eta = float(eta)
         if not 0.0 <= eta <= 1.0:
             raise ValueError(f"eta must lie in [0, 1], got {eta}")
@@ -152,7 +155,7 @@ class GeneralizedDDIM(DDIM):
     def sampling_step(self, x_tau_i: Tensor, i: Tensor, noise: Optional[Tensor] = None) -> Tensor:
         r"""x_{tau_{i-1}} from x_{tau_i}; i has shape (1,) as in `DDIM.sampling_step`; `noise` replaces the drawn normals"""
         idx = self._index(_scalar_index(i, "an index"), "sampling_step")
-        eps = self.model(x_tau_i, self.tau[idx].reshape(1))
+        eps = self._eps(x_tau_i, self.tau[idx].reshape(1))
         x = x_tau_i.detach().to(torch.float32).clone()
         return self._gddim_update(x, eps, self._rev_rows[idx], noise, self._draws)
 
@@ -190,7 +193,7 @@ class GeneralizedDDIM(DDIM):
         x = x0.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
         if upto == 0:
             return x
-        step = lambda j: self._gddim_update(x, self.model(x, self._enc_t_tensor(j, x.device)), self._enc_rows[j])
+        step = lambda j: self._gddim_update(x, self._eps(x, self._enc_t_tensor(j, x.device)), self._enc_rows[j])
         return self._run_chain(self._encode_runner(x.shape, x.device), x, S, upto, step)
 
     @torch.no_grad()

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor, nn
 
@@ -121,6 +122,8 @@ class ChainRunner(ChainTables):
         self.kind, (n, rows, ttab) = spec if spec is not None else (process._chain_kind, process._chain_tables())
         self.draws = chain_draws(self.kind, rows)
         self.n_steps = n
+        self.pred = getattr(process, "_pred", _lib.PRED_EPS)
+        self.pred_ab = process._pred_table(x.device).clone() if self.pred != _lib.PRED_EPS else None  # (the runner's own: see _set_prediction)
         super().__init__(rows, ttab, x.device)
         self.out = torch.empty((B, model.out_channels, H, W), dtype=torch.float32, device=x.device)
         self.quads = x.numel() // 4
@@ -130,7 +133,15 @@ class ChainRunner(ChainTables):
         self.capture_error = None  # why this runner launches eagerly although a graph was asked for (None: it does not)
         self._wkey = None
 
+    def _set_prediction(self, plan=None):
+        """tell the plan what its network predicts, in front of every chain-step call: the plan is shared by every process that wraps
+        the same network, so an eps process says so too.  `pred_ab` is the process's device table, held by this runner because the
+        captured graph holds its address."""
+        plan = self.plan if plan is None else plan
+        _lib.check(_lib.lib().dmme_unet_plan_set_prediction(plan.h, self.pred, _lib.ptr(self.pred_ab), self.process.timesteps), "dmme_unet_plan_set_prediction")
+
     def _launch(self, packed):
+        self._set_prediction()
         _lib.check(
             _lib.lib().dmme_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace), self.kind,
                                        _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
@@ -212,15 +223,72 @@ class ChainRunner(ChainTables):
         return self.x
 
 
+LOSS_WEIGHTS = ("uniform", "min-snr")
+
+
+def prediction_table(alpha_bar, prediction: str) -> np.ndarray:
+    """float64 [T+1][2] = (a_t, b_t) with eps = a_t * out + b_t * x_t for a network that predicts `prediction` (include/dmme_hip.h:
+    dmme_pred_to_eps).  x0: a = -sqrt(abar)/sqrt(1-abar), b = 1/sqrt(1-abar), and (NaN, NaN) where abar = 1 (index 0: never stepped
+    from, and a misuse should be loud); v: a = sqrt(abar), b = sqrt(1-abar); eps: the identity (1, 0)."""
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
+    out = np.empty((ab.size, 2), dtype=np.float64)
+    if prediction == "x0":
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[:, 0], out[:, 1] = -np.sqrt(ab) / np.sqrt(1 - ab), 1.0 / np.sqrt(1 - ab)
+        out[ab >= 1.0] = np.nan
+    elif prediction == "v":
+        out[:, 0], out[:, 1] = np.sqrt(ab), np.sqrt(1 - ab)
+    elif prediction == "eps":
+        out[:, 0], out[:, 1] = 1.0, 0.0
+    else:
+        raise ValueError(f"prediction = {prediction!r}; use one of {tuple(_lib.PREDICTIONS)}")
+    return out
+
+
+def loss_weight_table(alpha_bar, prediction: str, loss_weight: str, snr_gamma: float = 5.0) -> np.ndarray:
+    """float64 [T+1] weights of the per-timestep MSE.  "min-snr" (Hang et al. 2023) with snr = abar/(1-abar): min(snr, gamma)/snr for an
+    eps network, min(snr, gamma) for x0, min(snr, gamma)/(snr + 1) for v - the same weight min(snr, gamma) on the x0 error each
+    loss implies.  Where abar = 1 (index 0, snr infinite: never drawn) the limits 0, gamma, 0.  "uniform": ones."""
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
+    if prediction not in _lib.PREDICTIONS:
+        raise ValueError(f"prediction = {prediction!r}; use one of {tuple(_lib.PREDICTIONS)}")
+    if loss_weight == "uniform":
+        return np.ones_like(ab)
+    if loss_weight != "min-snr":
+        raise ValueError(f"loss_weight = {loss_weight!r}; use one of {LOSS_WEIGHTS}")
+    gamma = float(snr_gamma)
+    one = ab >= 1.0
+    snr = np.where(one, 1.0, ab) / np.where(one, 1.0, 1 - ab)
+    clipped = np.minimum(snr, gamma)
+    if prediction == "eps":
+        return np.where(one, 0.0, clipped / snr)
+    if prediction == "x0":
+        return np.where(one, gamma, clipped)
+    return np.where(one, 0.0, clipped / (snr + 1.0))
+
+
 class DDPM(nn.Module):
     beta: Tensor
     alpha: Tensor
     alpha_bar: Tensor
 
-    def __init__(self, model: nn.Module, timesteps: int = 1000, start: float = 0.0001, end: float = 0.02) -> None:
+    def __init__(self, model: nn.Module, timesteps: int = 1000, start: float = 0.0001, end: float = 0.02, *, prediction: str = "eps",
+                 loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        """`prediction`: what the network's output is - "eps" (the noise), "x0", or "v" = sqrt(abar_t) eps - sqrt(1 - abar_t) x0 (Salimans
+        & Ho 2022).  Training regresses on that target; sampling turns the output into an eps prediction with one elementwise launch
+        behind the network (dmme_pred_to_eps) and runs today's updates on it.  `loss_weight`: "uniform" or "min-snr" (Hang et al.
+        2023, clipped at `snr_gamma`)."""
         super().__init__()
         self.model = model
         self.timesteps = timesteps
+        if prediction not in _lib.PREDICTIONS:
+            raise ValueError(f"prediction = {prediction!r}; use one of {tuple(_lib.PREDICTIONS)}")
+        if loss_weight not in LOSS_WEIGHTS:
+            raise ValueError(f"loss_weight = {loss_weight!r}; use one of {LOSS_WEIGHTS}")
+        if isinstance(snr_gamma, bool) or not float(snr_gamma) > 0.0:
+            raise ValueError(f"snr_gamma = {snr_gamma!r}; a positive number")
+        self.prediction, self.loss_weight, self.snr_gamma = prediction, loss_weight, float(snr_gamma)
+        self._pred = _lib.PREDICTIONS[prediction]
 
         beta = linear_schedule(timesteps, start, end).reshape(-1, 1, 1, 1)
         alpha = 1 - beta
@@ -236,6 +304,23 @@ class DDPM(nn.Module):
         self._c1, self._c2, self._sigma = sampling_coefficients(beta, alpha, alpha_bar)
         self._all_t: Optional[Tensor] = None
         self._runner: Optional[ChainRunner] = None
+        self._pred_setup()
+
+    def _pred_setup(self) -> None:
+        """the fp32 device tables of the x0 / v adapter ([T+1][2]) and of the loss weights ([T+1]), folded in float64 from alpha_bar and
+        rounded once; an eps process with uniform weights registers neither"""
+        ab64 = self.alpha_bar.detach().reshape(-1).to(torch.float64).cpu().numpy()
+        if self._pred != _lib.PRED_EPS:
+            tab = prediction_table(ab64, self.prediction).astype(np.float32)
+            self.register_buffer("_pred_ab", torch.from_numpy(tab).reshape(-1).contiguous(), persistent=False)
+        if self.loss_weight != "uniform":
+            w = loss_weight_table(ab64, self.prediction, self.loss_weight, self.snr_gamma).astype(np.float32)
+            self.register_buffer("_loss_w", torch.from_numpy(w).contiguous(), persistent=False)
+
+    def _pred_table(self, device) -> Tensor:
+        """the adapter's table on `device` (the buffer itself where the process lives there)"""
+        tab = self._pred_ab
+        return tab if tab.device == torch.device(device) else tab.to(device)
 
     def _use_alpha_bar(self, alpha_bar) -> None:
         """a (T+1) alpha_bar table in place of the linear schedule's (samplers built over another process's schedule): the buffers and
@@ -250,6 +335,7 @@ class DDPM(nn.Module):
                         ("_sqrt_one_minus_alpha_bar", torch.sqrt(1 - ab).reshape(-1).contiguous())):
             self.register_buffer(name, v, persistent=False)
         self._c1, self._c2, self._sigma = sampling_coefficients(self.beta, self.alpha, self.alpha_bar)
+        self._pred_setup()
 
     # ------------------------------------------------------------------ device-resident loop (replayable step)
     _chain_kind = _lib.CHAIN_DDPM
@@ -344,33 +430,67 @@ class DDPM(nn.Module):
     # ------------------------------------------------------------------ training
     def _noised(self, x_0: Tensor, t: Tensor, noise: Tensor, target: bool = True):
         """forward noising for every loss here: (x0, t, x_t, target) = fp32 x_0, int64 t, x_t ~ q(x_t | x_0) built from `noise`, and the
-        noise as the loss re-derives it from x_t (None with target=False).  The caller draws `t` and `noise`."""
+        regression target of the process's `prediction` (None with target=False): for an eps network the noise as the loss re-derives it
+        from x_t, for x0 the image, for v sqrt(abar_t) noise - sqrt(1 - abar_t) x_0.  The caller draws `t` and `noise`."""
         x0 = x_0.detach().to(torch.float32).contiguous()
         z = noise.detach().to(device=x0.device, dtype=torch.float32).contiguous()
         t = t.to(device=x0.device, dtype=torch.int64).contiguous()
         x_t = torch.empty_like(x0)
         tgt = torch.empty_like(x0) if target else None
-        _lib.check(
-            _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), x0.size(0), x0[0].numel(), _lib.ptr(x_t), _lib.ptr(tgt), _lib.stream_ptr()),
-            "dmme_q_sample",
-        )
+        if self._pred == _lib.PRED_EPS:  # (the launch an eps process has always made; dmme_q_sample_pred writes the same bits)
+            _lib.check(
+                _lib.lib().dmme_q_sample(_lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), x0.size(0), x0[0].numel(), _lib.ptr(x_t), _lib.ptr(tgt), _lib.stream_ptr()),
+                "dmme_q_sample",
+            )
+        else:
+            _lib.check(
+                _lib.lib().dmme_q_sample_pred(self._pred, _lib.ptr(x0), _lib.ptr(z), _lib.ptr(self._sqrt_alpha_bar), _lib.ptr(self._sqrt_one_minus_alpha_bar), _lib.ptr(t), x0.size(0),
+                                              x0[0].numel(), _lib.ptr(x_t), _lib.ptr(tgt), _lib.stream_ptr()),
+                "dmme_q_sample_pred",
+            )
         return x0, t, x_t, tgt
 
+    def _loss(self, out: Tensor, target: Tensor, t: Tensor) -> Tensor:
+        """the MSE of the network output against `_noised`'s target: plain (dmme_mse_loss, what an eps process has always called) with
+        uniform weights, else weighted per image by the table entry of its timestep (dmme_mse_loss_rows)"""
+        from ..autograd import mse_loss_apply, weighted_mse_loss_apply
+
+        if self.loss_weight == "uniform":
+            return mse_loss_apply(out, target)
+        return weighted_mse_loss_apply(out, target, self._loss_w, t)
+
     def training_step(self, x_0: Tensor, t: Optional[Tensor] = None, noise: Optional[Tensor] = None) -> Tensor:
-        r"""L_simple for one batch (reference: diffusion_models/ddpm.py:53-81).
+        r"""L_simple for one batch (reference: diffusion_models/ddpm.py:53-81), on the target of the process's `prediction` and with its
+        `loss_weight`.
 
         `t` / `noise` may be injected for parity tests; by default t ~ randint(1, T)
         (never T itself, as in the reference) and noise ~ N(0, I)."""
-        from ..autograd import mse_loss_apply
-
         if t is None:
             t = uniform_int(1, self.timesteps, x_0.size(0), device=x_0.device)
         if noise is None:
             noise = gaussian_like(x_0)
         _, t, x_t, target = self._noised(x_0, t, noise)
-        return mse_loss_apply(self.model(x_t, t), target)
+        return self._loss(self.model(x_t, t), target, t)
 
     # ------------------------------------------------------------------ sampling
+    def _eps(self, x: Tensor, t: Tensor, *labels, **kw) -> Tensor:
+        """the network's noise prediction at (x, t): its output for an eps network; for an x0 / v network one dmme_pred_to_eps launch on
+        the output (eps = a_t out + b_t x).  Every sampling call of the network goes through here; `forward` returns the raw output."""
+        out = self.model(x, t, *labels, **kw)
+        if self._pred == _lib.PRED_EPS:
+            return out
+        e = out.detach().to(torch.float32).contiguous()
+        if out.requires_grad and e.data_ptr() == out.data_ptr():
+            e = e.clone()  # (never in place on a tensor autograd may still read)
+        xx = x.detach().to(device=e.device, dtype=torch.float32).contiguous()
+        tt = t.detach().reshape(-1).to(device=e.device, dtype=torch.int64).contiguous()
+        B = e.shape[0]
+        if tuple(e.shape) != tuple(xx.shape) or tt.numel() not in (1, B):
+            raise ValueError(f"prediction = {self.prediction!r}: a network output of shape {tuple(e.shape)} for images {tuple(xx.shape)} at {tt.numel()} timesteps")
+        _lib.check(_lib.lib().dmme_pred_to_eps(self._pred, _lib.ptr(e), _lib.ptr(xx), _lib.ptr(self._pred_table(e.device)), self.timesteps, _lib.ptr(tt), tt.numel(), B,
+                                               e[0].numel(), _lib.stream_ptr()), "dmme_pred_to_eps")
+        return e
+
     def _reverse_update(self, x_t: Tensor, eps: Tensor, t: int, noise: Optional[Tensor]) -> Tensor:
         if noise is None:
             noise = gaussian_like(x_t)  # drawn even when t == 1, then unused (reference :107-110)
@@ -383,7 +503,7 @@ class DDPM(nn.Module):
     def sampling_step(self, x_t: Tensor, t: Tensor, noise: Optional[Tensor] = None) -> Tensor:
         r"""one draw from p_theta(x_{t-1} | x_t) (reference: diffusion_models/ddpm.py:83-111); t has shape (1,)"""
         step = _scalar_index(t, "a timestep")
-        eps = self.model(x_t, t.reshape(1))
+        eps = self._eps(x_t, t.reshape(1))
         x = x_t.detach().to(torch.float32).clone()
         return self._reverse_update(x, eps, step, noise)
 
@@ -394,7 +514,7 @@ class DDPM(nn.Module):
         out = self._once_via_runner(x_t, t)
         if out is not None:
             return out
-        eps = self.model(x_t, self.timestep_tensor(t, x_t.device))
+        eps = self._eps(x_t, self.timestep_tensor(t, x_t.device))
         x = x_t.detach().to(torch.float32).clone()
         return self._reverse_update(x, eps, t, None)
 
@@ -404,7 +524,8 @@ class DDPM(nn.Module):
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
         runner, T = self._buffered_runner("_runner", img_size, dev), self.timesteps
-        return self._run_chain(runner, x_t, T, T, lambda t: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(t, dev)), t, None), history)
+        return self._run_chain(runner, x_t, T, T, lambda t: self._reverse_update(x_t, self._eps(x_t, self.timestep_tensor(t, dev)), t, None), history)
 
     def forward(self, x: Tensor, t: Tensor) -> Tensor:
+        """the raw network output (eps, x0 or v, as `prediction` says), not converted: sampling reads it through `_eps`"""
         return self.model(x, t)

@@ -92,6 +92,7 @@ class DPMChainRunner(ChainRunner):
         return super()._carried() + [self.hist]
 
     def _launch(self, packed):
+        self._set_prediction()
         _lib.check(
             _lib.lib().dmme_dpmpp_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace), _lib.ptr(self.hist),
                                              _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
@@ -105,7 +106,8 @@ def _row_arg(row):
 
 
 class DPMSolverPP(DDIM):
-    r"""DPM-Solver++(2M) over any noise-prediction network of the package (an IDDPM network's learned variance is not used).
+    r"""DPM-Solver++(2M) over any noise-prediction network of the package (an IDDPM network's learned variance is not used), or an x0 / v
+    network (`prediction=`: its output becomes an eps prediction behind the forward, from which the rows form the solver's x0).
 
     `tau_schedule`: "linear" / "quadratic" (DDIM's) or "logsnr" (the integer timesteps nearest to `sub_timesteps` points uniform in
     lambda between t = T and t = 1).  The solver's grid is the strictly increasing subsequence of that schedule: `n_steps` may be below
@@ -116,8 +118,8 @@ class DPMSolverPP(DDIM):
     _runner_class = DPMChainRunner
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 20, tau_schedule: str = "logsnr", order: int = 2, clip_x0: bool = False,
-                 alpha_bar: Optional[Tensor] = None) -> None:
-        DDPM.__init__(self, model, timesteps)  # (DDIM's constructor knows two schedules and the linear beta only)
+                 alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        DDPM.__init__(self, model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)  # (DDIM's constructor knows two schedules and the linear beta only)
         kind = str(tau_schedule).lower()
         if kind not in TAU_SCHEDULES:
             raise ValueError(f"tau_schedule = {tau_schedule!r}; use one of {TAU_SCHEDULES}")
@@ -140,7 +142,8 @@ class DPMSolverPP(DDIM):
 
     @classmethod
     def from_process(cls, p: DDPM, **kw):
-        """the solver over `p`'s network and noise schedule (an IDDPM's cosine schedule, for one)"""
+        """the solver over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one) and prediction"""
+        kw.setdefault("prediction", getattr(p, "prediction", "eps"))
         return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
 
     def _make_rows(self, scale: float):
@@ -191,7 +194,7 @@ class DPMSolverPP(DDIM):
         valid = self._history_valid(history, history_valid)
         x = x_tau_i.detach().to(torch.float32).contiguous().clone()
         with torch.no_grad():
-            eps = self.model(x, self.tau[idx].reshape(1))
+            eps = self._eps(x, self.tau[idx].reshape(1))
         return self._dpm_update(x, eps, idx, self._history(x, history), valid)
 
     def denoise_once(self, x: Tensor, i: int) -> Tensor:
@@ -202,7 +205,7 @@ class DPMSolverPP(DDIM):
             return done
         out = x.detach().to(torch.float32).contiguous().clone()
         with torch.no_grad():
-            eps = self.model(out, self.tau_tensor(i, out.device))
+            eps = self._eps(out, self.tau_tensor(i, out.device))
         return self._dpm_update(out, eps, i, torch.empty_like(out), False)
 
     def _eager_chain(self, x: Tensor, start: int, recorder=None) -> Tensor:
@@ -213,7 +216,7 @@ class DPMSolverPP(DDIM):
         for k, i in enumerate(range(start, 0, -1)):
             if recorder is not None:
                 recorder.at(k, x)
-            self._dpm_update(x, self.model(x, self.tau_tensor(i, x.device)), i, hist, k > 0)
+            self._dpm_update(x, self._eps(x, self.tau_tensor(i, x.device)), i, hist, k > 0)
         if recorder is not None:
             recorder.at(start, x)
         return x

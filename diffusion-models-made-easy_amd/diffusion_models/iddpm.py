@@ -44,7 +44,14 @@ class IDDPM(DDPM):
         start: float = 0.0001,
         end: float = 0.02,
         t_sampler: str = "uniform",
+        *,
+        prediction: str = "eps",
+        loss_weight: str = "uniform",
+        snr_gamma: float = 5.0,
     ) -> None:
+        if prediction != "eps" or loss_weight != "uniform":
+            raise ValueError(f"IDDPM predicts (eps, v-interpolated variance) and trains on its hybrid loss: prediction = {prediction!r} / loss_weight = "
+                             f"{loss_weight!r} are not supported (only 'eps' / 'uniform'); x0 / v networks run under DDPM, DDIM, DPMSolverPP, RePaint and the guided processes")
         super().__init__(model, timesteps, start, end)
         if t_sampler not in T_SAMPLERS:
             raise ValueError(f"t_sampler = {t_sampler!r}; use one of {T_SAMPLERS}")

@@ -111,6 +111,7 @@ class PaintChainRunner(ChainRunner):
         self.noise_numel = STREAMS * x.numel()
 
     def _launch(self, packed):
+        self._set_prediction()
         _lib.check(
             _lib.lib().dmme_repaint_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace),
                                                _lib.ptr(self.known), _lib.ptr(self.mask), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
@@ -129,7 +130,7 @@ class PaintChainRunner(ChainRunner):
 
 class RePaint(DDPM):
     r"""RePaint / SDEdit over any unconditional noise-prediction network of the package (an IDDPM network's learned variance is not used:
-    the reverse step's variance is beta).
+    the reverse step's variance is beta), or an x0 / v network (`prediction=`).
 
     `sub_timesteps`: levels of the grid (`sub_timesteps = timesteps`: every timestep, and the reverse half is DDPM's update bit for bit);
     `jump_length`, `resamples`: the walk of `repaint_levels`.  `alpha_bar`: a (T+1) table in place of the linear schedule's
@@ -139,8 +140,8 @@ class RePaint(DDPM):
     _runner_class = PaintChainRunner
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 250, jump_length: int = 10, resamples: int = 10, start: float = 0.0001,
-                 end: float = 0.02, alpha_bar: Optional[Tensor] = None) -> None:
-        super().__init__(model, timesteps, start, end)
+                 end: float = 0.02, alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         for name, v in (("jump_length", jump_length), ("resamples", resamples)):
             if isinstance(v, bool) or int(v) != v or v < 1:
                 raise ValueError(f"{name} = {v!r}; an integer of at least 1")
@@ -161,7 +162,8 @@ class RePaint(DDPM):
 
     @classmethod
     def from_process(cls, p: DDPM, **kw):
-        """RePaint over `p`'s network and noise schedule (an IDDPM's cosine schedule, for one)"""
+        """RePaint over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one) and prediction"""
+        kw.setdefault("prediction", getattr(p, "prediction", "eps"))
         return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
 
     def _make_tables(self, walk):
@@ -212,7 +214,7 @@ class RePaint(DDPM):
         for k, i in enumerate(range(first, 0, -1)):
             if history is not None:
                 history.at(k, x)
-            eps = self.model(x, tt[i]).detach().to(torch.float32).contiguous()
+            eps = self._eps(x, tt[i]).detach().to(torch.float32).contiguous()
             draws = _row_draws(rows[i])
             if draws:
                 _lib.check(lib.dmme_randn(_lib.ptr(z3), z3.numel(), seed, off + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")

@@ -168,6 +168,7 @@ class GuidedChainRunner(ChainRunner):
             raise RuntimeError("guided sampling runs the classifier in eval mode")
         cp = self.cls_plan
         cls_packed = self.cls._bwd_buffers(cp)
+        self._set_prediction()  # (the UNet's plan; the classifier's predicts no noise and is never told)
         _lib.check(
             _lib.lib().dmme_guided_chain_step(self.plan.h, _lib.ptr(packed), cp.h, _lib.ptr(cls_packed), _lib.ptr(cp.packed_bwd), _lib.ptr(self.x),
                                               _lib.ptr(self.out), _lib.ptr(self.plan.workspace), _lib.ptr(cp.workspace), _lib.ptr(cp.bws), _lib.ptr(self.y),
@@ -219,7 +220,7 @@ class _Guided:
 
     def _guided_step(self, x_t: Tensor, index: int, t_dev: Tensor, y, noise: Optional[Tensor]) -> Tensor:
         with torch.no_grad():
-            eps = self.model(x_t, t_dev).to(torch.float32).contiguous()
+            eps = self._eps(x_t, t_dev).to(torch.float32).contiguous()
             g = self.classifier.input_grad(x_t, t_dev, y)
         x = x_t.detach().to(torch.float32).clone().contiguous()
         return self._eager_update(x, eps, g, index, noise)
@@ -244,8 +245,8 @@ class ClassifierGuidedDDPM(_Guided, DDPM):
     _chain_kind = _lib.CHAIN_DDPM_GUIDED
 
     def __init__(self, model: nn.Module, classifier: EncoderClassifier, timesteps: int = 1000, guidance_scale: float = 1.0, start: float = 0.0001,
-                 end: float = 0.02) -> None:
-        super().__init__(model, timesteps, start, end)
+                 end: float = 0.02, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         self.classifier = classifier
         self.guidance_scale = float(guidance_scale)
 
@@ -272,8 +273,8 @@ class ClassifierGuidedDDIM(_Guided, DDIM):
     _chain_kind = _lib.CHAIN_DDIM_GUIDED
 
     def __init__(self, model: nn.Module, classifier: EncoderClassifier, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic",
-                 guidance_scale: float = 1.0) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule)
+                 guidance_scale: float = 1.0, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         self.classifier = classifier
         self.guidance_scale = float(guidance_scale)
 

@@ -63,6 +63,7 @@ class CFGChainRunner(ChainRunner):
 
     def _launch(self, packed):
         lib, plan = _lib.lib(), self.plan
+        self._set_prediction()
         if self.batched and self.dpmpp:
             _lib.check(
                 lib.dmme_cfg_dpmpp_chain_step(plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.y), _lib.ptr(self.out), _lib.ptr(plan.workspace),
@@ -82,6 +83,12 @@ class CFGChainRunner(ChainRunner):
                                            _lib.ptr(plan.workspace), None, 0, _lib.ptr(self.status), _lib.stream_ptr()),
                 "dmme_unet_forward_cond",
             )
+            if self.pred != _lib.PRED_EPS:  # (no chain-step entry point on this path: the adapter's launch is made here, where theirs sits)
+                _lib.check(
+                    lib.dmme_pred_to_eps(self.pred, _lib.ptr(self.out), _lib.ptr(self.x), _lib.ptr(self.pred_ab), self.process.timesteps, _lib.ptr(t_dev), 1,
+                                         self.images, self.x[0].numel(), _lib.stream_ptr()),
+                    "dmme_pred_to_eps",
+                )
             if self.dpmpp:
                 _lib.check(
                     lib.dmme_chain_update_dpmpp(_lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.hist), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
@@ -144,8 +151,6 @@ class _ClassifierFree:
 
         `t` / `noise` / `drop` (bool per image: True drops) may be injected for tests.  Labels given on the host are range-checked
         there; labels already on the device are checked by the kernels (`model.check_labels()` reads their status word)."""
-        from ..autograd import mse_loss_apply
-
         model = self.model
         B, dev, K = x_0.size(0), x_0.device, model.num_classes
         if isinstance(y, Tensor) and y.is_cuda:
@@ -164,7 +169,7 @@ class _ClassifierFree:
         elif self.p_uncond > 0.0:
             labels = self.drop_labels(labels)
         _, t, x_t, target = self._noised(x_0, t, noise)
-        return mse_loss_apply(model(x_t, t, labels, check_labels=False), target)
+        return self._loss(model(x_t, t, labels, check_labels=False), target, t)
 
     # ------------------------------------------------------------------ sampling
     def _predict(self, x_t: Tensor, t_dev: Tensor, y) -> Tuple[Tensor, Tensor, int]:
@@ -181,7 +186,7 @@ class _ClassifierFree:
             x = torch.cat([x, x], dim=0)
             labels = torch.cat([labels, torch.full_like(labels, model.null_label)])
         with torch.no_grad():
-            eps = model(x, t_dev, labels, check_labels=False).to(torch.float32).contiguous()
+            eps = self._eps(x, t_dev, labels, check_labels=False).to(torch.float32).contiguous()
         return x, eps, B
 
     def _cfg_update(self, x: Tensor, eps: Tensor, B: int, row, add_noise: bool, z: Optional[Tensor]) -> Tensor:
@@ -221,8 +226,9 @@ class ClassifierFreeDDPM(_ClassifierFree, DDPM):
 
     _chain_kind = _lib.CHAIN_DDPM_CFG
 
-    def __init__(self, model: nn.Module, timesteps: int = 1000, guidance_scale: float = 1.0, p_uncond: float = 0.1, start: float = 0.0001, end: float = 0.02) -> None:
-        super().__init__(model, timesteps, start, end)
+    def __init__(self, model: nn.Module, timesteps: int = 1000, guidance_scale: float = 1.0, p_uncond: float = 0.1, start: float = 0.0001, end: float = 0.02, *,
+                 prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         self._init_cfg(guidance_scale, p_uncond)
 
     def _chain_tables(self):
@@ -245,6 +251,7 @@ class ClassifierFreeDDPM(_ClassifierFree, DDPM):
         return self._cfg_generate(img_size, y, self.timesteps, history)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
+        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
         return self.model(x, t, y)
 
 
@@ -254,8 +261,8 @@ class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
     _chain_kind = _lib.CHAIN_GDDIM_CFG
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", eta: float = 0.0,
-                 guidance_scale: float = 1.0, p_uncond: float = 0.1) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule, eta)
+                 guidance_scale: float = 1.0, p_uncond: float = 0.1, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, eta, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         self._init_cfg(guidance_scale, p_uncond)
 
     def _chain_tables(self):
@@ -283,6 +290,7 @@ class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
         return self._cfg_generate(img_size, y, self.sub_timesteps, history)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
+        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
         return self.model(x, t, y)
 
 
@@ -292,8 +300,9 @@ class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
     _chain_kind = _lib.CHAIN_DPMPP_CFG
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 20, tau_schedule: str = "logsnr", order: int = 2, clip_x0: bool = False,
-                 alpha_bar: Optional[Tensor] = None, guidance_scale: float = 1.0, p_uncond: float = 0.1) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule, order, clip_x0, alpha_bar)
+                 alpha_bar: Optional[Tensor] = None, guidance_scale: float = 1.0, p_uncond: float = 0.1, *, prediction: str = "eps", loss_weight: str = "uniform",
+                 snr_gamma: float = 5.0) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, order, clip_x0, alpha_bar, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         self._init_cfg(guidance_scale, p_uncond)
 
     def _scaled_rows(self):
@@ -336,4 +345,5 @@ class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
         return self._cfg_generate(img_size, y, self.n_steps, history)
 
     def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
+        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
         return self.model(x, t, y)

@@ -26,13 +26,16 @@ class LitClassifierFreeDDPM(LitDDPM):
         num_classes: int = 10,
         guidance_scale: float = 1.0,
         p_uncond: float = 0.1,
+        prediction: str = "eps",
+        loss_weight: str = "uniform",
+        snr_gamma: float = 5.0,
     ) -> None:
         if diffusion_model is None:
             from ..guidance.cfg import ClassifierFreeDDPM
 
             if model is None:
                 model = ConditionalUNet(num_classes=num_classes)
-            diffusion_model = ClassifierFreeDDPM(model, timesteps, guidance_scale, p_uncond)
+            diffusion_model = ClassifierFreeDDPM(model, timesteps, guidance_scale, p_uncond, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         super().__init__(lr, warmup, decay, diffusion_model)
 
     def forward(self, x_t: Tensor, t, y):

@@ -23,9 +23,12 @@ class LitDDIM(LitDDPM):
         timesteps: int = 1000,
         sample_steps: int = 50,
         tau_schedule: str = "quadratic",
+        prediction: str = "eps",
+        loss_weight: str = "uniform",
+        snr_gamma: float = 5.0,
     ):
         if diffusion_model is None:
             if model is None:
                 model = UNet()
-            diffusion_model = DDIM(model, timesteps, sample_steps, tau_schedule)
+            diffusion_model = DDIM(model, timesteps, sample_steps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         super().__init__(lr, warmup, decay, diffusion_model)

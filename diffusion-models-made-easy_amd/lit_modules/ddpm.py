@@ -34,7 +34,12 @@ class LitDDPM(_Base):
         diffusion_model: Optional[DDPM] = None,
         model: Optional[nn.Module] = None,
         timesteps: int = 1000,
+        prediction: str = "eps",
+        loss_weight: str = "uniform",
+        snr_gamma: float = 5.0,
     ) -> None:
+        """`prediction` / `loss_weight` / `snr_gamma`: what the network predicts ("eps", "x0", "v") and how the loss weighs the timesteps
+        ("uniform", "min-snr"), for the process built here (a `diffusion_model` handed in keeps its own)"""
         super().__init__()
         self.lr = lr
         self.warmup = warmup
@@ -42,11 +47,12 @@ class LitDDPM(_Base):
         if diffusion_model is None:
             if model is None:
                 model = UNet()
-            diffusion_model = DDPM(model, timesteps)
+            diffusion_model = DDPM(model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
         self.diffusion_model = diffusion_model
 
     def forward(self, x_t: Tensor, t: int):
-        r"""denoise once: x_t -> x_{t-1} (reference: lit_modules/ddpm.py:65-79)"""
+        r"""denoise once: x_t -> x_{t-1} (reference: lit_modules/ddpm.py:65-79): a sampling step, whatever the network predicts (the raw
+        network output is `self.diffusion_model(x, t)`)"""
         if hasattr(self.diffusion_model, "denoise_once") and not isinstance(t, torch.Tensor):
             return self.diffusion_model.denoise_once(x_t, t)  # resident timestep table: no host-to-device copy per step
         timestep = torch.as_tensor(t, device=x_t.device).reshape(1)

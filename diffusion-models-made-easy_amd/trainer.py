@@ -24,6 +24,7 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
+  python -m dmme_amd.trainer fit    --config configs/vpred/cifar10.yaml   (a v-prediction network under min-SNR weights; --prediction / --loss-weight / --snr-gamma override any YAML)
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml --preview-dir DIR --preview-every N   (a history grid DIR/step_<n>.png every N optimiser steps)
 """
 
@@ -216,6 +217,28 @@ def parse_config(path: str) -> Dict[str, Any]:
     }
 
 
+PREDICTION_FLAGS = ("prediction", "loss_weight", "snr_gamma")
+
+
+def override_prediction(conf: Dict[str, Any], **overrides) -> None:
+    """--prediction / --loss-weight / --snr-gamma over the YAML: written into the init_args of the block that builds the process (a nested
+    `diffusion_model` where the YAML has one, else the Lit module's own); exits where that class takes no such argument (Improved DDPM)"""
+    given = {k: v for k, v in overrides.items() if v is not None}
+    if not given:
+        return
+    spec = conf["model_spec"] = dict(conf["model_spec"])
+    args = spec["init_args"] = dict(spec.get("init_args") or {})
+    inner = args.get("diffusion_model")
+    if isinstance(inner, dict) and "class_path" in inner:
+        spec = args["diffusion_model"] = dict(inner)
+        args = spec["init_args"] = dict(spec.get("init_args") or {})
+    cls = _resolve(spec["class_path"])
+    missing = [k for k in given if k not in inspect.signature(cls.__init__).parameters]
+    if missing:
+        raise SystemExit(f"{spec['class_path']} takes no {', '.join('--' + k.replace('_', '-') for k in missing)}: it is written for eps prediction and its own loss")
+    args.update(given)
+
+
 def build_module(conf: Dict[str, Any]):
     module = _instantiate(conf["model_spec"])
     unet = module.diffusion_model.model
@@ -357,6 +380,9 @@ def main(argv=None):
     ap.add_argument("--sample-steps", type=int, default=None,
                     help="sample, Improved DDPM configs: a strided chain over this many of the T timesteps, with the learned variance; "
                          "sample --sampler dpm++: the solver's steps")
+    ap.add_argument("--prediction", default=None, choices=["eps", "x0", "v"], help="what the network predicts, over the YAML's `prediction` (default eps)")
+    ap.add_argument("--loss-weight", default=None, choices=["uniform", "min-snr"], help="fit: the loss's weight per timestep, over the YAML's `loss_weight`")
+    ap.add_argument("--snr-gamma", type=float, default=None, help="fit --loss-weight min-snr: the SNR the weight is clipped at (default 5)")
     args = ap.parse_args(argv)
     _check_solver_args(args)
     _check_paint_args(args)
@@ -377,6 +403,7 @@ def main(argv=None):
     from . import distributed as D
 
     conf = parse_config(args.config)
+    override_prediction(conf, prediction=args.prediction, loss_weight=args.loss_weight, snr_gamma=args.snr_gamma)
     if args.sampler in PAINT_SAMPLERS:
         if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
             raise SystemExit(f"--sampler {args.sampler} needs an unconditional config: guided inpainting / editing is not implemented")
@@ -417,7 +444,7 @@ def main(argv=None):
             old = module.diffusion_model
             if not isinstance(old, DDIM):
                 raise SystemExit("--sampler ddim-paper needs a DDIM config (sub_timesteps and a tau schedule)")
-            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta or 0.0).cuda()
+            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta or 0.0, prediction=old.prediction).cuda()
         elif args.sampler == "dpm++":
             module.diffusion_model = _dpm_solver(module, args).cuda()
         elif args.sampler in PAINT_SAMPLERS:

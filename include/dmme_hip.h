@@ -390,6 +390,48 @@ DMME_API int dmme_slerp(const float* xa, const float* xb, const float* w, int n,
 DMME_API int dmme_mse_loss(const float* eps, const float* target, int64_t numel, float* loss, float* d_eps,
                   float grad_scale, float* scratch, void* stream);
 
+/* ---- networks that predict x0 or v instead of the noise (csrc/prediction.hip) -----------------------------------------
+ * Every sampler update of this library is written for a noise prediction.  A network trained to predict x0, or v = sqrt(abar_t) eps -
+ * sqrt(1 - abar_t) x0 (Salimans & Ho 2022), is served by ONE elementwise launch behind its forward that turns the output into the eps
+ * prediction it implies; the update kinds, their tables and their entry points are untouched, and an eps network launches nothing new. */
+enum { DMME_PRED_EPS = 0, DMME_PRED_X0 = 1, DMME_PRED_V = 2 };
+
+/* in place on model_out (B, chw), x: the x_t the network was evaluated on:
+ *   e = (a[t_b] * out) + (b[t_b] * x)      two products and one sum, each rounded to fp32 on its own (no fma)
+ * ab: device fp32 table [T+1][2] = {a_t, b_t}, folded by the host in float64 from alpha_bar and rounded once:
+ *   DMME_PRED_X0:  a = -sqrt(abar)/sqrt(1 - abar), b = 1/sqrt(1 - abar); row 0 (abar_0 = 1) is (NaN, NaN): nothing steps from index 0
+ *   DMME_PRED_V:   a = sqrt(abar),                 b = sqrt(1 - abar)
+ * t: int64 in DEVICE memory, t_len = 1 (every image at t[0]: a chain passes the second word of its loop state) or B (image b at t[b]).
+ * An image whose t lies outside 0..T comes out NaN; the table is not read there.  16-byte accesses where chw % 4 == 0 and both
+ * pointers are 16-byte aligned, element by element otherwise (any chw).  pred == DMME_PRED_EPS is DMME_ERR_INVALID: do not launch. */
+DMME_API int dmme_pred_to_eps(int pred, float* model_out, const float* x, const float* ab, int T, const int64_t* t, int t_len, int B,
+                              int64_t chw, void* stream);
+
+/* host-only state of a plan: what its network predicts.  With DMME_PRED_X0 / DMME_PRED_V every capturable step over the plan
+ * (dmme_chain_step, dmme_cfg_chain_step, dmme_dpmpp_chain_step, dmme_cfg_dpmpp_chain_step, dmme_repaint_chain_step,
+ * dmme_guided_chain_step) launches dmme_pred_to_eps(pred, model_out, x, ab, T, &state.t, 1, plan batch, C*H*W) directly behind the
+ * forward - over all 2B images of a classifier-free plan: the mixing weights 1 - s and s sum to one, so the affine map commutes
+ * with e_u + s (e_c - e_u) - and in front of the classifier pass and the update.  `ab` stays the caller's and must outlive every launch and
+ * every captured graph that holds its address.  A plan is shared by every process that wraps the same network: set the prediction in
+ * front of EVERY chain-step call, DMME_PRED_EPS included (ab is ignored and may be NULL then).  DMME_ERR_UNSUPPORTED: x0 / v on a plan
+ * with more than one output plane (an IDDPM network's (eps, v)) or on a classifier; DMME_ERR_INVALID: C*H*W no multiple of 4. */
+DMME_API int dmme_unet_plan_set_prediction(dmme_plan* plan, int pred, const float* ab, int T);
+
+/* dmme_q_sample with the regression target of a parameterisation.  x_t: dmme_q_sample's, the same bits.  target (optional):
+ *   DMME_PRED_EPS  (x_t - mean)/std, what dmme_q_sample writes, the same bits
+ *   DMME_PRED_X0   x0
+ *   DMME_PRED_V    (sqrt_abar[t_n] * z) - (sqrt_1m_abar[t_n] * x0), each operation rounded on its own; z is the injected noise */
+DMME_API int dmme_q_sample_pred(int pred, const float* x0, const float* z, const float* sqrt_abar, const float* sqrt_1m_abar, const int64_t* t,
+                                int B, int64_t chw, float* x_t, float* target, void* stream);
+
+/* MSE with a weight per timestep (min-SNR-gamma, Hang et al. 2023): out, target (B, chw), t: int64[B], w_table: device fp32 indexed by t
+ *   loss[0] = 1/(B chw) sum_b w[t_b] sum_j (out - target)^2
+ *   d_out (optional) = (out - target) * g_b,  g_b = 2 w[t_b] grad_scale / (B chw) formed once per image and rounded once
+ * grad_scale as in dmme_mse_loss (the fp16 loss-scaling path).  Reduced like dmme_mse_loss, with up to 64 blocks per image:
+ * `scratch` needs 64 * B floats.  B <= 65535.  The caller guarantees that every t indexes the table. */
+DMME_API int dmme_mse_loss_rows(const float* out, const float* target, const float* w_table, const int64_t* t, int B, int64_t chw, float* loss,
+                                float* d_out, float grad_scale, float* scratch, void* stream);
+
 /* ---- input pipeline: training batch from an HBM-resident uint8 image set ---------------------------------------------
  * Replaces the per-sample transform chain of the reference's data module (data_modules/cifar10.py:39-44:
  * [RandomHorizontalFlip] -> torchvision ToTensor (uint8 / 255) -> norm, common/norm.py:4-6) plus the DataLoader's collate:
