@@ -1476,7 +1476,8 @@ DMME_API int dmme_amp_scale(float* grad, int64_t numel, const float* amp_state, 
 DMME_API int dmme_adam_step_amp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, float lr, float beta1,
                                 float beta2, float eps, const float* grad_norm, float max_grad_norm, float ema_decay, float grad_scale,
                                 float* amp_state, float growth_factor, float backoff_factor, int growth_interval, void* stream) {
-    DMME_REQUIRE(param && grad && exp_avg && exp_avg_sq && grad_norm && amp_state && numel >= 0, DMME_ERR_INVALID, "adam_step_amp: null argument");
+    DMME_REQUIRE(param && grad && exp_avg && exp_avg_sq && grad_norm && amp_state, DMME_ERR_INVALID, "adam_step_amp: null argument");
+    DMME_REQUIRE(numel > 0 && grad_scale > 0.f, DMME_ERR_INVALID, "adam_step_amp: bad argument");  // (numel 0 would be a zero-block launch)
     DMME_REQUIRE(growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval >= 1, DMME_ERR_INVALID, "adam_step_amp: bad scaler constants");
     return launch_adam_amp(param, grad, exp_avg, exp_avg_sq, ema, numel, lr, beta1, beta2, eps, grad_norm, max_grad_norm, ema_decay, grad_scale, amp_state,
                            growth_factor, backoff_factor, growth_interval, (hipStream_t)stream);

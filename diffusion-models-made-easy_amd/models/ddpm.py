@@ -329,14 +329,24 @@ class UNet(nn.Module):
 
     def amp_state(self, device=None) -> Optional[Tensor]:
         """the device-resident loss-scaling state (8 floats: scale, growth tracker, steps taken, found_inf, steps skipped) when
-        dynamic loss scaling is on and the compute dtype is IEEE half; created at first use"""
+        dynamic loss scaling is on and the compute dtype is IEEE half; created at first use.  A state that already exists FOLLOWS the
+        model to another device with its values (a checkpoint loaded before .cuda() keeps its scale and its bias-correction count);
+        on a host device it is a plain tensor filled here - dmme_amp_init is a kernel launch and takes device pointers only"""
         if self._amp is None or self._dtype != _lib.F16:
             return None
-        dev = device if device is not None else self.flat_parameters().device
+        dev = torch.device(device) if device is not None else self.flat_parameters().device
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
         st = self._amp_state
-        if st is None or st.device != torch.device(dev):
+        if st is None:
             st = torch.zeros(8, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().dmme_amp_init(_lib.ptr(st), float(self._amp["init_scale"]), _lib.stream_ptr()), "dmme_amp_init")
+            if dev.type == "cuda":
+                _lib.check(_lib.lib().dmme_amp_init(_lib.ptr(st), float(self._amp["init_scale"]), _lib.stream_ptr()), "dmme_amp_init")
+            else:
+                st[0] = float(self._amp["init_scale"])
+            self._amp_state = st
+        elif st.device != dev:
+            st = st.to(dev)
             self._amp_state = st
         return st
 

@@ -55,18 +55,25 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        flats = [m.flat_parameters() for m in self._owners]
+        if not all(f.is_cuda for f in flats):
+            raise _lib.DmmeError("FusedAdam.step needs the model on a GPU: the fused clip + Adam + EMA pass has no CPU fallback")
         self._step_count += 1
         g0 = self.param_groups[0]
         lr, (b1, b2), eps = float(g0["lr"]), g0["betas"], float(g0["eps"])
         max_norm, decay = float(g0["max_grad_norm"] or 0.0), float(g0["ema_decay"] or 0.0)
         lib = _lib.lib()
-        for m in self._owners:
-            flat = m.flat_parameters()
+        for m, flat in zip(self._owners, flats):
             grad = m.flat_grad()
             st = self._flat_state.get(id(m))
-            if st is None or st["m"].device != flat.device:
+            if st is None:
                 st = {"m": torch.zeros_like(flat), "v": torch.zeros_like(flat), "norm": torch.zeros(1, device=flat.device),
                       "scratch": torch.empty(1024, device=flat.device), "ema": flat.clone() if decay > 0 else None}
+                self._flat_state[id(m)] = st
+            elif st["m"].device != flat.device:
+                # the model moved after the state was made (load_state_dict on the CPU, then .cuda()): the moments and the EMA copy
+                # follow it with their values - re-creating them here would silently restart Adam and the sampler's weights
+                st = {k: (t.to(flat.device) if t is not None else None) for k, t in st.items()}
                 self._flat_state[id(m)] = st
             norm_ptr = _lib.ptr(None)
             amp = m.amp_state(flat.device) if hasattr(m, "amp_state") else None

@@ -283,7 +283,8 @@ DMME_API int dmme_adam_step(float* param, const float* grad, float* exp_avg, flo
  *   dmme_adam_step_amp: dmme_adam_step on the SCALED gradient: divides S out (with grad_scale), clips the unscaled norm (grad_norm is
  *     dmme_grad_norm of the scaled buffer - always required here: it is also the inf / NaN detector), takes the bias-correction step
  *     count from amp_state[2]; a non-finite norm leaves parameters, moments and EMA untouched and multiplies S by backoff_factor
- *     (0.5), growth_interval (2000) finite steps in a row multiply it by growth_factor (2). */
+ *     (0.5), growth_interval (2000) finite steps in a row multiply it by growth_factor (2).  Like dmme_adam_step it refuses
+ *     numel <= 0 and grad_scale <= 0 (DMME_ERR_INVALID) before anything is launched. */
 DMME_API int dmme_amp_init(float* amp_state, float init_scale, void* stream);
 DMME_API int dmme_amp_scale(float* grad, int64_t numel, const float* amp_state, void* stream);
 DMME_API int dmme_adam_step_amp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, float lr, float beta1,
