@@ -84,6 +84,27 @@ class DDIM(DDPM):
         runner = self._buffered_runner("_runner", x.shape, x.device)
         return self._run_chain(runner, x, start, start, lambda i: self._ddim_update(x, self._eps(x, self.tau_tensor(i, x.device)), i), history)
 
+    # ------------------------------------------------------------------ argument checks of the samplers with `decode` (GeneralizedDDIM, DPMSolverPP)
+    def _last_index(self) -> int:
+        """the loop index a full chain starts from"""
+        return self.sub_timesteps
+
+    def _index(self, i, what: str) -> int:
+        i, n = int(i), self._last_index()
+        if not 1 <= i <= n:
+            raise ValueError(f"{what}: index {i} outside 1..{n}")
+        return i
+
+    def _decode(self, x: Tensor, start: Optional[int], history) -> Tensor:
+        n = self._last_index()
+        start = n if start is None else int(start)
+        if not 0 <= start <= n:
+            raise ValueError(f"decode: start {start} outside 0..{n}")
+        x = x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
+        if start == 0 and history is not None:
+            raise ValueError("decode: start = 0 runs no chain to record")
+        return x if start == 0 else self._decode_chain(x, start, history)
+
 
 class GeneralizedDDIM(DDIM):
     r"""DDIM as published (Song, Meng & Ermon 2021, eq. 12), next to `DDIM`, which keeps the reference's collapsed update
@@ -133,12 +154,6 @@ class GeneralizedDDIM(DDIM):
     def _encode_tables(self):
         return self.sub_timesteps, list(self._enc_rows), list(self._enc_t)
 
-    def _index(self, i, what: str) -> int:
-        i = int(i)
-        if not 1 <= i <= self.sub_timesteps:
-            raise ValueError(f"{what}: index {i} outside 1..{self.sub_timesteps}")
-        return i
-
     def _gddim_update(self, x: Tensor, eps: Tensor, row, noise: Optional[Tensor] = None, draw: bool = False) -> Tensor:
         """in place on x; `draw`: a step of a chain that draws takes its span of the Philox stream whether or not k2 uses it"""
         if noise is None and draw:
@@ -174,14 +189,7 @@ class GeneralizedDDIM(DDIM):
     @torch.no_grad()
     def decode(self, x: Tensor, start: Optional[int] = None, history=None) -> Tensor:
         r"""x_0 from x_{tau_start} (start = S by default): `start` reverse steps; draws noise where eta > 0"""
-        S = self.sub_timesteps
-        start = S if start is None else int(start)
-        if not 0 <= start <= S:
-            raise ValueError(f"decode: start {start} outside 0..{S}")
-        x = x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
-        if start == 0 and history is not None:
-            raise ValueError("decode: start = 0 runs no chain to record")
-        return x if start == 0 else self._decode_chain(x, start, history)
+        return self._decode(x, start, history)
 
     @torch.no_grad()
     def encode(self, x0: Tensor, upto: Optional[int] = None) -> Tensor:

@@ -24,7 +24,8 @@ from .. import _lib
 from ..common.noise import gaussian
 from ..equations.ddim import linear_tau, quadratic_tau
 from .ddim import DDIM
-from .ddpm import DDPM, ChainRunner, _scalar_index
+from .chain import ChainRunner, walk
+from .ddpm import DDPM, _scalar_index
 
 TAU_SCHEDULES = ("linear", "quadratic", "logsnr")
 ROW = 8  # floats per table row: q0, q1, k0, k1, w, clip, s, -
@@ -91,18 +92,23 @@ class DPMChainRunner(ChainRunner):
     def _carried(self):
         return super()._carried() + [self.hist]
 
-    def _launch(self, packed):
-        self._set_prediction()
+    def _call(self, packed):
         _lib.check(
             _lib.lib().dmme_dpmpp_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace), _lib.ptr(self.hist),
                                              _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
             "dmme_dpmpp_chain_step",
         )
-        self.plan.overwritten()
 
 
 def _row_arg(row):
+    """a table row of ROW floats as the C array the eager entry points take (this module's rows and RePaint's)"""
     return (C.c_float * ROW)(*row)
+
+
+def _from_process(cls, p: DDPM, **kw):
+    """the sampler over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one) and prediction"""
+    kw.setdefault("prediction", getattr(p, "prediction", "eps"))
+    return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
 
 
 class DPMSolverPP(DDIM):
@@ -140,11 +146,7 @@ class DPMSolverPP(DDIM):
         self._s1, self._s2 = np.sqrt(1 - ab64).tolist(), np.sqrt(ab64).tolist()  # what DDIM's constructor leaves for its collapsed update
         self._rows = self._make_rows(1.0)
 
-    @classmethod
-    def from_process(cls, p: DDPM, **kw):
-        """the solver over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one) and prediction"""
-        kw.setdefault("prediction", getattr(p, "prediction", "eps"))
-        return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
+    from_process = classmethod(_from_process)
 
     def _make_rows(self, scale: float):
         rows = solver_rows(self._ab64, self._tau_host, self.order, self.clip_x0, scale)
@@ -153,11 +155,8 @@ class DPMSolverPP(DDIM):
     def _chain_tables(self):
         return self.n_steps, list(self._rows), list(self._tau_host)
 
-    def _index(self, i, what: str) -> int:
-        i = int(i)
-        if not 1 <= i <= self.n_steps:
-            raise ValueError(f"{what}: index {i} outside 1..{self.n_steps}")
-        return i
+    def _last_index(self) -> int:
+        return self.n_steps
 
     def _eps_planes(self, x: Tensor, eps: Tensor) -> int:
         planes = eps[0].numel() // x[0].numel()
@@ -211,15 +210,7 @@ class DPMSolverPP(DDIM):
     def _eager_chain(self, x: Tensor, start: int, recorder=None) -> Tensor:
         """the host loop, bit-identical to the captured chain: the same update on the same scalars, the history valid after the first step"""
         hist = torch.empty_like(x)
-        if recorder is not None:
-            recorder.begin(x, start)
-        for k, i in enumerate(range(start, 0, -1)):
-            if recorder is not None:
-                recorder.at(k, x)
-            self._dpm_update(x, self._eps(x, self.tau_tensor(i, x.device)), i, hist, k > 0)
-        if recorder is not None:
-            recorder.at(start, x)
-        return x
+        return walk(x, start, start, lambda k, i: self._dpm_update(x, self._eps(x, self.tau_tensor(i, x.device)), i, hist, k > 0), recorder)
 
     def _decode_chain(self, x: Tensor, start: int, recorder=None) -> Tensor:
         runner = self._buffered_runner("_runner", x.shape, x.device)
@@ -232,14 +223,7 @@ class DPMSolverPP(DDIM):
     def decode(self, x: Tensor, start: Optional[int] = None, history=None) -> Tensor:
         r"""x_0 from x_{tau_start} (start = n_steps by default): `start` solver steps, the first of them first order.  `history`: a
         HistoryRecorder for the chain's frames (not the x0 history of `sampling_step`)"""
-        n = self.n_steps
-        start = n if start is None else int(start)
-        if not 0 <= start <= n:
-            raise ValueError(f"decode: start {start} outside 0..{n}")
-        x = x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
-        if start == 0 and history is not None:
-            raise ValueError("decode: start = 0 runs no chain to record")
-        return x if start == 0 else self._decode_chain(x, start, history)
+        return self._decode(x, start, history)
 
     @torch.no_grad()
     def generate(self, img_size: Tuple[int, int, int, int], history=None) -> Tensor:

@@ -20,7 +20,6 @@ that goes up and down, which the replayed step's `t = t_table[i]` never minded. 
 
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -29,8 +28,9 @@ from torch import Tensor, nn
 
 from .. import _lib
 from ..common.noise import gaussian, gaussian_like, philox_reserve
-from .ddpm import DDPM, ChainRunner
-from .dpm_solver import solver_grid
+from .chain import ChainRunner, walk
+from .ddpm import DDPM
+from .dpm_solver import _from_process, _row_arg, solver_grid
 
 ROW = 8  # floats per table row: c0, c1, c2, ka, ks, r0, r1, -
 STREAMS = 3  # normal streams a step owns: z0 (reverse step), z1 (known pixels), z2 (jump)
@@ -92,10 +92,6 @@ def repaint_rows(alpha_bar, grid: Sequence[int], walk: Sequence[int], reverse=No
     return rows, ttab
 
 
-def _row_arg(row):
-    return (C.c_float * ROW)(*row)
-
-
 def _row_draws(row) -> bool:
     return row[2] != 0.0 or row[4] != 0.0 or row[6] != 0.0
 
@@ -110,15 +106,13 @@ class PaintChainRunner(ChainRunner):
         self.mask = torch.zeros_like(x)
         self.noise_numel = STREAMS * x.numel()
 
-    def _launch(self, packed):
-        self._set_prediction()
+    def _call(self, packed):
         _lib.check(
             _lib.lib().dmme_repaint_chain_step(self.plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.plan.workspace),
                                                _lib.ptr(self.known), _lib.ptr(self.mask), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
                                                _lib.stream_ptr()),
             "dmme_repaint_chain_step",
         )
-        self.plan.overwritten()
 
     def paint(self, x: Tensor, known: Tensor, mask: Tensor, first: int, recorder=None) -> Tensor:
         """the chain from loop index `first` down to 0 on copies of the three images; a new tensor"""
@@ -160,11 +154,7 @@ class RePaint(DDPM):
         self._plain_tables = self._make_tables(list(range(self.n_levels, -1, -1)))  # SDEdit's: loop index = level
         self.n_rows = self._tables[0]
 
-    @classmethod
-    def from_process(cls, p: DDPM, **kw):
-        """RePaint over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one) and prediction"""
-        kw.setdefault("prediction", getattr(p, "prediction", "eps"))
-        return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
+    from_process = classmethod(_from_process)
 
     def _make_tables(self, walk):
         full = self.n_levels == self.timesteps
@@ -206,23 +196,19 @@ class RePaint(DDPM):
         n, rows, ttab = tables if tables is not None else self._tables
         first = n if first is None else int(first)
         lib, numel = _lib.lib(), x.numel()
-        if history is not None:
-            history.begin(x, first)
-        seed, off = philox_reserve(x.device, STREAMS * numel * first)
+        span = []  # (seed, offset) of the walk's normals, taken once the recorder has accepted the walk
         tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
         z3 = torch.empty(STREAMS * numel, dtype=torch.float32, device=x.device)
-        for k, i in enumerate(range(first, 0, -1)):
-            if history is not None:
-                history.at(k, x)
+
+        def step(k, i):
             eps = self._eps(x, tt[i]).detach().to(torch.float32).contiguous()
             draws = _row_draws(rows[i])
             if draws:
-                _lib.check(lib.dmme_randn(_lib.ptr(z3), z3.numel(), seed, off + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
+                _lib.check(lib.dmme_randn(_lib.ptr(z3), z3.numel(), span[0], span[1] + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
             _lib.check(lib.dmme_repaint_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(z3 if draws else None), _row_arg(rows[i]),
                                              x.shape[0], x[0].numel(), eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_repaint_step")
-        if history is not None:
-            history.at(first, x)
-        return x
+
+        return walk(x, first, first, step, history, lambda: span.extend(philox_reserve(x.device, STREAMS * numel * first)))
 
     def _chain(self, slot: str, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None, history=None) -> Tensor:
         first = (tables if tables is not None else self._tables)[0] if first is None else first

@@ -28,7 +28,8 @@ from torch import Tensor, nn
 from .. import _lib
 from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..diffusion_models.ddim import DDIM
-from ..diffusion_models.ddpm import DDPM, ChainRunner, ChainTables, _scalar_index
+from ..diffusion_models.chain import ChainRunner, ChainTables
+from ..diffusion_models.ddpm import DDPM, _scalar_index
 from ..models.cond import class_labels
 from ..models.ddpm import UNet
 
@@ -163,12 +164,11 @@ class GuidedChainRunner(ChainRunner):
         cp = self.cls_plan
         return super()._weights_key() + (getattr(cp, "packed_version", None), getattr(cp, "packed_bwd_version", None))
 
-    def _launch(self, packed):
+    def _call(self, packed):
         if self.cls.training:
             raise RuntimeError("guided sampling runs the classifier in eval mode")
         cp = self.cls_plan
         cls_packed = self.cls._bwd_buffers(cp)
-        self._set_prediction()  # (the UNet's plan; the classifier's predicts no noise and is never told)
         _lib.check(
             _lib.lib().dmme_guided_chain_step(self.plan.h, _lib.ptr(packed), cp.h, _lib.ptr(cls_packed), _lib.ptr(cp.packed_bwd), _lib.ptr(self.x),
                                               _lib.ptr(self.out), _lib.ptr(self.plan.workspace), _lib.ptr(cp.workspace), _lib.ptr(cp.bws), _lib.ptr(self.y),
@@ -176,8 +176,7 @@ class GuidedChainRunner(ChainRunner):
                                               _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state), _lib.stream_ptr()),
             "dmme_guided_chain_step",
         )
-        self.plan.overwritten()
-        cp.overwritten()
+        cp.overwritten()  # (the UNet's plan is `_launch`'s; it alone is told the prediction: the classifier's predicts no noise)
 
     def step(self):
         self.cls._bwd_buffers(self.cls_plan)  # (re-packs outside any capture when the classifier's parameters changed)
@@ -225,8 +224,10 @@ class _Guided:
         x = x_t.detach().to(torch.float32).clone().contiguous()
         return self._eager_update(x, eps, g, index, noise)
 
-    def _guided_generate(self, img_size, y, n_steps: int, history=None) -> Tensor:
-        dev = self.beta.device
+    @torch.no_grad()
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the guided chain from pure noise (`chain_length()` steps), one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        dev, n_steps = self.beta.device, self.chain_length()
         x_t = gaussian(img_size, device=dev)
         labels = _labels(y, img_size[0], self.classifier.num_classes, dev)
         runner = self._guided_runner(img_size, dev)
@@ -240,7 +241,8 @@ class _Guided:
 
 class ClassifierGuidedDDPM(_Guided, DDPM):
     """DDPM sampling with classifier guidance (Dhariwal & Nichol 2021, Algorithm 1):
-    x_{t-1} = mu(x_t, t) + s beta_t grad_x log p(y | x_t, t) + sqrt(beta_t) z  (no noise at t = 1; the mean shift stays)."""
+    x_{t-1} = mu(x_t, t) + s beta_t grad_x log p(y | x_t, t) + sqrt(beta_t) z  (no noise at t = 1; the mean shift stays); `generate` runs
+    the T-step chain."""
 
     _chain_kind = _lib.CHAIN_DDPM_GUIDED
 
@@ -260,15 +262,11 @@ class ClassifierGuidedDDPM(_Guided, DDPM):
         step = _scalar_index(t, "a timestep")
         return self._guided_step(x_t, step, self.timestep_tensor(step, x_t.device), y, noise)
 
-    @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
-        """the T-step guided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
-        return self._guided_generate(img_size, y, self.timesteps, history)
-
 
 class ClassifierGuidedDDIM(_Guided, DDIM):
     """DDIM sampling with classifier guidance (Dhariwal & Nichol 2021, Algorithm 2):
-    eps' = eps - s sqrt(1 - abar_tau_i) grad_x log p(y | x_tau_i, tau_i), then the DDIM update with eps'."""
+    eps' = eps - s sqrt(1 - abar_tau_i) grad_x log p(y | x_tau_i, tau_i), then the DDIM update with eps'; `generate` runs the S-step
+    strided chain."""
 
     _chain_kind = _lib.CHAIN_DDIM_GUIDED
 
@@ -287,8 +285,3 @@ class ClassifierGuidedDDIM(_Guided, DDIM):
         """x_{tau_{i-1}} from x_{tau_i} with guidance; i has shape (1,)"""
         idx = _scalar_index(i, "an index")
         return self._guided_step(x_tau_i, idx, self.tau_tensor(idx, x_tau_i.device), y, None)
-
-    @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
-        """the S-step guided strided chain, one captured graph per step; `history`: a HistoryRecorder for its frames"""
-        return self._guided_generate(img_size, y, self.sub_timesteps, history)

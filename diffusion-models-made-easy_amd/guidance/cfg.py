@@ -23,7 +23,8 @@ from .. import _lib
 from ..common.noise import gaussian, gaussian_like, philox_reserve, uniform_int
 from ..diffusion_models.ddim import GeneralizedDDIM
 from ..diffusion_models.dpm_solver import DPMSolverPP, _row_arg
-from ..diffusion_models.ddpm import DDPM, ChainRunner, _scalar_index
+from ..diffusion_models.chain import ChainRunner, walk
+from ..diffusion_models.ddpm import DDPM, _scalar_index
 from ..models.cond import ConditionalUNet, class_labels
 
 __all__ = ["ClassifierFreeDDPM", "ClassifierFreeDDIM", "ClassifierFreeDPMSolver", "CFGChainRunner"]
@@ -61,9 +62,8 @@ class CFGChainRunner(ChainRunner):
     def _carried(self):
         return super()._carried() + ([self.hist] if self.dpmpp else [])
 
-    def _launch(self, packed):
+    def _call(self, packed):
         lib, plan = _lib.lib(), self.plan
-        self._set_prediction()
         if self.batched and self.dpmpp:
             _lib.check(
                 lib.dmme_cfg_dpmpp_chain_step(plan.h, _lib.ptr(packed), _lib.ptr(self.x), _lib.ptr(self.y), _lib.ptr(self.out), _lib.ptr(plan.workspace),
@@ -101,11 +101,10 @@ class CFGChainRunner(ChainRunner):
                                           self.images, self.x[0].numel(), _lib.stream_ptr()),
                     "dmme_chain_update",
                 )
-        plan.overwritten()
 
 
 class _ClassifierFree:
-    """shared parts of the two classifier-free samplers (the chain tables, `_n_steps` and the eager updates come from the sampler)"""
+    """shared parts of the three classifier-free samplers (the chain tables and the eager updates come from the sampler)"""
 
     guidance_scale: float
     p_uncond: float
@@ -194,8 +193,10 @@ class _ClassifierFree:
                                             x[0].numel(), _lib.stream_ptr()), "dmme_cfg_step")
         return x[:B]
 
-    def _cfg_generate(self, img_size, y, n_steps: int, history=None) -> Tensor:
-        dev = self.beta.device
+    @torch.no_grad()
+    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
+        """the guided chain from pure noise (`chain_length()` steps), one captured graph per step; `history`: a HistoryRecorder for its frames"""
+        dev, n_steps = self.beta.device, self.chain_length()
         model = self.model
         B = int(img_size[0])
         labels = class_labels(y, B, model.num_classes, dev)
@@ -212,6 +213,10 @@ class _ClassifierFree:
         model.check_labels()
         return out
 
+    def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
+        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
+        return self.model(x, t, y)
+
 
 def _needs_labels(name: str):
     def refuse(self, *a, **kw):
@@ -222,7 +227,8 @@ def _needs_labels(name: str):
 
 
 class ClassifierFreeDDPM(_ClassifierFree, DDPM):
-    """DDPM training and sampling with classifier-free guidance: x_{t-1} = mu(x_t, e^) + sqrt(beta_t) z (no noise at t = 1)."""
+    """DDPM training and sampling with classifier-free guidance: x_{t-1} = mu(x_t, e^) + sqrt(beta_t) z (no noise at t = 1); `generate`
+    runs the T-step chain."""
 
     _chain_kind = _lib.CHAIN_DDPM_CFG
 
@@ -245,18 +251,10 @@ class ClassifierFreeDDPM(_ClassifierFree, DDPM):
 
     denoise_once = _needs_labels("denoise_once")
 
-    @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
-        """the T-step guided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
-        return self._cfg_generate(img_size, y, self.timesteps, history)
-
-    def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
-        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
-        return self.model(x, t, y)
-
 
 class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
-    """Paper-form DDIM (Song et al. 2021, eq. 12, any eta) with classifier-free guidance: x' = (k0 x + k1 e^) + k2 z."""
+    """Paper-form DDIM (Song et al. 2021, eq. 12, any eta) with classifier-free guidance: x' = (k0 x + k1 e^) + k2 z; `generate` runs
+    the S-step strided chain."""
 
     _chain_kind = _lib.CHAIN_GDDIM_CFG
 
@@ -284,18 +282,10 @@ class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
 
     denoise_once, encode, decode, interpolate = (_needs_labels(n) for n in ("denoise_once", "encode", "decode", "interpolate"))
 
-    @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
-        """the S-step guided strided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
-        return self._cfg_generate(img_size, y, self.sub_timesteps, history)
-
-    def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
-        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
-        return self.model(x, t, y)
-
 
 class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
-    """DPM-Solver++(2M) with classifier-free guidance: the solver's update on e^ = e_u + s (e_c - e_u); the history holds B images."""
+    """DPM-Solver++(2M) with classifier-free guidance: the solver's update on e^ = e_u + s (e_c - e_u); the history holds B images;
+    `generate` runs the n_steps chain."""
 
     _chain_kind = _lib.CHAIN_DPMPP_CFG
 
@@ -333,17 +323,10 @@ class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
 
     def _eager_generate(self, x_T: Tensor, y) -> Tensor:
         """the host loop over the eager twins, bit-identical to the captured chain of `generate`"""
-        x, hist = x_T, torch.empty_like(x_T)
-        for k, i in enumerate(range(self.n_steps, 0, -1)):
+        x, hist = x_T.clone(), torch.empty_like(x_T)
+
+        def step(k, i):
             xb, eps, B = self._predict(x, self.tau_tensor(i, x.device), y)
-            x = self._guided_update(xb, eps, B, i, hist, k > 0)
-        return x.clone()
+            x.copy_(self._guided_update(xb, eps, B, i, hist, k > 0))
 
-    @torch.no_grad()
-    def generate(self, img_size: Tuple[int, int, int, int], y, history=None) -> Tensor:
-        """the n_steps guided chain from pure noise, one captured graph per step; `history`: a HistoryRecorder for its frames"""
-        return self._cfg_generate(img_size, y, self.n_steps, history)
-
-    def forward(self, x: Tensor, t: Tensor, y) -> Tensor:
-        """the raw network output (eps, x0 or v, as `prediction` says), not converted"""
-        return self.model(x, t, y)
+        return walk(x, self.n_steps, self.n_steps, step)

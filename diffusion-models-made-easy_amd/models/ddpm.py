@@ -545,23 +545,15 @@ class UNet(nn.Module):
         key = (x_static.data_ptr(), t_static.data_ptr(), tuple(x_static.shape), self._dtype) + self._weights_key(flat)
         g = getattr(self, "_graph", None)
         if g is None or g[0] != key:
+            from ..diffusion_models.chain import capture
+
             with torch.no_grad():
-                # the eager trial forward (packs weights, sets kernel attributes) is OUTSIDE the fallback: a DmmeError or a kernel
-                # fault in it is a real error and propagates (as ChainRunner.step does); only a failure of the CAPTURE itself makes
-                # this module stay eager, and the cause is kept in `_graph_error`
-                self._forward_impl(x_static, t_static)
-                torch.cuda.synchronize()
-                self._last_plan.check()
-                try:
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        y = self._forward_impl(x_static, t_static)
-                except RuntimeError as exc:  # stream capture unavailable / invalidated here: the same launches, eagerly
-                    if isinstance(exc, _lib.DmmeError):
-                        raise
-                    self._graph_disabled = True
-                    self._graph_error = exc
-                    self._graph = None
+                # (see `capture`: an error of its trial forward propagates; a failed capture makes this module stay eager)
+                graph, y, error = capture(lambda: self._forward_impl(x_static, t_static), lambda: self._last_plan.check())
+                if error is not None:
+                    if isinstance(error, _lib.DmmeError):
+                        raise error
+                    self._graph_disabled, self._graph_error, self._graph = True, error, None
                     return self._forward_impl(x_static, t_static)
             g = (key, graph, y, self._last_plan)  # the plan whose workspace the replays overwrite
             self._graph = g

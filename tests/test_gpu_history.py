@@ -283,6 +283,51 @@ def test_recorded_repaint_chain():
     assert torch.equal(proc.edit(x0, 0.5, history=rec2), plain) and rec2.recorded == 3
 
 
+@pytest.mark.parametrize("case", ["ddpm", "iddpm-strided", "dpm-solver", "repaint"])
+def test_recorded_host_walk_equals_the_recorded_captured_chain(case):
+    """the host walk (diffusion_models/chain.py: walk) with a recorder - what a process runs where its step cannot be replayed - keeps
+    the frames of the captured chain and returns its images, bit for bit: DDPM's and the strided IDDPM's `_run_chain`, DPMSolverPP's
+    and RePaint's `_eager_chain` (a walk with a jump: 4 levels, jump length 2, 2 resamples, 6 steps).  Chains of 4 to 8 steps."""
+    import dmme_amd
+    from dmme_amd.models import iddpm as iddpm_models
+
+    if case == "ddpm":
+        proc = dmme_amd.DDPM(_tiny(), 8).cuda()
+        count, run = 8, lambda rec: proc.generate(SHAPE, history=rec)
+    elif case == "iddpm-strided":
+        proc = dmme_amd.IDDPM(iddpm_models.UNet(3, 4, 8, 2, 0.0, (4, 8), 1, (2,)).cuda().eval(), 20).cuda()
+        count, run = proc._respaced_tables(5)[0], lambda rec: proc.generate(SHAPE, sample_steps=5, history=rec)
+        assert count == 5
+    elif case == "dpm-solver":
+        proc = dmme_amd.DPMSolverPP(_tiny(), 100, 4).cuda()
+        count, run = 4, lambda rec: proc.generate(SHAPE, history=rec)
+    else:
+        proc = dmme_amd.RePaint(_tiny(), 100, 4, 2, 2).cuda()
+        x0 = (0.5 * synth.normal(42, SHAPE)).clamp(-1, 1).cuda()
+        m = torch.zeros((1, 1, 32, 32))
+        m[..., :16] = 1.0
+        count, run = 6, lambda rec: proc.inpaint(x0, m, history=rec)
+        assert proc.chain_length() == 6
+    ords = dmme_amd.history_ordinals(count, 3)
+    captured, hosted = (dmme_amd.HistoryRecorder(SHAPE[0], *SHAPE[1:], ords) for _ in range(2))
+    torch.manual_seed(23)
+    want = run(captured).clone()
+    asked = []
+
+    def never(x):
+        asked.append(tuple(x.shape))
+        return False
+
+    proc._replayable = never  # no runner: the process walks on the host
+    torch.manual_seed(23)
+    got = run(hosted)
+    assert asked == [SHAPE] and torch.equal(got, want)
+    assert hosted.recorded == captured.recorded == len(ords) == 3 and torch.equal(hosted.canvas, captured.canvas)
+    assert bool(captured.canvas.any())
+    torch.manual_seed(23)
+    assert torch.equal(run(None), want) and len(asked) == 2  # the same walk with nobody watching
+
+
 def _column(canvas, k, b):
     return canvas[:, b * 34 + 2:b * 34 + 34, k * 34 + 2:k * 34 + 34]
 

@@ -448,3 +448,37 @@ def test_trainer_sample_geometry_and_precision_follow_the_yaml(tmp_path):
     y.write_text("trainer:\n  precision: bf16\nmodel:\n  class_path: dmme.LitDDPM\ndata:\n  class_path: dmme.LSUN\n  init_args:\n    imgsize: 64\n")
     c2 = trainer.parse_config(str(y))
     assert c2["image_size"] == 64 and c2["sample_precision"] == "bf16"
+
+
+@pytest.mark.parametrize("first,count", [(5, 5), (5, 2), (3, 0)])
+def test_walk_is_begin_then_frame_and_step_in_turn_then_the_last_frame(first, count):
+    """diffusion_models/chain.py: `walk`, the one host loop of every chain (eager and replayed): the recorder is asked first, `reserve`
+    comes between its answer and the first step, ordinal s runs at loop index first - s, and a walk of no steps records frame 0 only;
+    a recorder whose last ordinal lies behind the chain's end refuses in `begin`, before the reservation and before any step"""
+    from dmme_amd.diffusion_models.chain import walk
+
+    calls = []
+
+    class Recorder:
+        def begin(self, x, n):
+            calls.append(("begin", x, n))
+
+        def at(self, s, x):
+            calls.append(("at", s, x))
+
+    x = object()
+    want = [("begin", x, count), ("reserve",)]
+    for s in range(count):
+        want += [("at", s, x), ("step", s, first - s)]
+    want.append(("at", count, x))
+    assert walk(x, first, count, lambda s, i: calls.append(("step", s, i)), Recorder(), lambda: calls.append(("reserve",))) is x
+    assert calls == want
+    del calls[:]
+    assert walk(x, first, count, lambda s, i: calls.append(("step", s, i))) is x  # no recorder, nothing to reserve: the steps alone
+    assert calls == [w for w in want if w[0] == "step"]
+    del calls[:]
+    img = torch.zeros(2, 3, 4, 4)
+    late = dmme_amd.HistoryRecorder(2, 3, 4, 4, [0, count + 1], device="cpu")
+    with pytest.raises(ValueError, match=f"ordinal {count + 1} in a chain of {count} steps"):
+        walk(img, first, count, lambda s, i: calls.append(("step", s, i)), late, lambda: calls.append(("reserve",)))
+    assert calls == []
