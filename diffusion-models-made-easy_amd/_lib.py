@@ -89,7 +89,10 @@ PROTOTYPES = {
     "dmme_unet_plan_dropmask_numel": (_i64, [_vp]),
     "dmme_unet_plan_out_channels": (_i, [_vp]),
     "dmme_unet_plan_num_launches": (_i, [_vp]),
+    "dmme_unet_plan_num_launches_nograd": (_i, [_vp]),
+    "dmme_unet_plan_num_folded": (_i, [_vp]),
     "dmme_unet_pack_params": (_i, [_vp, _vp, _vp, _vp]),
+    "dmme_unet_pack_folded": (_i, [_vp, _vp, _vp]),
     "dmme_unet_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "dmme_unet_forward_nograd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "dmme_unet_forward_cond": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -165,6 +168,8 @@ PROTOTYPES = {
     "dmme_groupnorm_scale_shift": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp]),
     "dmme_attention": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "dmme_attention_proj": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "dmme_attention_fold": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_attention_block": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "dmme_attention_heads": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "dmme_nchw_to_nhwc": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),
     "dmme_nhwc_to_nchw": (_i, [_i, _vp, _i, _i, _i, _vp, _vp]),

@@ -16,6 +16,8 @@
 //     (row pitch = 16 banks mod 64: the four key rows of a transposed read hit disjoint banks).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "conv_common.h"
 
 namespace dmme {
@@ -312,6 +314,28 @@ struct AttnProj {
     long long* stamps;  // diagnostic (null: off): cycle stamps of wave 0 of workgroup 0 in -DAT_STAMPS builds (dmme_debug_set_stamps; tools/stamp_attn.py)
     int dbg;            // DMME_DEBUG_ROUTE=attn_proj_dbg=<mask> (timing experiments, wrong results): 1 no statistics, 2 no epilogue loads / stores, 4 no phase-4 MFMAs, 8 image 0's K / V for every workgroup
 };
+// FOLD (the no-grad form of a single-head block behind a GroupNorm, weights fixed over a sampling chain): the launch reads the block's RAW
+// input x [N][S][C] and nothing else.  With n_j = a x_j + b the normalised pixel (a = rstd gamma, b = beta - mean a per image and channel)
+// and s = C^-0.5:  q_i . k_j s = n_j . (s Wk^T (Wq n_i + bq)) + (terms without j), and a softmax over j ignores terms without j - bk drops
+// out, and so does y_i . b of  y_i . n_j = (a y_i) . x_j + y_i . b  with  y_i = M n_i + c,  M = s Wk^T Wq,  c = s Wk^T bq.  The keys are
+// the stored x.  Rows of P sum to 1, so ctx_i = Wv (a o_i + b) + bv with o_i = sum_j P_ij x_j: the values are the stored x too, and
+// out_i = res_i + Wpv (a o_i + b) + b'  with  Wpv = Wp Wv,  b' = Wp bv + bp.  M, c, Wpv, b' depend on the weights only
+// (dmme_unet_pack_folded computes them once per weight version).  The launch gains
+//   phase 0  y^T = M n_q^T over the C / 32 row tiles of M (phase 4's structure: same ring, same fragment addresses), the query rows loaded
+//            raw and normalised in registers; + c, * a, one rounding, phase 4's register swap: the Q^T operand of phase 1;
+// phases 1 and 3 stream x (row pitch C), phase 2 sums the ROUNDED probabilities (the values carry their group's mean, many sigma at
+// times: a row sum of the unrounded ones leaves 2^-9 of that mean in the output), a o + b is applied where O^T becomes phase 4's operand.
+// The norm in front of the block is finished here from its producers' partials (GnIn) or read as (scale, shift) rows; a, b and c sit in
+// LDS behind the ring / the staging tiles, so that nothing between the first and the last LDS-DMA is an ordinary load.
+struct AttnFold {
+    const void* M;       // [C][C] 16-bit, row = channel of y (the packed 1x1 layout)
+    const float* c;      // [C]
+    const float* scale;  // [N][C] the norm's rows (has_gni == 0), else written by the image's first workgroup where non-null
+    const float* shift;
+    GnIn gni;
+    int has_gni;
+};
+struct AttnNoFold {};
 // the fp32 product as a value of its own: hipcc otherwise folds `(half)(a * b)` into v_fma_mix*_f16 in one form of the kernel and not in
 // the other - one rounding instead of two, a last-bit difference in ~3e-5 of the context tensor's elements between them
 __device__ __forceinline__ float at_keep_f32(float x) {
@@ -324,11 +348,15 @@ __device__ __forceinline__ float at_sum64(float v) {
     permlane32_swap(a, b);
     return a + b;
 }
-template <int C, typename T = bf16, bool PROJ = false>
-__global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qkv, AttnGeom g, T* __restrict__ out, float* __restrict__ lse, int xcd_order, AttnProj pj) {
+template <int C, typename T = bf16, bool PROJ = false, bool FOLD = false>
+__global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qkv, AttnGeom g, T* __restrict__ out, float* __restrict__ lse, int xcd_order, AttnProj pj,
+                                                        typename std::conditional<FOLD, AttnFold, AttnNoFold>::type fd) {
     typedef T tx8 __attribute__((ext_vector_type(8)));
+    static_assert(!FOLD || PROJ, "attn_full: the folded form carries the proj phase");
     constexpr int S = 256, NKT = S / AT_KT, KSTEPS = C / 16, CT = C / 32;
-    constexpr int NTOT = 2 * NKT + (PROJ ? CT : 0);  // tiles of the stream: K, V, then the proj matrix
+    constexpr int T0 = FOLD ? CT : 0;                     // FOLD: the stream starts with the row tiles of M
+    constexpr int NTOT = T0 + 2 * NKT + (PROJ ? CT : 0);  // tiles of the stream: (M,) K, V, then the proj matrix
+    constexpr int KOFF = FOLD ? 0 : C, VOFF = FOLD ? 0 : 2 * C;  // where keys / values start in a row (FOLD: both are the raw x)
     constexpr int ROWB = C * 2, TILEB = AT_KT * ROWB;      // bytes per key row / per tile (unpadded)
     constexpr int DPT = TILEB / (256 * 16);                // DMA wave-instructions per tile and wave
     // PAIR (-DAT_PAIR_STEPS=0: one barrier per tile, seven tiles ahead): the stream advances in steps of TWO tiles - one counted wait, one
@@ -337,6 +365,7 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
     // every workgroup on one L2-resident image - the K / V stream is not what the kernel waits for); a pair pays that once.
     constexpr bool PAIR = AT_PAIR_STEPS != 0;
     constexpr int NSLOT_BYTES = 8 * TILEB;
+    constexpr int MAINB = PROJ && 4 * 32 * (C * 4 + 16) > NSLOT_BYTES ? 4 * 32 * (C * 4 + 16) : NSLOT_BYTES;  // the ring, or the epilogue's staging tiles over it
     constexpr int NSLOT = 8, AHEAD = PAIR ? 6 : 7;  // (a four-slot ring, 48 KB in flight per CU, measured 24 us at C = 256: bytes in flight / latency)
     static_assert(!PAIR || (NTOT % 2 == 0 && NKT % 2 == 0), "pair steps: even tile counts per phase");
     static_assert(DPT >= 1 && DPT * 256 * 16 == TILEB, "attn_full: tile does not split over the DMA lanes");
@@ -361,7 +390,7 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
     // vmcnt queue of the counted waits
     // (-DAT_STAMPS builds only: compiled in, even unused, they cost the sampling step 0.3 %)
 #ifdef AT_STAMPS
-    long long* st_lds = reinterpret_cast<long long*>(lds + (PROJ ? (4 * 32 * (C * 4 + 16) > NSLOT_BYTES ? 4 * 32 * (C * 4 + 16) : NSLOT_BYTES) : NSLOT_BYTES));
+    long long* st_lds = reinterpret_cast<long long*>(lds + MAINB);
     int st_i = 0;
     const bool stamping = PROJ && pj.stamps && blockIdx.x == 0 && tid == 0;
 #define AF_STAMP() { if (PROJ && stamping && st_i < 120) st_lds[st_i++] = (long long)clock64(); }
@@ -386,6 +415,15 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
     }
     auto dma_tile = [&](int t) __attribute__((always_inline)) {
         const unsigned dst = lds0 + (unsigned)((t % NSLOT) * TILEB);
+        if constexpr (FOLD) {
+            if (t < T0) {
+                const char* src = (const char*)fd.M + (size_t)t * TILEB;
+#pragma unroll
+                for (int i = 0; i < DPT; ++i) glds16_hidden_s(src, woff[i], dst + (unsigned)((wave + 4 * i) * 1024));
+                return;
+            }
+        }
+        t -= T0;
         if (PROJ && t >= 2 * NKT) {
             const char* src = (const char*)pj.w + (size_t)(t - 2 * NKT) * TILEB;
 #pragma unroll
@@ -394,7 +432,7 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
         }
         const bool isv = t >= NKT;
         const T* kvb = (PROJ && (pj.dbg & 8)) ? qkv : base;  // (timing experiment: every workgroup streams image 0's K / V)
-        const char* src = (const char*)(kvb + (int64_t)((isv ? t - NKT : t) * AT_KT) * ld + (isv ? 2 * C : C));
+        const char* src = (const char*)(kvb + (int64_t)((isv ? t - NKT : t) * AT_KT) * ld + (isv ? VOFF : KOFF));
 #pragma unroll
         for (int i = 0; i < DPT; ++i) glds16_hidden_s(src, isv ? voff[i] : koff[i], dst + (unsigned)((wave + 4 * i) * 1024));
     };
@@ -404,9 +442,47 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
     // the counted waits below care about (they are waited for by the compiler before the first MFMA).  (Requested BEFORE the tiles -
     // so that the first counted wait asks for two tiles instead of all six - the launch's first 9.5 k cycles stay what they are:
     // 24 MB requested by 256 CUs at once, the HBM's rate.)
+    // FOLD: these are the raw query rows of x; they become n_q = a x + b below, once the rows are in LDS
     uint4 qf[KSTEPS];
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) qf[ks] = *reinterpret_cast<const uint4*>(base + (int64_t)q_row * ld + ks * 16 + h * 8);
+    typedef __attribute__((address_space(3))) char lc;
+    typedef __attribute__((address_space(3))) f32x4 lf4;
+#ifdef AT_STAMPS
+    const lc* rows3 = (const lc*)(lds + MAINB + 1024);  // [3][C] floats: a, b, c
+#else
+    const lc* rows3 = (const lc*)(lds + MAINB);
+#endif
+    if constexpr (FOLD) {
+        if (tid < C) {
+            float sc, sh;
+            if (fd.has_gni) {
+                gn_in_scale_shift_g(fd.gni, const_cast<float*>(fd.scale), const_cast<float*>(fd.shift), n, tid, C, qb == 0 && fd.scale != nullptr, sc, sh);
+            } else {
+                sc = fd.scale[(int64_t)n * C + tid];
+                sh = fd.shift[(int64_t)n * C + tid];
+            }
+            typedef __attribute__((address_space(3))) float lf1;
+            lf1* w3 = (lf1*)rows3;
+            w3[tid] = sc;
+            w3[C + tid] = sh;
+            w3[2 * C + tid] = fd.c[tid];
+        }
+        wait_lgkm_all();
+        asm volatile("s_barrier" ::: "memory");
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {  // the qkv conv's prologue: fma in fp32, one rounding
+            const int ch = ks * 16 + h * 8;
+            tx8 x = __builtin_bit_cast(tx8, qf[ks]);
+#pragma unroll
+            for (int e = 0; e < 8; e += 4) {
+                const f32x4 a4 = *(const lf4*)(rows3 + (ch + e) * 4), b4 = *(const lf4*)(rows3 + (C + ch + e) * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[e + j] = (T)fmaf((float)x[e + j], a4[j], b4[j]);
+            }
+            qf[ks] = __builtin_bit_cast(uint4, x);
+        }
+    }
     // per-lane fragment bases.  K: row r, piece (2 u + h) of k-step u -> ((2 u & 7) ^ x) with x = h ^ (r & 7): four variants
     unsigned kb[4];
     {
@@ -421,7 +497,6 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
 #pragma unroll
     for (int par = 0; par < 2; ++par)
         vb[par] = lds0 + (unsigned)((4 * h + tr_q) * ROWB + ((((par ^ (tr_q >> 1)) << 2) | ((tr_g1 ^ (tr_q & 1)) << 1) | (tr_p >> 1)) << 4) + ((tr_p & 1) << 3));
-    typedef __attribute__((address_space(3))) char lc;
     typedef unsigned u32x4_af __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) u32x4_af lu4;
 
@@ -474,13 +549,53 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
                 }                                                                                                                  \
             }                                                                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                                                     \
-            if (!(PROJ && (t) >= 2 * NKT && (pj.dbg & 4)))                                                                         \
+            if (!(PROJ && (t) >= T0 + 2 * NKT && (pj.dbg & 4)))                                                                         \
             _Pragma("unroll") for (int u = 0; u < FG; ++u) at_mma<T>(__builtin_bit_cast(tx8, kf[cur][u]), __builtin_bit_cast(tx8, BF[g0 + u]), ACC); \
             __builtin_amdgcn_sched_barrier(0);                                                                                     \
         }                                                                                                                          \
         AF_STAMP()                                                                                                                 \
     }
-#define AF_K_TILE(t) AF_A_TILE(t, qf, st[t])
+    // 16 accumulators of a 32 x 32 tile (lane = query, register j = channel 32 ct + (j & 3) + 8 (j >> 2) + 4 h) -> 16-bit B operands.  Per 16
+    // channels the lane holds {0-3} + 4 h (jg even) and {8-11} + 4 h (jg odd) as two register pairs X, Y; swapping X's upper half-wave with
+    // Y's lower one leaves h = 0 with channels 0-7 and h = 1 with 8-15 (v_permlane32_swap): the layout of the Q^T fragments
+#define AF_ACC_TO_B(DST, VAL)                                                                                                      \
+    _Pragma("unroll") for (int ct = 0; ct < CT; ++ct) _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                            \
+        typedef T tx2 __attribute__((ext_vector_type(2)));                                                                         \
+        float w4[4];                                                                                                               \
+        _Pragma("unroll") for (int p2 = 0; p2 < 4; ++p2) { /* p2 = 0, 1: X (jg = 2 s2); 2, 3: Y (jg = 2 s2 + 1) */                  \
+            const int j = (2 * s2 + (p2 >> 1)) * 4 + (p2 & 1) * 2;                                                                 \
+            tx2 v;                                                                                                                 \
+            v[0] = (T)VAL(ct, j);                                                                                                  \
+            v[1] = (T)VAL(ct, j + 1);                                                                                              \
+            w4[p2] = __builtin_bit_cast(float, v);                                                                                 \
+        }                                                                                                                          \
+        permlane32_swap(w4[0], w4[2]);                                                                                             \
+        permlane32_swap(w4[1], w4[3]);                                                                                             \
+        DST[2 * ct + s2] = make_uint4(__builtin_bit_cast(unsigned, w4[0]), __builtin_bit_cast(unsigned, w4[1]), __builtin_bit_cast(unsigned, w4[2]), \
+                                      __builtin_bit_cast(unsigned, w4[3]));                                                        \
+    }
+    // the lane's a / b / c values of accumulator (ct, j): rows3 + row * C floats, channel 32 ct + 8 (j >> 2) + 4 h + (j & 3)
+    auto row_val = [&](int row, int ct, int j) __attribute__((always_inline)) -> float {
+        const f32x4 v = *(const lf4*)(rows3 + (row * C + 32 * ct + 8 * (j >> 2) + 4 * h) * 4);
+        return v[j & 3];
+    };
+    if constexpr (FOLD) {
+        // ---- phase 0: y^T = M n_q^T, the rows of M streamed in tiles of 32; y' = a (y + c) becomes the Q^T operand ----
+        f32x16 yt[CT];
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) yt[t][j] = 0.f;
+#define AF_M_TILE(t) AF_A_TILE(t, qf, yt[t])
+        AF_M_TILE(0) AF_M_TILE(1) AF_M_TILE(2) AF_M_TILE(3)
+        if constexpr (CT > 4) { AF_M_TILE(4) AF_M_TILE(5) AF_M_TILE(6) AF_M_TILE(7) }
+#undef AF_M_TILE
+#define AF_YVAL(ct, j) ((yt[ct][j] + row_val(2, ct, j)) * row_val(0, ct, j))
+        AF_ACC_TO_B(qf, AF_YVAL)
+#undef AF_YVAL
+        AF_STAMP()
+    }
+#define AF_K_TILE(t) AF_A_TILE(T0 + (t), qf, st[t])
     AF_K_TILE(0) AF_K_TILE(1) AF_K_TILE(2) AF_K_TILE(3) AF_K_TILE(4) AF_K_TILE(5) AF_K_TILE(6) AF_K_TILE(7)
 #undef AF_K_TILE
     // ---- phase 2: softmax of the lane's query over its 128 keys (the other 128 are on lane ^ 32) ----
@@ -499,8 +614,9 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const float p = __builtin_amdgcn_exp2f(fmaf(st[t][j], c1, -m));
-            l += p;
             pf[t][j >> 3][j & 7] = (T)p;
+            if constexpr (FOLD) l += (float)pf[t][j >> 3][j & 7];  // the sum of what the matrix product is fed
+            else l += p;
         }
     const float ltot = l + __shfl_xor(l, 32, 64);
     AF_STAMP()
@@ -519,8 +635,8 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
     }
 #define AF_V_TILE(t)                                                                                                               \
     {                                                                                                                              \
-        AF_STEP_SYNC(NKT + (t));                                                                                                   \
-        constexpr unsigned so = (unsigned)(((NKT + (t)) % NSLOT) * TILEB);                                                         \
+        AF_STEP_SYNC(T0 + NKT + (t));                                                                                              \
+        constexpr unsigned so = (unsigned)(((T0 + NKT + (t)) % NSLOT) * TILEB);                                                    \
         constexpr int VG = 2;                                                                                                      \
         s16x4 vlo[2][VG][2], vhi[2][VG][2];                                                                                        \
         AF_VREAD(0, vlo[0], vhi[0])                                                                                                \
@@ -560,28 +676,11 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
             }
         }
     } else {
-        // O^T -> 16-bit B operands of phase 4.  Per 16 channels the lane holds {0-3} + 4 h (jg even) and {8-11} + 4 h (jg odd) as two
-        // register pairs X, Y; swapping X's upper half-wave with Y's lower one leaves h = 0 with channels 0-7 and h = 1 with 8-15
+        // O^T -> 16-bit B operands of phase 4 (AF_ACC_TO_B); FOLD: the norm's a o + b on the way, still one rounding
         uint4 of[KSTEPS];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                typedef T tx2 __attribute__((ext_vector_type(2)));
-                float w4[4];
-#pragma unroll
-                for (int p2 = 0; p2 < 4; ++p2) {  // p2 = 0, 1: X (jg = 2 s2); 2, 3: Y (jg = 2 s2 + 1)
-                    const int j = (2 * s2 + (p2 >> 1)) * 4 + (p2 & 1) * 2;
-                    tx2 v;
-                    v[0] = (T)at_keep_f32(o[ct][j] * inv);
-                    v[1] = (T)at_keep_f32(o[ct][j + 1] * inv);
-                    w4[p2] = __builtin_bit_cast(float, v);
-                }
-                permlane32_swap(w4[0], w4[2]);
-                permlane32_swap(w4[1], w4[3]);
-                of[2 * ct + s2] = make_uint4(__builtin_bit_cast(unsigned, w4[0]), __builtin_bit_cast(unsigned, w4[1]), __builtin_bit_cast(unsigned, w4[2]),
-                                             __builtin_bit_cast(unsigned, w4[3]));
-            }
+#define AF_OVAL(ct, j) (FOLD ? fmaf(o[ct][j] * inv, row_val(0, ct, j), row_val(1, ct, j)) : at_keep_f32(o[ct][j] * inv))
+        AF_ACC_TO_B(of, AF_OVAL)
+#undef AF_OVAL
         AF_STAMP()
         // ---- phase 4: out^T = Wp O^T, the proj matrix streamed in row tiles of 32 couts ----
         f32x16 ot[CT];
@@ -589,7 +688,7 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
         for (int t = 0; t < CT; ++t)
 #pragma unroll
             for (int j = 0; j < 16; ++j) ot[t][j] = 0.f;
-#define AF_W_TILE(t) AF_A_TILE(2 * NKT + (t), of, ot[t])
+#define AF_W_TILE(t) AF_A_TILE(T0 + 2 * NKT + (t), of, ot[t])
         AF_W_TILE(0) AF_W_TILE(1) AF_W_TILE(2) AF_W_TILE(3)
         if constexpr (CT > 4) { AF_W_TILE(4) AF_W_TILE(5) AF_W_TILE(6) AF_W_TILE(7) }
 #undef AF_W_TILE
@@ -706,6 +805,7 @@ __global__ void __launch_bounds__(256) attn_full_kernel(const T* __restrict__ qk
 #undef AF_STAMP
 #undef AF_A_TILE
 #undef AF_STEP_SYNC
+#undef AF_ACC_TO_B
 }
 
 // The same whole-row form for launches that do NOT fill the chip (batch < 128): a wave's chain above is 256 dependent MFMAs whatever
@@ -877,22 +977,24 @@ static int launch_attn_split_t(const T* qkv, const AttnGeom& g, T* out, float* l
     return DMME_OK;
 }
 
-template <int D, typename T, bool PROJ = false>
-static int launch_attn_full_t(const T* qkv, const AttnGeom& g, T* out, float* lse, hipStream_t s, const AttnProj& pj = AttnProj{}) {
+template <int D, typename T, bool PROJ = false, bool FOLD = false>
+static int launch_attn_full_t(const T* qkv, const AttnGeom& g, T* out, float* lse, hipStream_t s, const AttnProj& pj = AttnProj{},
+                              const typename std::conditional<FOLD, AttnFold, AttnNoFold>::type& fd = {}) {
     const int rows = g.N * g.heads;
     const size_t ring = (size_t)8 * AT_KT * D * 2, stage = (size_t)4 * 32 * (D * 4 + 16);  // (PROJ: the epilogue's fp32 staging tiles lie over the ring)
+    const size_t rows3 = FOLD ? (size_t)3 * D * 4 : 0;                                       // (FOLD: the a / b / c rows behind them)
 #ifdef AT_STAMPS
-    const size_t lds = (PROJ && stage > ring ? stage : ring) + 1024;  // (+ the diagnostic stamps' buffer)
+    const size_t lds = (PROJ && stage > ring ? stage : ring) + 1024 + rows3;  // (+ the diagnostic stamps' buffer)
 #else
-    const size_t lds = PROJ && stage > ring ? stage : ring;
+    const size_t lds = (PROJ && stage > ring ? stage : ring) + rows3;
 #endif
     static bool attr_done = false;
     if (!attr_done) {
-        DMME_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_full_kernel<D, T, PROJ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        DMME_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_full_kernel<D, T, PROJ, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_done = true;
     }
     const int xcd_order = ((!debug_route("no_xcd_order") && rows % 8 == 0) ? 1 : 0) | ((debug_route("attn_sleep", -1) >= 0 ? debug_route("attn_sleep", -1) : rows * 2 >= 256 ? 2 : 0) << 1);  // pacing level (kernel comment): s_sleep 4 per tile where the launch fills the chip
-    hipLaunchKernelGGL((attn_full_kernel<D, T, PROJ>), dim3((unsigned)(rows * 2)), dim3(256), lds, s, qkv, g, out, lse, xcd_order, pj);
+    hipLaunchKernelGGL((attn_full_kernel<D, T, PROJ, FOLD>), dim3((unsigned)(rows * 2)), dim3(256), lds, s, qkv, g, out, lse, xcd_order, pj, fd);
     DMME_CHECK_LAUNCH();
     return DMME_OK;
 }
@@ -980,6 +1082,36 @@ int launch_attn_proj(int dtype, const void* qkv, int N, int S, int C, void* ctx,
     if (dtype == DMME_F16)
         return C == 256 ? launch_attn_full_t<256, f16, true>((const f16*)qkv, g, (f16*)ctx, lse, s, pj) : launch_attn_full_t<128, f16, true>((const f16*)qkv, g, (f16*)ctx, lse, s, pj);
     return C == 256 ? launch_attn_full_t<256, bf16, true>((const bf16*)qkv, g, (bf16*)ctx, lse, s, pj) : launch_attn_full_t<128, bf16, true>((const bf16*)qkv, g, (bf16*)ctx, lse, s, pj);
+}
+// the folded block (attn_full_kernel<.., PROJ, FOLD>, AttnFold): x in, out = res + block(x) out.  Any N >= 1 (whether the launch fills the
+// chip is the plan's decision); gni null: the norm's rows are read from scale / shift [N][C]
+bool attn_fold_shape_ok(int dtype, int N, int S, int C, int gn_cg, int gn_tiles) {
+    if (!is16(dtype) || S != 256 || (C != 128 && C != 256) || N < 1) return false;
+    return gn_tiles == 0 || ((gn_cg == 4 || gn_cg == 8) && C % gn_cg == 0 && gn_tiles == S / 32);
+}
+int launch_attn_fold(int dtype, const void* x, int N, int S, int C, const GnIn* gni, const float* scale, const float* shift, const void* M, const float* c,
+                     const void* wpv, const float* bias2, const void* res, void* dst, float* gn_part, int gn_tiles, int gn_cg, hipStream_t s, long long* stamps) {
+    DMME_REQUIRE(attn_fold_shape_ok(dtype, N, S, C, gn_part ? gn_cg : 0, gn_part ? gn_tiles : 0) && x && M && c && wpv && bias2 && res && dst && (gni || (scale && shift)),
+                 DMME_ERR_UNSUPPORTED, "attn_fold: unsupported shape N=%d S=%d C=%d (statistics tiles %d, %d channels per group) or a null operand", N, S, C, gn_tiles, gn_cg);
+    if (gni) {  // the one-batch form of gn_in_scale_shift_g: at most 32 partials per group, one source
+        const int fg = gni->C1 / gni->groups, nf = fg > 0 ? (C / gni->groups) / fg : 0;
+        DMME_REQUIRE(gni->p1 && !gni->p2 && gni->C1 == C && gni->groups > 0 && C % gni->groups == 0 && (nf == 1 || nf == 2 || nf == 4) && gni->t1 * nf <= 32 && !gni->t_scale,
+                     DMME_ERR_UNSUPPORTED, "attn_fold: the norm's partials (%d tiles, %d channels, %d groups) are not a single unconditioned source of at most 32", gni->t1, gni->C1, gni->groups);
+    }
+    AttnGeom g{S, C, C, 1, N, 1.0f};  // rows of x; C^-0.5 is inside M and c
+    const AttnProj pj{wpv, bias2, res, dst, gn_part, gn_tiles, gn_cg, stamps, 0};
+    AttnFold fd{};
+    fd.M = M;
+    fd.c = c;
+    fd.scale = scale;
+    fd.shift = shift;
+    if (gni) {
+        fd.gni = *gni;
+        fd.has_gni = 1;
+    }
+    if (dtype == DMME_F16)
+        return C == 256 ? launch_attn_full_t<256, f16, true, true>((const f16*)x, g, nullptr, nullptr, s, pj, fd) : launch_attn_full_t<128, f16, true, true>((const f16*)x, g, nullptr, nullptr, s, pj, fd);
+    return C == 256 ? launch_attn_full_t<256, bf16, true, true>((const bf16*)x, g, nullptr, nullptr, s, pj, fd) : launch_attn_full_t<128, bf16, true, true>((const bf16*)x, g, nullptr, nullptr, s, pj, fd);
 }
 
 // =====================================================================================

@@ -384,6 +384,20 @@ int launch_attn_mfma(int dtype, const void* qkv, int N, int S, int C, void* out,
 bool attn_proj_fusable(int dtype, int N, int S, int C, int gn_cg, int gn_tiles);
 int launch_attn_proj(int dtype, const void* qkv, int N, int S, int C, void* ctx, float* lse, const void* w, const float* bias, const void* res, void* dst,
                      float* gn_part, int gn_tiles, int gn_cg, hipStream_t s, long long* stamps = nullptr);
+// the folded single-head block (attn_mfma.hip, AttnFold): x [N][S][C] in, dst = res + block(x) out, no qkv tensor.  The norm in front of
+// the block comes as its producers' partials (gni) or, gni null, as (scale, shift) rows [N][C]; M / c / wpv / bias2 are the folded
+// slots of the packed buffer (launch_attn_fold_weights).  Any N >= 1.
+struct AttnFoldJob {  // one block's fold: byte offsets into the packed buffer
+    int64_t wq, bq, wp, bp;      // in: qkv weight [3C][C] 16-bit and bias [3C] fp32, proj weight [C][C] and bias [C]
+    int64_t M, c, wpv, bias2;    // out: 16-bit [C][C] x 2, fp32 [C] x 2
+    int32_t C, pad;
+};
+bool attn_fold_shape_ok(int dtype, int N, int S, int C, int gn_cg, int gn_tiles);
+int launch_attn_fold(int dtype, const void* x, int N, int S, int C, const GnIn* gni, const float* scale, const float* shift, const void* M, const float* c,
+                     const void* wpv, const float* bias2, const void* res, void* dst, float* gn_part, int gn_tiles, int gn_cg, hipStream_t s,
+                     long long* stamps = nullptr);
+// M = s Wk^T Wq, c = s Wk^T bq, Wpv = Wp Wv, b' = Wp bv + bp (s = C^-0.5) of every job: fp32 sums over the 16-bit weights, one rounding
+int launch_attn_fold_weights(int dtype, const AttnFoldJob* jobs_dev, int n_jobs, int maxC, void* packed, hipStream_t s, const AttnFoldJob* one = nullptr);
 bool attn_heads_mfma_supported(int dtype, int N, int S, int C, int heads);
 int launch_attn_heads_mfma(int dtype, const void* qkv, int N, int S, int C, int heads, void* out, float* lse, hipStream_t s);
 int launch_attn_heads_bwd_mfma(int dtype, const void* qkv, const void* O, const void* dO, const float* lse, int N, int S, int C, int heads, void* P,

@@ -903,6 +903,55 @@ int launch_pack_table(int dtype, const PackItem* items_dev, int n_items, const f
     return DMME_OK;
 }
 
+// ------------------------------------------------------------------ folded attention blocks (attn_mfma.hip, AttnFold)
+// Per job (one single-head block of width C): M = s Wk^T Wq and Wpv = Wp Wv as 16-bit [C][C] rows, c = s Wk^T bq and b' = Wp bv + bp as
+// fp32 rows, s = C^-0.5.  Sums in fp32 over the 16-bit weights the unfolded kernels read, one rounding.  blockIdx.x = job, blockIdx.y =
+// row i of both matrices; thread j = column (the loop over o reads Wq / Wv rows coalesced; Wk^T's column i is one broadcast per o).
+// Once per weight version: nothing here is worth tuning.
+template <typename T>
+__global__ void __launch_bounds__(256) attn_fold_weights_kernel(const AttnFoldJob* __restrict__ jobs, AttnFoldJob one, char* __restrict__ packed) {
+    const AttnFoldJob jb = jobs ? jobs[blockIdx.x] : one;  // (one: a single job by value - the single-op entry point)
+    const int C = jb.C, i = blockIdx.y, j = threadIdx.x;
+    if (i >= C) return;
+    const T* wq = (const T*)(packed + jb.wq);
+    const T* wk = wq + (int64_t)C * C;
+    const T* wv = wk + (int64_t)C * C;
+    const T* wp = (const T*)(packed + jb.wp);
+    const float* bq = (const float*)(packed + jb.bq);
+    const float* bv = bq + 2 * C;
+    const float s = 1.0f / sqrtf((float)C);
+    if (j < C) {
+        float m = 0.f, pv = 0.f;
+        for (int o = 0; o < C; ++o) {
+            m = fmaf((float)wk[(int64_t)o * C + i], (float)wq[(int64_t)o * C + j], m);
+            pv = fmaf((float)wp[(int64_t)i * C + o], (float)wv[(int64_t)o * C + j], pv);
+        }
+        ((T*)(packed + jb.M))[(int64_t)i * C + j] = from_f<T>(m * s);
+        ((T*)(packed + jb.wpv))[(int64_t)i * C + j] = from_f<T>(pv);
+    }
+    if (j == 0) {
+        float c = 0.f, b2 = 0.f;
+        for (int o = 0; o < C; ++o) {
+            c = fmaf((float)wk[(int64_t)o * C + i], bq[o], c);
+            b2 = fmaf((float)wp[(int64_t)i * C + o], bv[o], b2);
+        }
+        ((float*)(packed + jb.c))[i] = c * s;
+        ((float*)(packed + jb.bias2))[i] = b2 + ((const float*)(packed + jb.bp))[i];
+    }
+}
+int launch_attn_fold_weights(int dtype, const AttnFoldJob* jobs_dev, int n_jobs, int maxC, void* packed, hipStream_t s, const AttnFoldJob* one) {
+    if (n_jobs == 0) return DMME_OK;
+    DMME_REQUIRE((jobs_dev != nullptr) != (one != nullptr) && (!one || n_jobs == 1), DMME_ERR_INVALID, "attn_fold_weights: a device table, or one job by value");
+    const AttnFoldJob j1 = one ? *one : AttnFoldJob{};
+    DMME_REQUIRE(is16(dtype) && maxC >= 1 && maxC <= 256, DMME_ERR_UNSUPPORTED, "attn_fold_weights: 16-bit plans, blocks of at most 256 channels (got %d)", maxC);
+    if (dtype == DMME_F16)
+        hipLaunchKernelGGL(attn_fold_weights_kernel<f16>, dim3((unsigned)n_jobs, (unsigned)maxC), dim3(256), 0, s, jobs_dev, j1, (char*)packed);
+    else
+        hipLaunchKernelGGL(attn_fold_weights_kernel<bf16>, dim3((unsigned)n_jobs, (unsigned)maxC), dim3(256), 0, s, jobs_dev, j1, (char*)packed);
+    DMME_CHECK_LAUNCH();
+    return DMME_OK;
+}
+
 // ------------------------------------------------------------------ diagnostic: what one CU can pull from L2
 // Every workgroup (one per CU) streams the same `bytes` of an L2-resident buffer `iters` times, DEPTH 16-byte loads in flight per
 // thread (mode 0: into registers; mode 1: global -> LDS DMA, no registers; mode m >= 2: DMA gathering eight 128-byte rows per wave instruction, m 16-byte vectors apart).  tools/l2_stream.py turns the elapsed time into bytes

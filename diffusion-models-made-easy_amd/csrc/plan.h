@@ -146,6 +146,12 @@ struct Op {
     // that conv, whose own launch is skipped (fused_away = 2).  The context tensor at_out is then written only by forwards a backward
     // pass may follow (run_op's keep_ctx); the backward pass itself is untouched.
     int at_proj = -1;
+    // The FOLDED form of such a block (attn_mfma.hip, AttnFold; assign_attn_fold): forwards no backward pass follows skip the qkv conv
+    // (op at_fold_qkv) and launch the attention kernel's fold form on the block's raw input, with the folded slots of the packed buffer
+    // (byte offsets; written by dmme_unet_pack_folded, valid for the buffer dmme_plan::fold_packed names).  -1: not foldable.
+    int at_fold_qkv = -1;
+    int folded_into = -1;  // OP_CONV: the qkv conv of attention op `folded_into`, skipped by the walks that run that block folded
+    int64_t fold_M = -1, fold_c = -1, fold_wpv = -1, fold_b2 = -1;
     // precision="fp16r32" (dmme_plan::mix): how this conv of the fp32 level runs.  mix: ConvArgs::mix (1 / 2: split-pass 3x3 kernel, 3: split-pass
     // thin output conv); route_f32: on the fp32-tensor kernels with three-pass bf16 products (input conv, the blocks' 1x1 residual convs)
     int mix = 0, route_f32 = 0;
@@ -263,6 +269,13 @@ struct dmme_plan {
     // the workspace the last forward wrote WITHOUT the tensors only a backward pass reads (dmme_unet_forward_nograd, dmme_chain_step):
     // dmme_unet_backward refuses it instead of differentiating stale activations (null: the last forward kept everything)
     mutable const void* nograd_ws = nullptr;
+    // folded attention blocks: one job per foldable block (dmme_unet_pack_folded), the launches of the no-grad walk with every fold
+    // in place, and the packed buffer whose folded slots are current (null: none - dmme_unet_pack_params of that buffer clears it, and
+    // a no-grad forward with any other buffer runs the unfolded walk)
+    std::vector<AttnFoldJob> fold_jobs;
+    DevTable<AttnFoldJob> fold_jobs_dev;
+    int fold_maxC = 0, n_launches_nograd = 0;
+    mutable const void* fold_packed = nullptr;
     // what the network predicts (dmme_unet_plan_set_prediction; host-only): DMME_PRED_X0 / DMME_PRED_V make the capturable chain steps
     // launch dmme_pred_to_eps over the plan's batch right behind the forward, with this device table [pred_T + 1][2] (the caller's)
     int pred = DMME_PRED_EPS, pred_T = 0;
@@ -288,6 +301,7 @@ void assign_levels(dmme_plan* P);
 void assign_rseg(dmme_plan* P);
 int run_level(const dmme_plan* P, const LvlRun& R, const char* pk, char* ws, int nt, const float* drop_masks, hipStream_t s, bool keep_ctx = true);
 void assign_lvl_nograd(dmme_plan* P);
+void assign_attn_fold(dmme_plan* P);
 int lvl_check(const dmme_plan* P, const char* where, hipStream_t stream = nullptr, bool have_stream = false);
 // plan.hip: the weight-gradient image's unpack table, in parameter order (the gradient buckets cut it)
 void build_unpack_items(const dmme_plan* P, std::vector<PackItem>& items);

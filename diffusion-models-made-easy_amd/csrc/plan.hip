@@ -986,6 +986,69 @@ void assign_attn_proj(dmme_plan* P) {
     }
 }
 
+// The no-grad form of those blocks (attn_mfma.hip, AttnFold): no qkv conv, no qkv tensor - the attention launch reads the block's raw input,
+// finishes the norm from its producers' partials and uses matrices folded from the weights (dmme_unet_pack_folded: slots behind the
+// packed parameters).  A block qualifies when its proj conv already rides in the launch, the qkv conv reads ONE tensor through a norm its
+// consumer finishes from partials - or whose (scale, shift) rows are in the workspace by then: a norm its producers' epilogues finish, a
+// norm with a launch - (no conditioning, no activation, no mask), nothing but the attention reads qkv, and the residual is that same tensor.
+// DMME_NO_ATTN_FOLD: off (DMME_NO_ATTN_PROJ / DMME_NO_ATTN_FULL leave nothing to fold).  The backward-capable walk never folds.
+void assign_attn_fold(dmme_plan* P) {
+    if (getenv("DMME_NO_ATTN_FOLD") || debug_route("no_attn_fold") || !is16(P->dtype) || P->x3 || P->mix) return;
+    int64_t cur = P->packed_bytes;
+    const int64_t es = (int64_t)dtype_size(P->dtype);
+    for (int ai = 1; ai < (int)P->ops.size(); ++ai) {
+        Op& at = P->ops[ai];
+        if (at.kind != OP_ATTN || at.at_proj < 0 || at.at_heads != 1 || at.lvl >= 0) continue;
+        Op& qc = P->ops[ai - 1];
+        const Op& pr = P->ops[at.at_proj];
+        if (qc.kind != OP_CONV || qc.dst != at.at_qkv || qc.taps != 1 || qc.src1 < 0 || qc.src2 >= 0 || qc.gn < 0 || qc.pro_silu || qc.out_silu || qc.dmask_off >= 0 ||
+            qc.tproj_col >= 0 || qc.res1 >= 0 || qc.res2 >= 0 || qc.up || qc.stride != 1 || qc.gd_n > 0 || qc.mix || qc.route_f32 || qc.fused_away || qc.rseg >= 0 ||
+            qc.use_act || qc.lvl >= 0 || pr.res1 != qc.src1)
+            continue;
+        const Op& gn = P->ops[qc.gn];
+        const Tensor& tx = P->tensors[qc.src1];
+        const int C = tx.C, groups = P->cfg.num_groups;
+        if (gn.kind != OP_GN || gn.gn_src1 != qc.src1 || gn.gn_src2 >= 0 || gn.gn_mod_col >= 0 || gn.gn_act >= 0 || tx.f32 ||
+            (gn.gn_in_consumer && (tx.stats_off < 0 || tx.stats_tiles > 32)) || P->tensors[at.at_qkv].C != 3 * C || P->params[qc.w].pack_code >= 0 || P->params[pr.w].pack_code >= 0)
+            continue;
+        bool only_here = true;  // qkv read by nothing but this attention (forward ops; the backward reads it, and never follows a folded walk)
+        for (int oi = 0; oi < (int)P->ops.size() && only_here; ++oi) {
+            const Op& o = P->ops[oi];
+            if (oi == ai) continue;
+            if (o.kind == OP_CONV && (o.src1 == at.at_qkv || o.src2 == at.at_qkv || o.res1 == at.at_qkv || o.res2 == at.at_qkv)) only_here = false;
+            if (o.kind == OP_GN && (o.gn_src1 == at.at_qkv || o.gn_src2 == at.at_qkv)) only_here = false;
+            if (o.kind == OP_ATTN && o.at_qkv == at.at_qkv) only_here = false;
+            if (o.kind == OP_CAST && o.cast_src == at.at_qkv) only_here = false;
+        }
+        const Tensor& td = P->tensors[pr.dst];
+        const bool stats = td.stats_off >= 0;
+        if (!only_here || !attn_fold_shape_ok(P->dtype, P->B, tx.H * tx.W, C, stats ? C / groups : 0, stats ? td.stats_tiles : 0)) continue;
+        at.at_fold_qkv = ai - 1;
+        qc.folded_into = ai;
+        at.fold_M = cur;
+        cur = align_up(cur + (int64_t)C * C * es, 256);
+        at.fold_wpv = cur;
+        cur = align_up(cur + (int64_t)C * C * es, 256);
+        at.fold_c = cur;
+        cur = align_up(cur + (int64_t)C * 4, 256);
+        at.fold_b2 = cur;
+        cur = align_up(cur + (int64_t)C * 4, 256);
+        AttnFoldJob jb{};
+        jb.wq = P->params[qc.w].packed_off;
+        jb.bq = P->params[qc.b].packed_off;
+        jb.wp = P->params[pr.w].packed_off;
+        jb.bp = P->params[pr.b].packed_off;
+        jb.M = at.fold_M;
+        jb.c = at.fold_c;
+        jb.wpv = at.fold_wpv;
+        jb.bias2 = at.fold_b2;
+        jb.C = C;
+        P->fold_jobs.push_back(jb);
+        if (C > P->fold_maxC) P->fold_maxC = C;
+    }
+    P->packed_bytes = cur;
+}
+
 int run_gn(const dmme_plan* P, const Op& o, const char* pk, char* ws, int nt, const float* drop_masks, hipStream_t s) {
     if (o.gn_direct || o.gn_in_consumer) return DMME_OK;  // its producers (its consumer) wrote scale / shift / {mean, rstd} (and act)
     // scale-shift conditioning (iddpm.ResBlock): (shift | scale) columns of the batched time projection
@@ -1033,6 +1096,9 @@ int run_op(const dmme_plan* P, const Op& o, const char* pk, const float* x, cons
            char* ws, const float* drop_masks, hipStream_t s, bool keep_ctx, const int64_t* labels = nullptr, int* status = nullptr) {
     if (o.lvl >= 0) return o.lvl_first ? run_level(P, P->lvl_runs[o.lvl], pk, ws, nt, drop_masks, s, keep_ctx) : DMME_OK;
     if (o.fused_away) return DMME_OK;  // a residual 1x1 conv that runs inside its block's conv2 (assign_rseg)
+    // folded attention blocks: only where no backward follows AND this buffer's folded slots are current (never stale matrices)
+    const bool fold = !keep_ctx && P->fold_packed == (const void*)pk;
+    if (fold && o.kind == OP_CONV && o.folded_into >= 0) return DMME_OK;  // the qkv conv of a block that runs folded
     switch (o.kind) {
         case OP_SINUS:
             return launch_time_sinusoid(t, nt, (const float*)(pk + P->params[P->freqs_param].packed_off),
@@ -1066,6 +1132,13 @@ int run_op(const dmme_plan* P, const Op& o, const char* pk, const float* x, cons
         case OP_ATTN: {
             const Tensor& q = P->tensors[o.at_qkv];
             const int S = q.H * q.W, C = q.C / 3;
+            if (fold && o.at_fold_qkv >= 0) {  // no qkv: the block's raw input, the norm's partials, the folded slots (assign_attn_fold)
+                ConvArgs a{}, qa{};
+                fill_conv(P, P->ops[o.at_proj], pk, x, y, ws, drop_masks, nt, a, true);
+                fill_conv(P, P->ops[o.at_fold_qkv], pk, x, y, ws, drop_masks, nt, qa, true);
+                return launch_attn_fold(P->dtype, qa.src1, P->B, S, C, qa.has_gni ? &qa.gni : nullptr, qa.scale, qa.shift, pk + o.fold_M, (const float*)(pk + o.fold_c), pk + o.fold_wpv,
+                                        (const float*)(pk + o.fold_b2), a.res1, a.dst, a.gn_part, a.gn_tiles, a.gn_cg, s);
+            }
             if (o.at_proj >= 0) {  // the block's proj conv + residual inside the launch (assign_attn_proj)
                 ConvArgs a{};
                 fill_conv(P, P->ops[o.at_proj], pk, x, y, ws, drop_masks, nt, a, true);
@@ -1227,10 +1300,10 @@ static int check_mix_kernels(const dmme_plan* P) {
     return DMME_OK;
 }
 
-static int count_launches(const dmme_plan* P) {
+static int count_launches(const dmme_plan* P, bool nograd = false) {
     int n = 0;
     for (const Op& o : P->ops) {
-        if (o.fused_away) continue;
+        if (o.fused_away || (nograd && o.folded_into >= 0)) continue;
         if (o.lvl >= 0)
             n += o.lvl_first;
         else if (o.kind == OP_GN)
@@ -1262,6 +1335,7 @@ static int upload_tables(dmme_plan* P) {
     DMME_TRY(P->tp_tiles_dev.upload(P->tp_tiles));
     DMME_TRY(P->col_jobs_dev.upload(P->col_jobs));
     DMME_TRY(P->bias_jobs_dev.upload(P->bias_jobs));
+    if (!P->fold_jobs.empty()) DMME_TRY(P->fold_jobs_dev.upload(P->fold_jobs));
     std::vector<dmme_plan::WgGroup*> all_groups{&P->wg[0], &P->wg[1], &P->wg[2]};
     for (auto& B_ : P->gb)
         for (int k = 0; k < 3; ++k) all_groups.push_back(&B_.wg[k]);
@@ -1286,7 +1360,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 114; }  // 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 115; }  // 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1321,7 +1395,9 @@ DMME_API int dmme_unet_plan_create(const dmme_unet_cfg* cfg, int B, int H, int W
     assign_rseg(P);
     assign_attn_proj(P);
     assign_lvl_nograd(P);
+    assign_attn_fold(P);
     P->n_launches = count_launches(P);
+    P->n_launches_nograd = count_launches(P, true);
     plan_backward(P);
     if (device >= 0) DMME_TRY(upload_tables(P));
     *out = owned.release();
@@ -1354,11 +1430,26 @@ DMME_API int64_t dmme_unet_plan_workspace_bytes(const dmme_plan* plan) { return 
 DMME_API int64_t dmme_unet_plan_dropmask_numel(const dmme_plan* plan) { return plan ? plan->dropmask_numel : 0; }
 DMME_API int dmme_unet_plan_out_channels(const dmme_plan* plan) { return plan ? plan->out_channels : 0; }
 DMME_API int dmme_unet_plan_num_launches(const dmme_plan* plan) { return plan ? plan->n_launches : 0; }
+DMME_API int dmme_unet_plan_num_launches_nograd(const dmme_plan* plan) { return plan ? plan->n_launches_nograd : 0; }
+DMME_API int dmme_unet_plan_num_folded(const dmme_plan* plan) { return plan ? (int)plan->fold_jobs.size() : 0; }
 
 DMME_API int dmme_unet_pack_params(const dmme_plan* plan, const float* ref_flat, void* packed, void* stream) {
     DMME_REQUIRE(plan && ref_flat && packed, DMME_ERR_INVALID, "pack_params: null argument");
     DMME_REQUIRE(plan->items_dev, DMME_ERR_INVALID, "pack_params: plan was created without a device");
+    if (plan->fold_packed == packed) plan->fold_packed = nullptr;  // the folded slots describe the weights this call overwrites
     return launch_pack_table(plan->dtype, plan->items_dev.get(), plan->n_items, ref_flat, packed, (hipStream_t)stream);
+}
+
+// The folded attention matrices of `packed` (assign_attn_fold), from the 16-bit weights dmme_unet_pack_params left there: call it behind
+// that, on the same stream, ahead of the no-grad forwards / chain steps of a weight version.  Until the next dmme_unet_pack_params of
+// this buffer those walks then run their foldable blocks folded; with any other buffer, or without this call, they run unfolded.
+DMME_API int dmme_unet_pack_folded(const dmme_plan* plan, void* packed, void* stream) {
+    DMME_REQUIRE(plan && packed, DMME_ERR_INVALID, "pack_folded: null argument");
+    DMME_REQUIRE(plan->items_dev, DMME_ERR_INVALID, "pack_folded: plan was created without a device");
+    if (plan->fold_jobs.empty()) return DMME_OK;
+    const int rc = launch_attn_fold_weights(plan->dtype, plan->fold_jobs_dev.get(), (int)plan->fold_jobs.size(), plan->fold_maxC, packed, (hipStream_t)stream);
+    if (rc == DMME_OK) plan->fold_packed = packed;
+    return rc;
 }
 
 // labels / status: the conditional form (dmme_unet_forward_cond); a conditional plan never runs without labels
@@ -1967,6 +2058,41 @@ DMME_API int dmme_attention_proj(int dtype, const void* qkv, int N, int S, int C
                                  float* gn_part, int gn_cg, void* stream) {
     DMME_REQUIRE(qkv && w && bias && res && dst && N > 0 && S > 0 && C > 0, DMME_ERR_INVALID, "attention_proj: bad argument");
     return launch_attn_proj(dtype, qkv, N, S, C, ctx, nullptr, w, bias, res, dst, gn_part, S / 32, gn_cg, (hipStream_t)stream, g_stamps);
+}
+
+// one folded block as a single op (attn_mfma.hip, AttnFold): the fold of its weights, then the launch
+DMME_API int dmme_attention_fold(int dtype, int C, const void* wqkv, const float* bqkv, const void* wp, const float* bp, void* M, float* c, void* wpv, float* bias2,
+                                 void* stream) {
+    DMME_REQUIRE(wqkv && bqkv && wp && bp && M && c && wpv && bias2 && C > 0, DMME_ERR_INVALID, "attention_fold: bad argument");
+    AttnFoldJob jb{};  // byte offsets from a null base: the addresses themselves
+    jb.wq = (int64_t)(intptr_t)wqkv;
+    jb.bq = (int64_t)(intptr_t)bqkv;
+    jb.wp = (int64_t)(intptr_t)wp;
+    jb.bp = (int64_t)(intptr_t)bp;
+    jb.M = (int64_t)(intptr_t)M;
+    jb.c = (int64_t)(intptr_t)c;
+    jb.wpv = (int64_t)(intptr_t)wpv;
+    jb.bias2 = (int64_t)(intptr_t)bias2;
+    jb.C = C;
+    return launch_attn_fold_weights(dtype, nullptr, 1, C, nullptr, (hipStream_t)stream, &jb);
+}
+DMME_API int dmme_attention_block(int dtype, const void* x, int N, int S, int C, const float* parts, int part_tiles, int part_cnt, int groups, const float* gamma,
+                                  const float* beta, float eps, float* scale, float* shift, const void* M, const float* c, const void* wpv, const float* bias2,
+                                  const void* res, void* dst, float* gn_part, int gn_cg, void* stream) {
+    DMME_REQUIRE(x && M && c && wpv && bias2 && res && dst && N > 0 && S > 0 && C > 0, DMME_ERR_INVALID, "attention_block: bad argument");
+    GnIn gni{};
+    if (parts) {  // the norm finished inside the launch from [N][part_tiles][groups] {mean, M2} partials of part_cnt elements each
+        DMME_REQUIRE(gamma && beta && groups > 0 && part_tiles > 0 && part_cnt > 0, DMME_ERR_INVALID, "attention_block: partials without gamma / beta / geometry");
+        gni.p1 = parts;
+        gni.t1 = part_tiles;
+        gni.cnt1 = part_cnt;
+        gni.C1 = C;
+        gni.groups = groups;
+        gni.gamma = gamma;
+        gni.beta = beta;
+        gni.eps = eps;
+    }
+    return launch_attn_fold(dtype, x, N, S, C, parts ? &gni : nullptr, scale, shift, M, c, wpv, bias2, res, dst, gn_part, S / 32, gn_cg, (hipStream_t)stream, g_stamps);
 }
 
 DMME_API int dmme_attention_heads(int dtype, const void* qkv, int N, int S, int C, int heads, void* out, int force_generic, void* stream) {

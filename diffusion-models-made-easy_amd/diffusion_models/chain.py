@@ -4,6 +4,7 @@ replayable step.  The processes (ddpm.py and the samplers built on it) supply th
 
 from __future__ import annotations
 
+import gc
 from typing import Optional
 
 import torch
@@ -127,12 +128,22 @@ def capture(launch, check, carried=()):
     check()
     restore()
     graph, out, error = None, None, None
+    # No finalizer may run inside the capture: a dropped network's plan frees its device tables, a dropped runner's graph gives back its
+    # memory pool - device-memory calls the capture forbids - and torch's capture no longer collects garbage on entry, so Python's
+    # automatic collector could pick any allocation inside `launch()` to run them.  Collect now; keep the collector off until the
+    # capture has ended.
+    gc.collect()
+    gc_was_on = gc.isenabled()
+    gc.disable()
     try:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             out = launch()
     except RuntimeError as exc:
         graph, out, error = None, None, exc
+    finally:
+        if gc_was_on:
+            gc.enable()
     restore()
     return graph, out, error
 
@@ -194,13 +205,13 @@ class ChainRunner(ChainTables):
 
     def _weights_key(self):
         """identifies the packed weights the captured graph reads"""
-        return (self.plan.packed_version, self.plan.packed.data_ptr())
+        return (self.plan.packed_version, self.plan.fold_version, self.plan.packed.data_ptr())
 
     def step(self):
         model = self.model
         if model.training:
             raise RuntimeError("ChainRunner: sampling chains run in eval mode (no dropout masks inside the replayed step)")
-        packed = model._packed_for(self.plan)  # re-packs when the parameters changed
+        packed = model._packed_for(self.plan, fold=True)  # re-packs (and re-folds the attention blocks) when the parameters changed
         wkey = self._weights_key()
         if not self.use_graph or self.capture_error is not None:
             self._launch(packed)

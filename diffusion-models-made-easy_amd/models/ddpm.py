@@ -53,6 +53,7 @@ class _Plan:
         self.workspace = None
         self.packed = None
         self.packed_version = None
+        self.fold_version = None  # the weight version the folded attention slots of `packed` were computed for (dmme_unet_pack_folded)
         self.fwd_gen = 0
 
     def overwritten(self):
@@ -295,12 +296,19 @@ class UNet(nn.Module):
             self._plans[key] = plan
         return plan
 
-    def _packed_for(self, plan: _Plan) -> Tensor:
+    def _packed_for(self, plan: _Plan, fold: bool = False) -> Tensor:
+        """the packed weights of `plan`, re-packed when the parameters changed.  fold: a no-grad forward or a sampling chain follows -
+        the folded matrices of the attention blocks are brought up to this weight version too (once per version; the training step's
+        re-pack never pays for them, and it ends their validity on the C side: a later no-grad forward cannot read stale ones)"""
         flat = self._ensure_flat()
         ver = self._weights_key(flat)
         if plan.packed_version != ver:
             _lib.check(plan.lib.dmme_unet_pack_params(plan.h, _lib.ptr(flat), _lib.ptr(plan.packed), _lib.stream_ptr()), "dmme_unet_pack_params")
             plan.packed_version = ver
+            plan.fold_version = None
+        if fold and plan.fold_version != ver:
+            _lib.check(plan.lib.dmme_unet_pack_folded(plan.h, _lib.ptr(plan.packed), _lib.stream_ptr()), "dmme_unet_pack_folded")
+            plan.fold_version = ver
         return plan.packed
 
     def inject_dropout_masks(self, masks: Optional[Tensor]):
@@ -498,7 +506,7 @@ class UNet(nn.Module):
             raise _lib.DmmeError("UNet.forward while a gradient exchange of this model is in flight: call reducer.finish() first")
         B, _, H, W = x.shape
         plan = self._plan_for(B, H, W, x.device)
-        packed = self._packed_for(plan)
+        packed = self._packed_for(plan, fold=not want_ctx)
         xin = x.detach().to(torch.float32).contiguous()
         if c.is_floating_point() and bool((c != c.round()).any()):
             # the reference's sinusoid accepts any real t (models/ddpm.py:347); every caller passes integer timesteps and the C ABI

@@ -134,10 +134,22 @@ DMME_API int64_t dmme_unet_plan_dropmask_numel(const dmme_plan* plan);
 DMME_API int dmme_unet_plan_out_channels(const dmme_plan* plan);
 /* number of kernel launches one forward issues (for launch-overhead accounting) */
 DMME_API int dmme_unet_plan_num_launches(const dmme_plan* plan);
+/* ... of dmme_unet_forward_nograd / dmme_chain_step with every foldable attention block folded (dmme_unet_pack_folded): one launch
+ * fewer per such block.  dmme_unet_plan_num_launches and dmme_unet_plan_op_info describe the form a backward pass can follow.
+ * dmme_unet_plan_num_folded: how many blocks that is (0: nothing to fold - other batch sizes, precisions, DMME_NO_ATTN_FOLD). */
+DMME_API int dmme_unet_plan_num_launches_nograd(const dmme_plan* plan);
+DMME_API int dmme_unet_plan_num_folded(const dmme_plan* plan);
 
 /* fp32 reference-layout flat buffer -> packed buffer (replaces nothing in the
- * reference; it is the load_state_dict side of the boundary). */
+ * reference; it is the load_state_dict side of the boundary).  Ends the validity of this buffer's folded slots (below). */
 DMME_API int dmme_unet_pack_params(const dmme_plan* plan, const float* ref_flat, void* packed, void* stream);
+/* Once per weight version, behind dmme_unet_pack_params on the same stream and ahead of no-grad forwards / chain steps: the folded
+ * matrices of the single-head 16x16 attention blocks (M = C^-0.5 Wk^T Wq, c = C^-0.5 Wk^T bq, Wpv = Wp Wv, b' = Wp bv + bp; fp32 sums
+ * over the 16-bit weights in `packed`, one rounding) into their slots of `packed` (dmme_unet_plan_packed_bytes covers them).  From
+ * then until the next dmme_unet_pack_params of that buffer, dmme_unet_forward_nograd, dmme_chain_step and dmme_unet_forward_profiled
+ * with that buffer run those blocks without a qkv conv or tensor (dmme_attention_block).  Without this call, or with another buffer,
+ * they run the unfolded walk.  A captured graph holds the walk it was captured with.  A backward-capable forward never folds. */
+DMME_API int dmme_unet_pack_folded(const dmme_plan* plan, void* packed, void* stream);
 
 /* ---- UNet forward: replaces UNet.forward (models/ddpm.py:281-316) -------------------
  * y = eps_theta(x, t).  x: (B, C, H, W), y: (B, dmme_unet_plan_out_channels(), H, W), fp32 NCHW.
@@ -730,6 +742,17 @@ DMME_API int dmme_attention(int dtype, const void* qkv, int N, int S, int C, voi
  * next GroupNorm is finished from.  16-bit dtypes, S = 256, C = 128 or 256, N >= 128; DMME_ERR_UNSUPPORTED otherwise. */
 DMME_API int dmme_attention_proj(int dtype, const void* qkv, int N, int S, int C, const void* w, const float* bias, const void* res,
                                  void* dst, void* ctx, float* gn_part, int gn_cg, void* stream);
+/* The whole block `res + proj(attention(qkv(norm(x))))` in one launch, without a qkv tensor (weights fixed over a sampling chain).
+ * dmme_attention_fold: wqkv [3C][C] / wp [C][C] 16-bit (packed 1x1 layout), bqkv [3C] / bp [C] fp32 -> M, wpv [C][C] 16-bit and
+ *   c, bias2 [C] fp32 as dmme_unet_pack_folded defines them (bk drops out of a softmax over the keys).
+ * dmme_attention_block: x, res, dst [N][S][C] 16-bit.  The norm comes as partials - parts [N][part_tiles][groups] {mean, M2} of
+ *   part_cnt elements each, gamma / beta [C], eps; scale / shift [N][C] (nullable) then receive its rows - or, parts NULL, as the rows
+ *   scale / shift themselves.  gn_part / gn_cg as dmme_attention_proj.  16-bit dtypes, S = 256, C = 128 or 256, any N >= 1. */
+DMME_API int dmme_attention_fold(int dtype, int C, const void* wqkv, const float* bqkv, const void* wp, const float* bp, void* M, float* c, void* wpv,
+                                 float* bias2, void* stream);
+DMME_API int dmme_attention_block(int dtype, const void* x, int N, int S, int C, const float* parts, int part_tiles, int part_cnt, int groups,
+                                  const float* gamma, const float* beta, float eps, float* scale, float* shift, const void* M, const float* c,
+                                  const void* wpv, const float* bias2, const void* res, void* dst, float* gn_part, int gn_cg, void* stream);
 
 /* multi-head self-attention exactly as the reference ships it (MultiHeadAttention.forward_attention,
  * models/iddpm.py:35-47): qkv [N][S][3C]; head h of image n reads channels [h*3d, (h+1)*3d) as (q | k | v), d = C/heads;
