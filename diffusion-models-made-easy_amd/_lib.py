@@ -22,6 +22,8 @@ CHAIN_DPMPP, CHAIN_DPMPP_CFG = 8, 9  # DPM-Solver++(2M): tables of 8 floats per 
 CHAIN_REPAINT = 10  # RePaint / SDEdit: tables of 8 floats per index, the known image and its mask, three normal streams per step
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2  # what the network predicts (include/dmme_hip.h: DMME_PRED_*)
 PREDICTIONS = {"eps": PRED_EPS, "x0": PRED_X0, "v": PRED_V}
+THRESHOLD_NONE, THRESHOLD_STATIC, THRESHOLD_DYNAMIC = 0, 1, 2  # x0 thresholding in front of the update (include/dmme_hip.h: DMME_THRESHOLD_*)
+THRESHOLDS = {"none": THRESHOLD_NONE, "static": THRESHOLD_STATIC, "dynamic": THRESHOLD_DYNAMIC}
 ARCH_DDPM, ARCH_IDDPM, ARCH_CLASSIFIER, ARCH_DDPM_COND = 0, 1, 2, 3
 DTYPES = {"fp32": F32, "float32": F32, "32": F32, "bf16": BF16, "bfloat16": BF16, "16": BF16, "bf16-mixed": BF16, "16-mixed": BF16,
           "bf16x3": BF16X3, "fp16": F16, "float16": F16, "half": F16, "fp16r32": F16R32}
@@ -153,6 +155,10 @@ PROTOTYPES = {
     "dmme_mse_loss": (_i, [_vp, _vp, _i64, _vp, _vp, _f, _vp, _vp]),
     "dmme_pred_to_eps": (_i, [_i, _vp, _vp, _vp, _i, _vp, _i, _i, _i64, _vp]),
     "dmme_unet_plan_set_prediction": (_i, [_vp, _i, _vp, _i]),
+    "dmme_x0_threshold": (_i, [_i, _vp, _vp, _vp, _i, _vp, _i, _i, _i64, _i, _i, _f, _i, _f, _vp, _vp]),
+    "dmme_x0_threshold_scratch_bytes": (_i64, [_i, _i64]),
+    "dmme_x0_threshold_lds_capacity": (_i, []),
+    "dmme_unet_plan_set_threshold": (_i, [_vp, _i, _vp, _i, _i, _f, _vp]),
     "dmme_q_sample_pred": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "dmme_mse_loss_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _f, _vp, _vp]),
     "dmme_image_batch": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -73,6 +73,7 @@ class GenerateImage:
         module's diffusion process: its own chain (a DDIM module: its S steps), frames spread over it as the reference spreads them over
         `timesteps`.  For a LitDDPM with `timesteps` = T this equals `make_history(generate_img(pl_module))` under the same seed.
         out_kind 0: float32 in [0, 1]; 1: uint8.  `y`: labels for a class-conditional module (default: the null label).
+        The chain is the process's own, with its x0 thresholding (`threshold=` / `set_threshold`) as it is set.
         The canvas belongs to the callback: the next call overwrites it."""
         dm = pl_module.diffusion_model
         was_training = pl_module.training

@@ -451,6 +451,11 @@ int launch_q_sample(const float* x0, const float* z, const float* sqrt_abar, con
 // prediction.hip: an x0 / v network's output into an eps prediction, in place (dmme_pred_to_eps)
 int launch_pred_to_eps(int pred, float* model_out, const float* x, const float* ab, int T, const int64_t* t, int t_len, int B, int64_t chw,
                        hipStream_t s);
+// threshold.hip: the eps prediction rewritten so that the x0 it implies is clipped (dmme_x0_threshold); sg_coef / sg_state: a chain's
+// guidance scale, read on the device at the loop state's index (two halves), else sg
+int launch_x0_threshold(int mode, float* out, const float* x, const float* table, int T, const int64_t* t, int t_len, int B, int64_t chw, int planes,
+                        int halves, float sg, const float* sg_coef, int sg_row, int sg_col, const int64_t* sg_state, int k, float frac, void* scratch,
+                        hipStream_t s);
 int slerp_parts(int64_t chw);  // blocks per image of the first launch of launch_slerp: its scratch holds 3 * B * slerp_parts(chw) floats
 int launch_slerp(const float* xa, const float* xb, const float* w, int n, int B, int64_t chw, float* out, float* scratch, hipStream_t s);
 int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t seed, uint64_t offset, hipStream_t s);
@@ -460,6 +465,8 @@ int launch_chain_set(void* state, int64_t i, const int64_t* t_table, uint64_t se
 constexpr bool kind_known(int k) { return k >= DMME_CHAIN_DDPM && k <= DMME_CHAIN_REPAINT; }
 // x and the network output hold two halves (conditional, unconditional), mixed by s = row[kind_scol]; sizes are those of ONE half
 constexpr bool kind_cfg(int k) { return k == DMME_CHAIN_DDPM_CFG || k == DMME_CHAIN_GDDIM_CFG || k == DMME_CHAIN_DPMPP_CFG; }
+// the mixed prediction e^ = e_u + s (e_c - e_u), three separately rounded operations: the update's, and the thresholding stage's in front of it
+__device__ __forceinline__ float cfg_mix(float e_c, float e_u, float s) { return __fadd_rn(e_u, __fmul_rn(s, __fsub_rn(e_c, e_u))); }
 // the element arithmetic: sampler_update<kind_base> of a kind in [DDPM, GDDIM], or dpmpp_update
 constexpr int kind_base(int k) {
     return k == DMME_CHAIN_DDPM_CFG ? DMME_CHAIN_DDPM : k == DMME_CHAIN_GDDIM_CFG ? DMME_CHAIN_GDDIM : k == DMME_CHAIN_DPMPP_CFG ? DMME_CHAIN_DPMPP : k;

@@ -286,7 +286,7 @@ __device__ __forceinline__ void update_quad(const SamplerOperands& o, int64_t q,
         const float4 uv = load4(o.out + o.n4 * 4 + b);
         const float* us = reinterpret_cast<const float*>(&uv);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(r.c[kind_scol(KIND)], __fsub_rn(es[j], us[j])));
+        for (int j = 0; j < 4; ++j) es[j] = cfg_mix(es[j], us[j], r.c[kind_scol(KIND)]);
     }
     if constexpr (kind_hist(KIND)) {
         const DpmppRow d = {r.c[0], r.c[1], r.c[2], r.c[3], r.c[4], r.c[5], r.c[6]};

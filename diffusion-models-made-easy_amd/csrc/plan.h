@@ -280,6 +280,13 @@ struct dmme_plan {
     // launch dmme_pred_to_eps over the plan's batch right behind the forward, with this device table [pred_T + 1][2] (the caller's)
     int pred = DMME_PRED_EPS, pred_T = 0;
     const float* pred_ab = nullptr;
+    // x0 thresholding (dmme_unet_plan_set_threshold; host-only): DMME_THRESHOLD_STATIC / DMME_THRESHOLD_DYNAMIC make the capturable chain
+    // steps launch dmme_x0_threshold behind the adapter, with this device table [thr_T + 1][4], the order statistic (thr_k, thr_frac) and
+    // the streaming form's scratch (all the caller's)
+    int thr_mode = DMME_THRESHOLD_NONE, thr_T = 0, thr_k = 0;
+    float thr_frac = 0.f;
+    const float* thr_table = nullptr;
+    void* thr_scratch = nullptr;
 };
 
 namespace dmme {

@@ -1806,6 +1806,13 @@ static int chain_step_common(const char* what, const dmme_plan* plan, const void
         if (int rc = launch_pred_to_eps(plan->pred, model_out, x, plan->pred_ab, plan->pred_T, t_dev, 1, plan->B,
                                         (int64_t)plan->cfg.in_channels * plan->H * plan->W, (hipStream_t)stream))
             return rc;
+    // x0 thresholding: the eps plane the update will read (a classifier-free kind: the update's own mix of the two halves, its scale read
+    // from the step's table row on the device) rewritten so that the x0 it implies is clipped; off launches nothing
+    if (plan->thr_mode != DMME_THRESHOLD_NONE)
+        if (int rc = launch_x0_threshold(plan->thr_mode, model_out, x, plan->thr_table, plan->thr_T, t_dev, 1, cfg ? plan->B / 2 : plan->B,
+                                         (int64_t)plan->cfg.in_channels * plan->H * plan->W, planes, cfg ? 2 : 1, 1.0f, cfg ? step_coef : nullptr, kind_row(kind),
+                                         kind_scol(kind), (const int64_t*)state, plan->thr_k, plan->thr_frac, plan->thr_scratch, (hipStream_t)stream))
+            return rc;
     if (between)
         if (int rc = between()) return rc;
     return launch_sampler_chain(what, kind, sampler_operands(x, model_out, nullptr, cfg ? plan->B / 2 : plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,

@@ -170,8 +170,19 @@ class ChainRunner(ChainTables):
         self.n_steps = n
         self.pred = getattr(process, "_pred", _lib.PRED_EPS)
         self.pred_ab = process._pred_table(x.device).clone() if self.pred != _lib.PRED_EPS else None  # (the runner's own: see _set_prediction)
+        # x0 thresholding: the process's setting when the runner is built (`_runner_key` holds it), its table and the streaming form's
+        # scratch held by this runner because the captured graph holds their addresses
+        self.thr = getattr(process, "_thr", _lib.THRESHOLD_NONE)
+        self.thr_tab, self.thr_scratch, self.thr_k, self.thr_frac = None, None, 0, 0.0
+        if self.thr != _lib.THRESHOLD_NONE:
+            from .ddpm import threshold_rank
+
+            self.thr_tab = process._thr_table(x.device).clone()
+            if self.thr == _lib.THRESHOLD_DYNAMIC:
+                self.thr_k, self.thr_frac = threshold_rank(process.threshold_percentile, x[0].numel())
+                self.thr_scratch = torch.empty(int(_lib.lib().dmme_x0_threshold_scratch_bytes(B, x[0].numel())) // 4, dtype=torch.int32, device=x.device)
         super().__init__(rows, ttab, x.device)
-        self.out = torch.empty((B, model.out_channels, H, W), dtype=torch.float32, device=x.device)
+        self.out =torch.empty((B, model.out_channels, H, W), dtype=torch.float32, device=x.device)
         self.quads = x.numel() // 4
         self.noise_numel = x.numel()  # normals one step consumes (a runner whose buffer holds more than the images it draws for says so)
         self.use_graph = use_graph
@@ -186,9 +197,21 @@ class ChainRunner(ChainTables):
         plan = self.plan if plan is None else plan
         _lib.check(_lib.lib().dmme_unet_plan_set_prediction(plan.h, self.pred, _lib.ptr(self.pred_ab), self.process.timesteps), "dmme_unet_plan_set_prediction")
 
+    def no_threshold(self):
+        """this runner's chain never clips (GeneralizedDDIM's encoding direction: clipping would break the inversion)"""
+        self.thr = _lib.THRESHOLD_NONE
+        return self
+
+    def _set_threshold(self, plan=None):
+        """tell the plan how its eps prediction is thresholded, in front of every chain-step call, for the reason `_set_prediction` is"""
+        plan = self.plan if plan is None else plan
+        _lib.check(_lib.lib().dmme_unet_plan_set_threshold(plan.h, self.thr, _lib.ptr(self.thr_tab), self.process.timesteps, self.thr_k, self.thr_frac,
+                                                           _lib.ptr(self.thr_scratch)), "dmme_unet_plan_set_threshold")
+
     def _launch(self, packed):
         """the launches of one step, eager or under capture; a subclass supplies `_call`, the entry point of its kind"""
         self._set_prediction()
+        self._set_threshold()
         self._call(packed)
         self.plan.overwritten()
 

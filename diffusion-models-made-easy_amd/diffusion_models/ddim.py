@@ -23,8 +23,9 @@ class DDIM(DDPM):
     tau: Tensor
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", *, prediction: str = "eps",
-                 loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)  # start/end are not forwarded, as in the reference (:39)
+                 loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold,
+                         threshold_percentile=threshold_percentile)  # start/end are not forwarded, as in the reference (:39)
         self.sub_timesteps = sub_timesteps
         kind = tau_schedule.lower()
         if kind == "linear":
@@ -120,8 +121,9 @@ class GeneralizedDDIM(DDIM):
     _chain_kind = _lib.CHAIN_GDDIM
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", eta: float = 0.0, *,
-                 prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold,
+                         threshold_percentile=threshold_percentile)
         eta = float(eta)
         if not 0.0 <= eta <= 1.0:
             raise ValueError(f"eta must lie in [0, 1], got {eta}")
@@ -184,7 +186,8 @@ class GeneralizedDDIM(DDIM):
 
     def _encode_runner(self, shape, dev) -> Optional[ChainRunner]:
         """the encoding direction's runner: one per shape, on a buffer of its own (slot `_runner` is the decoding direction's)"""
-        return self._buffered_runner("_enc_runner", shape, dev, spec=lambda: (_lib.CHAIN_GDDIM, self._encode_tables()), buf="_enc_buf")
+        r = self._buffered_runner("_enc_runner", shape, dev, spec=lambda: (_lib.CHAIN_GDDIM, self._encode_tables()), buf="_enc_buf")
+        return r if r is None else r.no_threshold()  # (encoding never thresholds: a clipped step has no inverse)
 
     @torch.no_grad()
     def decode(self, x: Tensor, start: Optional[int] = None, history=None) -> Tensor:
@@ -201,7 +204,7 @@ class GeneralizedDDIM(DDIM):
         x = x0.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
         if upto == 0:
             return x
-        step = lambda j: self._gddim_update(x, self._eps(x, self._enc_t_tensor(j, x.device)), self._enc_rows[j])
+        step = lambda j: self._gddim_update(x, self._eps(x, self._enc_t_tensor(j, x.device), _threshold=False), self._enc_rows[j])
         return self._run_chain(self._encode_runner(x.shape, x.device), x, S, upto, step)
 
     @torch.no_grad()

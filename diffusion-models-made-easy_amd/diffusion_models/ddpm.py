@@ -50,6 +50,43 @@ def prediction_table(alpha_bar, prediction: str) -> np.ndarray:
     return out
 
 
+def threshold_table(alpha_bar) -> np.ndarray:
+    """float64 [T+1][4] = (A_t, B_t, C_t, D_t) of x0 thresholding (include/dmme_hip.h: dmme_x0_threshold): x0 = A x_t - B eps and
+    eps = C x_t - D x0, so A = 1/sqrt(abar), B = sqrt(1-abar)/sqrt(abar), C = 1/sqrt(1-abar), D = sqrt(abar)/sqrt(1-abar); NaN where
+    abar = 1 (index 0: never stepped from, and a misuse should be loud), as in `prediction_table`."""
+    ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
+    out = np.empty((ab.size, 4), dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sa, sd = np.sqrt(ab), np.sqrt(1 - ab)
+        out[:, 0], out[:, 1], out[:, 2], out[:, 3] = 1.0 / sa, sd / sa, 1.0 / sd, sa / sd
+    out[ab >= 1.0] = np.nan
+    return out
+
+
+def threshold_rank(percentile: float, n: int) -> Tuple[int, float]:
+    """(k, frac) of the `percentile`-quantile of n values with linear interpolation, q = a_k + frac (a_{k+1} - a_k) over the ascending
+    order statistics: k = floor(p (n - 1)) and the remainder, formed in float64; frac is what float32 holds of it.  p = 1: (n - 1, 0)."""
+    p, n = float(percentile), int(n)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"threshold_percentile = {percentile!r}; a number in [0, 1]")
+    if n < 1:
+        raise ValueError(f"threshold_rank: {n} values")
+    pos = p * (n - 1)
+    k = min(int(np.floor(pos)), n - 1)
+    frac = float(np.float32(pos - k))
+    if k == n - 1:
+        frac = 0.0
+    return k, frac
+
+
+def _check_threshold(mode, percentile) -> Tuple[str, float]:
+    if mode not in _lib.THRESHOLDS:
+        raise ValueError(f"threshold = {mode!r}; use one of {tuple(_lib.THRESHOLDS)}")
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, float, np.floating, np.integer)) or not 0.0 <= float(percentile) <= 1.0:
+        raise ValueError(f"threshold_percentile = {percentile!r}; a number in [0, 1]")
+    return mode, float(percentile)
+
+
 def loss_weight_table(alpha_bar, prediction: str, loss_weight: str, snr_gamma: float = 5.0) -> np.ndarray:
     """float64 [T+1] weights of the per-timestep MSE.  "min-snr" (Hang et al. 2023) with snr = abar/(1-abar): min(snr, gamma)/snr for an
     eps network, min(snr, gamma) for x0, min(snr, gamma)/(snr + 1) for v - the same weight min(snr, gamma) on the x0 error each
@@ -78,14 +115,18 @@ class DDPM(nn.Module):
     alpha_bar: Tensor
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, start: float = 0.0001, end: float = 0.02, *, prediction: str = "eps",
-                 loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
+                 loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
         """`prediction`: what the network's output is - "eps" (the noise), "x0", or "v" = sqrt(abar_t) eps - sqrt(1 - abar_t) x0 (Salimans
         & Ho 2022).  Training regresses on that target; sampling turns the output into an eps prediction with one elementwise launch
         behind the network (dmme_pred_to_eps) and runs today's updates on it.  `loss_weight`: "uniform" or "min-snr" (Hang et al.
-        2023, clipped at `snr_gamma`)."""
+        2023, clipped at `snr_gamma`).  `threshold`: sampling clips the x0 each eps prediction implies, in front of the update
+        (dmme_x0_threshold) - "static" to [-1, 1] (the published samplers' clip_denoised), "dynamic" to the image's
+        `threshold_percentile` quantile of |x0| where that exceeds 1, then rescaled (Saharia et al. 2022); see `set_threshold`."""
         super().__init__()
         self.model = model
         self.timesteps = timesteps
+        self.threshold, self.threshold_percentile = _check_threshold(threshold, threshold_percentile)
+        self._thr = _lib.THRESHOLDS[self.threshold]
         if prediction not in _lib.PREDICTIONS:
             raise ValueError(f"prediction = {prediction!r}; use one of {tuple(_lib.PREDICTIONS)}")
         if loss_weight not in LOSS_WEIGHTS:
@@ -121,6 +162,49 @@ class DDPM(nn.Module):
         if self.loss_weight != "uniform":
             w = loss_weight_table(ab64, self.prediction, self.loss_weight, self.snr_gamma).astype(np.float32)
             self.register_buffer("_loss_w", torch.from_numpy(w).contiguous(), persistent=False)
+        self._thr_setup()
+
+    def _thr_setup(self) -> None:
+        """the fp32 device table of x0 thresholding ([T+1][4]), folded in float64 from alpha_bar and rounded once; a process that does
+        not threshold registers none"""
+        if self._thr != _lib.THRESHOLD_NONE:
+            ab64 = self.alpha_bar.detach().reshape(-1).to(torch.float64).cpu().numpy()
+            tab = torch.from_numpy(threshold_table(ab64).astype(np.float32)).reshape(-1).contiguous()
+            self.register_buffer("_thr_tab", tab.to(self.alpha_bar.device), persistent=False)
+
+    def set_threshold(self, mode: str, percentile: Optional[float] = None):
+        """another x0 thresholding for the sampling calls that follow: "none", "static" or "dynamic" (at `percentile`, default: the
+        process's).  A cached runner is keyed by it: the next chain builds a runner and a graph with the new setting."""
+        self.threshold, self.threshold_percentile = _check_threshold(mode, self.threshold_percentile if percentile is None else percentile)
+        self._thr = _lib.THRESHOLDS[self.threshold]
+        self._thr_setup()
+        return self
+
+    def _thr_table(self, device) -> Tensor:
+        """the thresholding table on `device` (the buffer itself where the process lives there)"""
+        tab = self._thr_tab
+        return tab if tab.device == torch.device(device) else tab.to(device)
+
+    def _threshold_eps(self, e: Tensor, x: Tensor, t: Tensor, halves: int = 1, guidance_scale: float = 1.0) -> Tensor:
+        """the thresholding stage in place on the eps prediction `e` (a tensor this process owns): one plane per image, IDDPM's two, or
+        (halves = 2) the two halves of a classifier-free batch, mixed at `guidance_scale`; `x`: the images the network saw (B of them)"""
+        xx = x.detach().to(device=e.device, dtype=torch.float32).contiguous()
+        tt = t.detach().reshape(-1).to(device=e.device, dtype=torch.int64).contiguous()
+        B, chw = xx.shape[0], xx[0].numel()
+        planes = e[0].numel() // chw
+        if e.shape[0] != B * halves or planes * chw != e[0].numel() or planes not in (1, 2) or tt.numel() not in (1, B):
+            raise ValueError(f"threshold = {self.threshold!r}: a prediction of shape {tuple(e.shape)} for {halves} x images {tuple(xx.shape)} at {tt.numel()} timesteps")
+        k, frac = threshold_rank(self.threshold_percentile, chw) if self._thr == _lib.THRESHOLD_DYNAMIC else (0, 0.0)
+        lib = _lib.lib()
+        scratch = None
+        if self._thr == _lib.THRESHOLD_DYNAMIC:
+            scratch = getattr(self, "_thr_scratch", None)
+            need = int(lib.dmme_x0_threshold_scratch_bytes(B, chw)) // 4
+            if scratch is None or scratch.device != e.device or scratch.numel() < need:
+                scratch = self._thr_scratch = torch.empty(need, dtype=torch.int32, device=e.device)
+        _lib.check(lib.dmme_x0_threshold(self._thr, _lib.ptr(e), _lib.ptr(xx), _lib.ptr(self._thr_table(e.device)), self.timesteps, _lib.ptr(tt), tt.numel(), B, chw,
+                                         planes, halves, float(guidance_scale), k, frac, _lib.ptr(scratch), _lib.stream_ptr()), "dmme_x0_threshold")
+        return e
 
     def _pred_table(self, device) -> Tensor:
         """the adapter's table on `device` (the buffer itself where the process lives there)"""
@@ -184,8 +268,8 @@ class DDPM(nn.Module):
         return hasattr(model, "_plan_for") and not model.training and x.is_cuda and x.dim() == 4 and x[0].numel() % 4 == 0 and x.dtype == torch.float32 and x.is_contiguous()
 
     def _runner_key(self, x: Tensor, use_graph: bool):
-        """what a cached runner is good for: this buffer, this network (by identity) in this precision"""
-        return (x.data_ptr(), tuple(x.shape), self.model, self.model._dtype, use_graph)
+        """what a cached runner is good for: this buffer, this network (by identity) in this precision, this x0 thresholding"""
+        return (x.data_ptr(), tuple(x.shape), self.model, self.model._dtype, use_graph, (self.threshold, self.threshold_percentile))
 
     def _buffered_runner(self, slot: str, shape, device, spec=None, buf: str = "_gen_buf") -> Optional[ChainRunner]:
         """the runner in `slot`, bound to an internal image buffer (attribute `buf`) of this shape on this device; both outlive the call:
@@ -270,15 +354,19 @@ class DDPM(nn.Module):
         return self._loss(self.model(x_t, t), target, t)
 
     # ------------------------------------------------------------------ sampling
-    def _eps(self, x: Tensor, t: Tensor, *labels, **kw) -> Tensor:
+    def _eps(self, x: Tensor, t: Tensor, *labels, _threshold: bool = True, **kw) -> Tensor:
         """the network's noise prediction at (x, t): its output for an eps network; for an x0 / v network one dmme_pred_to_eps launch on
-        the output (eps = a_t out + b_t x).  Every sampling call of the network goes through here; `forward` returns the raw output."""
+        the output (eps = a_t out + b_t x); with `threshold` set, the thresholding stage behind that (`_threshold=False`: a caller that
+        must not clip, or applies the stage itself).  Every sampling call of the network goes through here; `forward` returns the raw output."""
         out = self.model(x, t, *labels, **kw)
-        if self._pred == _lib.PRED_EPS:
+        thr = _threshold and self._thr != _lib.THRESHOLD_NONE
+        if self._pred == _lib.PRED_EPS and not thr:
             return out
         e = out.detach().to(torch.float32).contiguous()
         if out.requires_grad and e.data_ptr() == out.data_ptr():
             e = e.clone()  # (never in place on a tensor autograd may still read)
+        if self._pred == _lib.PRED_EPS:
+            return self._threshold_eps(e, x, t)
         xx = x.detach().to(device=e.device, dtype=torch.float32).contiguous()
         tt = t.detach().reshape(-1).to(device=e.device, dtype=torch.int64).contiguous()
         B = e.shape[0]
@@ -286,7 +374,7 @@ class DDPM(nn.Module):
             raise ValueError(f"prediction = {self.prediction!r}: a network output of shape {tuple(e.shape)} for images {tuple(xx.shape)} at {tt.numel()} timesteps")
         _lib.check(_lib.lib().dmme_pred_to_eps(self._pred, _lib.ptr(e), _lib.ptr(xx), _lib.ptr(self._pred_table(e.device)), self.timesteps, _lib.ptr(tt), tt.numel(), B,
                                                e[0].numel(), _lib.stream_ptr()), "dmme_pred_to_eps")
-        return e
+        return self._threshold_eps(e, xx, tt) if thr else e
 
     def _reverse_update(self, x_t: Tensor, eps: Tensor, t: int, noise: Optional[Tensor]) -> Tensor:
         if noise is None:

@@ -106,8 +106,10 @@ def _row_arg(row):
 
 
 def _from_process(cls, p: DDPM, **kw):
-    """the sampler over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one) and prediction"""
+    """the sampler over `p`'s network, noise schedule (an IDDPM's cosine schedule, for one), prediction and x0 thresholding"""
     kw.setdefault("prediction", getattr(p, "prediction", "eps"))
+    kw.setdefault("threshold", getattr(p, "threshold", "none"))
+    kw.setdefault("threshold_percentile", getattr(p, "threshold_percentile", 0.995))
     return cls(p.model, p.timesteps, alpha_bar=p.alpha_bar.detach().reshape(-1).cpu(), **kw)
 
 
@@ -124,8 +126,8 @@ class DPMSolverPP(DDIM):
     _runner_class = DPMChainRunner
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 20, tau_schedule: str = "logsnr", order: int = 2, clip_x0: bool = False,
-                 alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        DDPM.__init__(self, model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)  # (DDIM's constructor knows two schedules and the linear beta only)
+                 alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        DDPM.__init__(self, model, timesteps, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)  # (DDIM's constructor knows two schedules and the linear beta only)
         kind = str(tau_schedule).lower()
         if kind not in TAU_SCHEDULES:
             raise ValueError(f"tau_schedule = {tau_schedule!r}; use one of {TAU_SCHEDULES}")

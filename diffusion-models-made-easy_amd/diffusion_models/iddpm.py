@@ -192,7 +192,7 @@ class IDDPM(DDPM):
         dev = self.beta.device
         x_t = gaussian(img_size, device=dev)
         runner = self._buffered_runner(f"_runner_k{K}", img_size, dev, spec=lambda: (_lib.CHAIN_IDDPM, (K, rows, ttab)))  # (on the full chain's buffer)
-        return self._run_chain(runner, x_t, K, K, lambda k: self._reverse_update(x_t, self.model(x_t, self.timestep_tensor(ttab[k], dev)), ttab[k], None, rows[k]), history)
+        return self._run_chain(runner, x_t, K, K, lambda k: self._reverse_update(x_t, self._eps(x_t, self.timestep_tensor(ttab[k], dev)), ttab[k], None, rows[k]), history)
 
     # ------------------------------------------------------------------ evaluation
     @torch.no_grad()

@@ -134,8 +134,8 @@ class RePaint(DDPM):
     _runner_class = PaintChainRunner
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 250, jump_length: int = 10, resamples: int = 10, start: float = 0.0001,
-                 end: float = 0.02, alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 end: float = 0.02, alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         for name, v in (("jump_length", jump_length), ("resamples", resamples)):
             if isinstance(v, bool) or int(v) != v or v < 1:
                 raise ValueError(f"{name} = {v!r}; an integer of at least 1")

@@ -247,8 +247,8 @@ class ClassifierGuidedDDPM(_Guided, DDPM):
     _chain_kind = _lib.CHAIN_DDPM_GUIDED
 
     def __init__(self, model: nn.Module, classifier: EncoderClassifier, timesteps: int = 1000, guidance_scale: float = 1.0, start: float = 0.0001,
-                 end: float = 0.02, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 end: float = 0.02, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         self.classifier = classifier
         self.guidance_scale = float(guidance_scale)
 
@@ -271,8 +271,8 @@ class ClassifierGuidedDDIM(_Guided, DDIM):
     _chain_kind = _lib.CHAIN_DDIM_GUIDED
 
     def __init__(self, model: nn.Module, classifier: EncoderClassifier, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic",
-                 guidance_scale: float = 1.0, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 guidance_scale: float = 1.0, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         self.classifier = classifier
         self.guidance_scale = float(guidance_scale)
 

@@ -89,6 +89,12 @@ class CFGChainRunner(ChainRunner):
                                          self.images, self.x[0].numel(), _lib.stream_ptr()),
                     "dmme_pred_to_eps",
                 )
+            if self.thr != _lib.THRESHOLD_NONE:  # (... and so is the thresholding stage's)
+                _lib.check(
+                    lib.dmme_x0_threshold(self.thr, _lib.ptr(self.out), _lib.ptr(self.x), _lib.ptr(self.thr_tab), self.process.timesteps, _lib.ptr(t_dev), 1,
+                                          self.images, self.x[0].numel(), 1, 1, 1.0, self.thr_k, self.thr_frac, _lib.ptr(self.thr_scratch), _lib.stream_ptr()),
+                    "dmme_x0_threshold",
+                )
             if self.dpmpp:
                 _lib.check(
                     lib.dmme_chain_update_dpmpp(_lib.ptr(self.x), _lib.ptr(self.out), _lib.ptr(self.hist), _lib.ptr(self.coef), _lib.ptr(self.ttab), _lib.ptr(self.state),
@@ -184,8 +190,11 @@ class _ClassifierFree:
         else:
             x = torch.cat([x, x], dim=0)
             labels = torch.cat([labels, torch.full_like(labels, model.null_label)])
+        batched = self.guidance_scale != 1.0
         with torch.no_grad():
-            eps = self._eps(x, t_dev, labels, check_labels=False).to(torch.float32).contiguous()
+            eps = self._eps(x, t_dev, labels, check_labels=False, _threshold=not batched).to(torch.float32).contiguous()
+            if batched and self._thr != _lib.THRESHOLD_NONE:  # (both halves: the x0 of the mixed prediction is what gets clipped)
+                eps = self._threshold_eps(eps, x[:B], t_dev, halves=2, guidance_scale=self.guidance_scale)
         return x, eps, B
 
     def _cfg_update(self, x: Tensor, eps: Tensor, B: int, row, add_noise: bool, z: Optional[Tensor]) -> Tensor:
@@ -233,8 +242,8 @@ class ClassifierFreeDDPM(_ClassifierFree, DDPM):
     _chain_kind = _lib.CHAIN_DDPM_CFG
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, guidance_scale: float = 1.0, p_uncond: float = 0.1, start: float = 0.0001, end: float = 0.02, *,
-                 prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         self._init_cfg(guidance_scale, p_uncond)
 
     def _chain_tables(self):
@@ -259,8 +268,8 @@ class ClassifierFreeDDIM(_ClassifierFree, GeneralizedDDIM):
     _chain_kind = _lib.CHAIN_GDDIM_CFG
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 50, tau_schedule: str = "quadratic", eta: float = 0.0,
-                 guidance_scale: float = 1.0, p_uncond: float = 0.1, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule, eta, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 guidance_scale: float = 1.0, p_uncond: float = 0.1, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, eta, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         self._init_cfg(guidance_scale, p_uncond)
 
     def _chain_tables(self):
@@ -291,8 +300,8 @@ class ClassifierFreeDPMSolver(_ClassifierFree, DPMSolverPP):
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 20, tau_schedule: str = "logsnr", order: int = 2, clip_x0: bool = False,
                  alpha_bar: Optional[Tensor] = None, guidance_scale: float = 1.0, p_uncond: float = 0.1, *, prediction: str = "eps", loss_weight: str = "uniform",
-                 snr_gamma: float = 5.0) -> None:
-        super().__init__(model, timesteps, sub_timesteps, tau_schedule, order, clip_x0, alpha_bar, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma)
+                 snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
+        super().__init__(model, timesteps, sub_timesteps, tau_schedule, order, clip_x0, alpha_bar, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         self._init_cfg(guidance_scale, p_uncond)
 
     def _scaled_rows(self):

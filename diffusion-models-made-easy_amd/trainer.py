@@ -24,6 +24,7 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
+  python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3 --guidance-scale 2.5 --threshold dynamic   (x0 thresholding in front of the update: none | static | dynamic [--threshold-percentile P]; any sampler)
   python -m dmme_amd.trainer fit    --config configs/vpred/cifar10.yaml   (a v-prediction network under min-SNR weights; --prediction / --loss-weight / --snr-gamma override any YAML)
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml --preview-dir DIR --preview-every N   (a history grid DIR/step_<n>.png every N optimiser steps)
 """
@@ -265,6 +266,19 @@ def _check_solver_args(args) -> None:
         raise SystemExit("--sample-steps must be at least 1")
 
 
+def _check_threshold_args(args) -> None:
+    """what goes with --threshold and what does not; exits with a message (before anything touches the GPU)"""
+    if args.threshold is None and args.threshold_percentile is None:
+        return
+    if args.command != "sample":
+        raise SystemExit("--threshold / --threshold-percentile belong to `sample`: x0 thresholding is a sampler's, training does not clip")
+    if args.threshold_percentile is not None:
+        if args.threshold != "dynamic":
+            raise SystemExit("--threshold-percentile belongs to --threshold dynamic")
+        if not 0.0 <= args.threshold_percentile <= 1.0:
+            raise SystemExit(f"--threshold-percentile {args.threshold_percentile} outside [0, 1]")
+
+
 def _dpm_solver(module, args):
     """DPM-Solver++(2M) over the network and the noise schedule of the process the YAML built (classifier-free where that one is)"""
     from .diffusion_models import DPMSolverPP
@@ -383,8 +397,13 @@ def main(argv=None):
     ap.add_argument("--prediction", default=None, choices=["eps", "x0", "v"], help="what the network predicts, over the YAML's `prediction` (default eps)")
     ap.add_argument("--loss-weight", default=None, choices=["uniform", "min-snr"], help="fit: the loss's weight per timestep, over the YAML's `loss_weight`")
     ap.add_argument("--snr-gamma", type=float, default=None, help="fit --loss-weight min-snr: the SNR the weight is clipped at (default 5)")
+    ap.add_argument("--threshold", default=None, choices=["none", "static", "dynamic"],
+                    help="sample, every sampler: clip the x0 each noise prediction implies, in front of the update - static: to [-1, 1] (clip_denoised); "
+                         "dynamic: to the image's --threshold-percentile quantile of |x0| where above 1, rescaled (wanted with --guidance-scale above 1)")
+    ap.add_argument("--threshold-percentile", type=float, default=None, help="sample --threshold dynamic: the quantile, in [0, 1] (default 0.995)")
     args = ap.parse_args(argv)
     _check_solver_args(args)
+    _check_threshold_args(args)
     _check_paint_args(args)
     if args.save is not None and args.command != "sample":
         raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
@@ -451,6 +470,8 @@ def main(argv=None):
             module.diffusion_model = _paint_process(module, args).cuda()
         module.eval()
         dm = module.diffusion_model
+        if args.threshold is not None:
+            dm.set_threshold(args.threshold, args.threshold_percentile)  # (whatever process the sampler flags built: every kind reads one eps buffer)
         t0 = time.perf_counter()
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)

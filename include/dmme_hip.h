@@ -430,6 +430,50 @@ DMME_API int dmme_pred_to_eps(int pred, float* model_out, const float* x, const 
  * with more than one output plane (an IDDPM network's (eps, v)) or on a classifier; DMME_ERR_INVALID: C*H*W no multiple of 4. */
 DMME_API int dmme_unet_plan_set_prediction(dmme_plan* plan, int pred, const float* ab, int T);
 
+/* ---- x0 thresholding in front of every sampler update (csrc/threshold.hip) ---------------------------------------------
+ * Every update runs on an eps prediction; the image it implies is x0 = (x_t - sqrt(1 - abar_t) eps) / sqrt(abar_t).  This stage
+ * rewrites the eps prediction in place, behind the x0 / v adapter and in front of the update, so that the implied x0 is clipped: the
+ * static clip to [-1, 1] (clip_denoised of the published DDPM / IDDPM / ADM samplers) or the dynamic percentile clip of Saharia et al.
+ * 2022 (section 2.3).  The update kinds, their tables and their entry points are untouched; with the mode off nothing is launched. */
+enum { DMME_THRESHOLD_NONE = 0, DMME_THRESHOLD_STATIC = 1, DMME_THRESHOLD_DYNAMIC = 2 };
+
+/* Per image b at timestep t_b, with table: device fp32 [T+1][4] = {A, B, C, D}_t folded by the host in float64 from alpha_bar and rounded
+ * once, A = 1/sqrt(abar), B = sqrt(1 - abar)/sqrt(abar), C = 1/sqrt(1 - abar), D = sqrt(abar)/sqrt(1 - abar); row 0 (abar_0 = 1) is NaN.
+ * Every product, difference and quotient is rounded to fp32 on its own (no fma):
+ *   x0  = (A x) - (B e)                           e: the eps the update will use
+ *   s   = 1                                       static
+ *       = max(1, a_k + frac (a_{k+1} - a_k))      dynamic: a_j the j-th smallest (0-based) of the image's chw values |x0|, exact; the host
+ *                                                 passes k = floor(p (chw - 1)) and frac = fp32 of the remainder for the percentile p;
+ *                                                 a_{k+1} is not looked at where frac == 0 (p = 1: k = chw - 1, frac = 0)
+ *   an element with s == 1 and |x0| <= 1 is not stored to: a step that clips nothing leaves the prediction's bits alone
+ *   every other element:  e' = (C x) - (D (clamp(x0, -s, s) / s))
+ * Non-finite x0: dynamic mode writes NaN to the image's whole eps plane (there is no percentile to take); static mode, which reduces
+ * nothing, writes NaN to that element.  An image whose t lies outside 0..T reads the NaN row's fate without touching the table.
+ * model_out: [B][planes][chw] with planes 1, or 2 (an IDDPM network's (eps, v): only the eps plane is read and rewritten).  halves == 2
+ * (planes == 1): model_out holds 2B images, B conditional then B unconditional, and e is the update's own mix e_u + s_g (e_c - e_u)
+ * (three rounded operations, the same device function); e' goes to BOTH halves, so that the update's mix returns it exactly, and an
+ * untouched element stays as it is in both; x is read from its first B images.  halves == 1 ignores guidance_scale.
+ * t: int64 in DEVICE memory, t_len = 1 or B, as in dmme_pred_to_eps.  Any chw < 2^31; B <= 65535.
+ * Static mode is one elementwise launch (16-byte accesses where chw % 4 == 0 and both pointers are aligned).  Dynamic mode selects by
+ * radix (four 8-bit digits of the bit pattern of |x0|, integer atomics only: deterministic): one workgroup per image with the image in
+ * LDS where chw <= dmme_x0_threshold_lds_capacity() (one launch), else several workgroups per image and per-digit histograms in
+ * `scratch` (dmme_x0_threshold_scratch_bytes; seven launches, the first clears the scratch: it need not be zero on entry; no host
+ * synchronisation, capturable).  Both forms give the same bits.  scratch may be NULL where the LDS form runs.
+ * DMME_ERR_INVALID: mode not 1 or 2, a null table, (k, frac) that no percentile in [0, 1] gives, planes / halves as above. */
+DMME_API int dmme_x0_threshold(int mode, float* model_out, const float* x, const float* table, int T, const int64_t* t, int t_len, int B,
+                               int64_t chw, int planes, int halves, float guidance_scale, int k, float frac, void* scratch, void* stream);
+DMME_API int64_t dmme_x0_threshold_scratch_bytes(int B, int64_t chw);
+DMME_API int dmme_x0_threshold_lds_capacity(void); /* elements of one image the one-workgroup form holds */
+
+/* host-only state of a plan, like dmme_unet_plan_set_prediction: with a mode other than DMME_THRESHOLD_NONE every capturable step over
+ * the plan launches dmme_x0_threshold behind the adapter and in front of the classifier pass (guided kinds: where ADM's clip_denoised
+ * sits) and the update, at t = &state.t, over the plan's batch (a classifier-free kind: two halves of B = plan batch / 2, the guidance
+ * scale read on the device from the step's own table row, coef[row length * state.i + scale column]).  table, scratch stay the caller's
+ * and must outlive every launch and captured graph; set it in front of EVERY chain-step call (the plan is shared).  Mode 0 clears it
+ * and ignores the rest.  DMME_ERR_INVALID: a classifier plan, a null table, (k, frac) out of range for the plan's C*H*W, no scratch
+ * where the streaming form would run. */
+DMME_API int dmme_unet_plan_set_threshold(dmme_plan* plan, int mode, const float* table, int T, int k, float frac, void* scratch);
+
 /* dmme_q_sample with the regression target of a parameterisation.  x_t: dmme_q_sample's, the same bits.  target (optional):
  *   DMME_PRED_EPS  (x_t - mean)/std, what dmme_q_sample writes, the same bits
  *   DMME_PRED_X0   x0
