@@ -15,6 +15,7 @@ from .callbacks import GenerateImage  # noqa: F401
 from .data_modules import CIFAR10  # noqa: F401
 from .diffusion_models import DDPM, DDIM, IDDPM, GeneralizedDDIM, DPMSolverPP  # noqa: F401
 from .diffusion_models import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401
+from .diffusion_models import ILVR, LikeChainRunner, ilvr_rows, lowpass_matrix  # noqa: F401
 from .lit_modules import LitDDPM, LitDDIM, LitIDDPM, LitClassifierFreeDDPM  # noqa: F401
 from .models.ddpm import UNet  # noqa: F401
 from .models.cond import ConditionalUNet  # noqa: F401
@@ -24,4 +25,4 @@ from .guidance import ClassifierFreeDDPM, ClassifierFreeDDIM, ClassifierFreeDPMS
 
 __all__ = ["gaussian", "gaussian_like", "uniform_int", "pad", "denorm", "norm", "UNet", "DDPM", "DDIM", "LitDDPM", "LitDDIM", "IDDPM", "LitIDDPM", "CIFAR10", "GeneralizedDDIM",
            "ConditionalUNet", "ClassifierFreeDDPM", "ClassifierFreeDDIM", "LitClassifierFreeDDPM", "DPMSolverPP", "ClassifierFreeDPMSolver",
-           "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows", "make_history", "save_png", "HistoryRecorder", "history_ordinals", "GenerateImage"]
+           "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows", "ILVR", "LikeChainRunner", "ilvr_rows", "lowpass_matrix", "make_history", "save_png", "HistoryRecorder", "history_ordinals", "GenerateImage"]

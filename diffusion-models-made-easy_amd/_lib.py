@@ -20,6 +20,7 @@ CHAIN_DDPM, CHAIN_DDIM, CHAIN_IDDPM, CHAIN_DDPM_GUIDED, CHAIN_DDIM_GUIDED, CHAIN
 CHAIN_DDPM_CFG, CHAIN_GDDIM_CFG = 6, 7  # classifier-free guidance: both halves of a 2B batch mixed, then the DDPM / paper-form DDIM update
 CHAIN_DPMPP, CHAIN_DPMPP_CFG = 8, 9  # DPM-Solver++(2M): tables of 8 floats per index, a history buffer, entry points of their own
 CHAIN_REPAINT = 10  # RePaint / SDEdit: tables of 8 floats per index, the known image and its mask, three normal streams per step
+CHAIN_ILVR = 11  # ILVR: tables of 8 floats per index, the reference image, two filter matrices, two normal streams per step; a plane-wise update
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2  # what the network predicts (include/dmme_hip.h: DMME_PRED_*)
 PREDICTIONS = {"eps": PRED_EPS, "x0": PRED_X0, "v": PRED_V}
 THRESHOLD_NONE, THRESHOLD_STATIC, THRESHOLD_DYNAMIC = 0, 1, 2  # x0 thresholding in front of the update (include/dmme_hip.h: DMME_THRESHOLD_*)
@@ -113,6 +114,12 @@ PROTOTYPES = {
     "dmme_repaint_step": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i64, _i, _vp]),
     "dmme_chain_update_repaint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp]),
     "dmme_repaint_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_lowpass": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "dmme_lowpass_lds_capacity": (_i, []),
+    "dmme_lowpass_scratch_bytes": (_i64, [_i, _i, _i]),
+    "dmme_ilvr_step": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_chain_update_ilvr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_ilvr_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmme_unet_plan_num_ops": (_i, [_vp]),
     "dmme_unet_plan_level_info": (_i, [_vp, C.c_char_p, _i]),
     "dmme_unet_plan_check": (_i, [_vp]),

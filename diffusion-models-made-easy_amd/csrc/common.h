@@ -515,6 +515,14 @@ struct SamplerOperands {
 // row: kind_row host floats; flag: add_noise, or history_valid (kind_hist); ignored where the row decides (NOISE_C2, NOISE_ROW).  The guided kinds have no eager form.
 int launch_sampler_eager(const char* what, int kind, const SamplerOperands& o, const float* row, int flag, hipStream_t s);
 int launch_sampler_chain(const char* what, int kind, const SamplerOperands& o, const float* coef, const int64_t* t_table, void* state, hipStream_t s);
+// ilvr.hip: the ILVR update (DDPM's reverse step, then the low-pass refinement against a reference; kind DMME_CHAIN_ILVR has no row in the
+// table above: its update works on whole planes) and the filter on its own.  row: the eager form's 8 host floats; coef / t_table / state:
+// the chain form's; exactly one of the two is given.
+int launch_lowpass(const float* src, float* dst, int planes, int H, int W, const float* Ph, const float* Pw, float* scratch, int force_streaming,
+                   hipStream_t s);
+int launch_ilvr(const char* what, float* x, const float* model_out, const float* ref, const float* z2, const float* row, const float* Ph, const float* Pw,
+                float* scratch, const float* coef, const int64_t* t_table, void* state, int B, int C, int H, int W, int out_planes, int force_streaming,
+                hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient

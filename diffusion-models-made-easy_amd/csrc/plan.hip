@@ -1360,7 +1360,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 115; }  // 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 116; }  // 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1774,26 +1774,20 @@ DMME_API int dmme_chain_update_repaint(float* x, const float* model_out, const f
                                 step_coef, t_table, state, (hipStream_t)stream);
 }
 
-// One capturable step of any kind: the checks of plan against kind, the network's no-grad forward at the device-resident t (the loop
-// state's second word), `between` (the guided kinds' classifier pass, which fills the gradient operand), the update.  A classifier-free kind
-// runs a class-conditional plan of batch 2B with labels (conditional half, unconditional half) and updates at B = plan batch / 2.
-// The forward looks at the level engine's status word itself, under the name unet_forward; the unconditional entry points have always
-// looked first under their own name, and still do.
-static int chain_step_common(const char* what, const dmme_plan* plan, const void* packed, float* x, const int64_t* labels, int* status, float* model_out,
-                             void* workspace, int kind, const float* grad, float* hist, const float* step_coef, const int64_t* t_table, void* state,
-                             void* stream, const std::function<int()>& between = nullptr, const float* known = nullptr, const float* mask = nullptr) {
-    const bool cfg = kind_cfg(kind);
-    DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state && (labels || !cfg) && (hist || !kind_hist(kind)) &&
-                     ((known && mask) || !kind_paint(kind)),
-                 DMME_ERR_INVALID, "%s: null argument", what);
+// The front half of a capturable step, shared by every kind: the checks of the plan (`cfg`: a classifier-free kind; want_planes: the
+// output planes per image the kind takes, 0 = one or two), the forward, the x0 / v adapter, x0 thresholding (row, scol: where a
+// classifier-free kind's table holds its scale).  planes: the network's output planes per image.
+static int chain_step_front(const char* what, const dmme_plan* plan, const void* packed, float* x, const int64_t* labels, int* status, float* model_out,
+                            void* workspace, int kind, bool cfg, int want_planes, const float* step_coef, int row, int scol, void* state, void* stream,
+                            int& planes) {
     if (cfg)
         DMME_REQUIRE(plan->cond && plan->B % 2 == 0, DMME_ERR_INVALID,
                      "%s: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", what, plan->B);
     else
         DMME_REQUIRE(!plan->cond, DMME_ERR_INVALID, "%s: a class-conditional plan takes labels: call dmme_cfg_chain_step / dmme_cfg_dpmpp_chain_step", what);
     DMME_REQUIRE(plan->cfg.arch != DMME_ARCH_CLASSIFIER, DMME_ERR_INVALID, "%s: architecture %d predicts no noise", what, plan->cfg.arch);
-    const int planes = plan->out_channels / plan->cfg.in_channels;
-    DMME_REQUIRE(plan->out_channels == planes * plan->cfg.in_channels && (kind_planes(kind) ? planes == kind_planes(kind) : planes == 1 || planes == 2),
+    planes = plan->out_channels / plan->cfg.in_channels;
+    DMME_REQUIRE(plan->out_channels == planes * plan->cfg.in_channels && (want_planes ? planes == want_planes : planes == 1 || planes == 2),
                  DMME_ERR_INVALID, "%s: sampler kind %d does not fit a network with %d output channels for %d input channels", what, kind, plan->out_channels,
                  plan->cfg.in_channels);
     if (!cfg)
@@ -1810,9 +1804,28 @@ static int chain_step_common(const char* what, const dmme_plan* plan, const void
     // from the step's table row on the device) rewritten so that the x0 it implies is clipped; off launches nothing
     if (plan->thr_mode != DMME_THRESHOLD_NONE)
         if (int rc = launch_x0_threshold(plan->thr_mode, model_out, x, plan->thr_table, plan->thr_T, t_dev, 1, cfg ? plan->B / 2 : plan->B,
-                                         (int64_t)plan->cfg.in_channels * plan->H * plan->W, planes, cfg ? 2 : 1, 1.0f, cfg ? step_coef : nullptr, kind_row(kind),
-                                         kind_scol(kind), (const int64_t*)state, plan->thr_k, plan->thr_frac, plan->thr_scratch, (hipStream_t)stream))
+                                         (int64_t)plan->cfg.in_channels * plan->H * plan->W, planes, cfg ? 2 : 1, 1.0f, cfg ? step_coef : nullptr, row, scol,
+                                         (const int64_t*)state, plan->thr_k, plan->thr_frac, plan->thr_scratch, (hipStream_t)stream))
             return rc;
+    return DMME_OK;
+}
+
+// One capturable step of any kind: the checks of plan against kind, the network's no-grad forward at the device-resident t (the loop
+// state's second word), `between` (the guided kinds' classifier pass, which fills the gradient operand), the update.  A classifier-free kind
+// runs a class-conditional plan of batch 2B with labels (conditional half, unconditional half) and updates at B = plan batch / 2.
+// The forward looks at the level engine's status word itself, under the name unet_forward; the unconditional entry points have always
+// looked first under their own name, and still do.
+static int chain_step_common(const char* what, const dmme_plan* plan, const void* packed, float* x, const int64_t* labels, int* status, float* model_out,
+                             void* workspace, int kind, const float* grad, float* hist, const float* step_coef, const int64_t* t_table, void* state,
+                             void* stream, const std::function<int()>& between = nullptr, const float* known = nullptr, const float* mask = nullptr) {
+    const bool cfg = kind_cfg(kind);
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && step_coef && t_table && state && (labels || !cfg) && (hist || !kind_hist(kind)) &&
+                     ((known && mask) || !kind_paint(kind)),
+                 DMME_ERR_INVALID, "%s: null argument", what);
+    int planes = 0;
+    if (int rc = chain_step_front(what, plan, packed, x, labels, status, model_out, workspace, kind, cfg, kind_planes(kind), step_coef, kind_row(kind),
+                                  kind_scol(kind), state, stream, planes))
+        return rc;
     if (between)
         if (int rc = between()) return rc;
     return launch_sampler_chain(what, kind, sampler_operands(x, model_out, nullptr, cfg ? plan->B / 2 : plan->B, (int64_t)plan->cfg.in_channels * plan->H * plan->W,
@@ -1851,6 +1864,19 @@ DMME_API int dmme_repaint_chain_step(const dmme_plan* plan, const void* packed, 
                                      const float* mask, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
     return chain_step_common("repaint_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_REPAINT, nullptr, nullptr, step_coef, t_table,
                              state, stream, nullptr, known, mask);
+}
+
+// ILVR: kind DMME_CHAIN_ILVR, whose update works on whole planes (csrc/ilvr.hip) behind the front half every chain step has
+DMME_API int dmme_ilvr_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* ref, const float* Ph,
+                                  const float* Pw, float* scratch, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && ref && Ph && Pw && step_coef && t_table && state, DMME_ERR_INVALID,
+                 "ilvr_chain_step: null argument");
+    int planes = 0;
+    if (int rc = chain_step_front("ilvr_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_ILVR, false, 0, nullptr, 8, 0, state,
+                                  stream, planes))
+        return rc;
+    return launch_ilvr("ilvr_chain_step", x, model_out, ref, nullptr, nullptr, Ph, Pw, scratch, step_coef, t_table, state, plan->B, plan->cfg.in_channels, plan->H,
+                       plan->W, planes, 0, (hipStream_t)stream);
 }
 
 // Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM): between the forward and the update, the classifier's forward, the log-softmax

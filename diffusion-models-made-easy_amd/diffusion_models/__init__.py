@@ -3,3 +3,4 @@ from .ddim import DDIM, GeneralizedDDIM  # noqa: F401
 from .iddpm import IDDPM  # noqa: F401
 from .dpm_solver import DPMSolverPP  # noqa: F401
 from .repaint import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401
+from .ilvr import ILVR, LikeChainRunner, ilvr_rows, lowpass_matrix  # noqa: F401

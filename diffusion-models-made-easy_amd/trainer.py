@@ -22,6 +22,7 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3,5 --guidance-scale 2.5   (classifier-free guidance)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dpm++ --sample-steps 20   (DPM-Solver++(2M); any of the four configs)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler ilvr --image X.npy --down-factor 8 --save OUT.npy   (ILVR: samples that share X's coarse content)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3 --guidance-scale 2.5 --threshold dynamic   (x0 thresholding in front of the update: none | static | dynamic [--threshold-percentile P]; any sampler)
@@ -300,6 +301,8 @@ def _check_paint_args(args) -> None:
     """what goes with --sampler repaint / sdedit and what does not; exits with a message (before anything touches the GPU)"""
     given = [f for f, v in (("--image", args.image), ("--mask", args.mask), ("--strength", args.strength), ("--jump-length", args.jump_length),
                             ("--resamples", args.resamples)) if v is not None]
+    if args.sampler == "ilvr":
+        return  # (`_check_ilvr_args` has looked at all of these)
     if args.sampler not in PAINT_SAMPLERS:
         if given:
             raise SystemExit(f"{', '.join(given)} belong{'s' if len(given) == 1 else ''} to --sampler repaint / sdedit")
@@ -328,6 +331,52 @@ def _check_paint_args(args) -> None:
             raise SystemExit(f"{', '.join(walk)} belong{'s' if len(walk) == 1 else ''} to --sampler repaint: SDEdit walks straight down")
         if args.strength is None or not 0.0 < args.strength <= 1.0:
             raise SystemExit("--sampler sdedit needs --strength S in (0, 1]: the share of the noise levels the guide is pushed up")
+
+
+def _check_ilvr_args(args):
+    """what goes with --sampler ilvr and what does not; exits with a message (before anything touches the GPU).  Returns the reference
+    image (--sampler ilvr) or None."""
+    own = [f for f, v in (("--down-factor", args.down_factor), ("--range-level", args.range_level)) if v is not None]
+    if args.sampler != "ilvr":
+        if own:
+            raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to --sampler ilvr")
+        return None
+    name = "--sampler ilvr"
+    if args.command != "sample":
+        raise SystemExit(f"{name} belongs to `sample`: it conditions a trained network on a reference image, training is the config's own")
+    other = [f for f, v in (("--mask", args.mask), ("--strength", args.strength), ("--jump-length", args.jump_length), ("--resamples", args.resamples))
+             if v is not None]
+    if other:
+        raise SystemExit(f"{', '.join(other)} belong{'s' if len(other) == 1 else ''} to --sampler repaint / sdedit, not to {name}")
+    for flag, v in (("--eta", args.eta), ("--steps", args.steps), ("--labels", args.labels), ("--guidance-scale", args.guidance_scale)):
+        if v is not None:
+            raise SystemExit(f"{flag} does not go with {name}: it runs whole chains of an unconditional network (--sample-steps K sets the grid)")
+    if args.image is None:
+        raise SystemExit(f"{name} needs --image X.npy, the reference (float32 in [-1, 1], (B, C, H, W) or (C, H, W))")
+    if args.sample_steps is not None and args.sample_steps < 1:
+        raise SystemExit("--sample-steps must be at least 1")
+    N = 4 if args.down_factor is None else args.down_factor
+    if N < 2:
+        raise SystemExit("--down-factor must be at least 2")
+    if args.range_level is not None and args.range_level < 0:
+        raise SystemExit("--range-level must be at least 0")
+    image = _load_npy(args.image, "--image")
+    H, W = image.shape[2:]
+    if H % N != 0 or W % N != 0:
+        raise SystemExit(f"--image {args.image}: the image size {H} x {W} is not divisible by --down-factor {N}")
+    return image
+
+
+def _ilvr_process(module, args):
+    """ILVR over the network and the noise schedule of the process the YAML built"""
+    from .diffusion_models import ILVR
+
+    old = module.diffusion_model
+    sub = min(250, old.timesteps) if args.sample_steps is None else args.sample_steps
+    r = args.range_level or 0
+    if r > sub:
+        raise SystemExit(f"--range-level {r} lies above the grid's {sub} levels")
+    return ILVR.from_process(old, sub_timesteps=sub, down_factor=args.down_factor or 4, range_level=r)
 
 
 def _load_npy(path: str, what: str) -> torch.Tensor:
@@ -368,15 +417,18 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
-    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit"],
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table; "
                          "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20); "
-                         "'repaint' inpaints --image where --mask is 0, 'sdedit' edits --image at --strength (any unconditional config; --sample-steps: grid levels, default 250)")
+                         "'repaint' inpaints --image where --mask is 0, 'sdedit' edits --image at --strength (any unconditional config; --sample-steps: grid levels, default 250); "
+                         "'ilvr' samples images that share the low frequencies of --image (any unconditional config; --down-factor N, --range-level R, --sample-steps)")
     ap.add_argument("--image", default=None, help="sample --sampler repaint / sdedit: .npy, float32 in [-1, 1], (B, C, H, W) or (C, H, W)")
     ap.add_argument("--mask", default=None, help="sample --sampler repaint (needed) / sdedit (optional): .npy broadcastable to the image, 1 = keep the pixel, 0 = generate")
     ap.add_argument("--strength", type=float, default=None, help="sample --sampler sdedit: in (0, 1], the share of the noise levels the guide is pushed up before it is denoised")
     ap.add_argument("--jump-length", type=int, default=None, help="sample --sampler repaint: levels a resampling jump climbs (default 10)")
     ap.add_argument("--resamples", type=int, default=None, help="sample --sampler repaint: times each stretch of --jump-length levels is walked (default 10)")
+    ap.add_argument("--down-factor", type=int, default=None, help="sample --sampler ilvr: N of the low-pass filter, at least 2 and a divisor of the image size (default 4); small N stays close to --image")
+    ap.add_argument("--range-level", type=int, default=None, help="sample --sampler ilvr: steps that end below this grid level are not conditioned (default 0: every step is)")
     ap.add_argument("--save", default=None, help="sample: write the images to this .npy file (float32, (B, C, H, W))")
     ap.add_argument("--grid", default=None, help="sample: write the images to this PNG file as a grid (every sampler; goes with --save)")
     ap.add_argument("--vis-length", type=int, default=1,
@@ -404,6 +456,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     _check_solver_args(args)
     _check_threshold_args(args)
+    ilvr_image = _check_ilvr_args(args)
     _check_paint_args(args)
     if args.save is not None and args.command != "sample":
         raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
@@ -428,6 +481,10 @@ def main(argv=None):
             raise SystemExit(f"--sampler {args.sampler} needs an unconditional config: guided inpainting / editing is not implemented")
         image = _load_npy(args.image, "--image")
         mask = None if args.mask is None else _load_npy(args.mask, "--mask")
+    elif args.sampler == "ilvr":
+        if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+            raise SystemExit("--sampler ilvr needs an unconditional config: guided ILVR is not implemented")
+        image = ilvr_image
     elif args.sample_steps is not None and args.sampler != "dpm++":
         from .lit_modules import LitIDDPM
 
@@ -468,6 +525,8 @@ def main(argv=None):
             module.diffusion_model = _dpm_solver(module, args).cuda()
         elif args.sampler in PAINT_SAMPLERS:
             module.diffusion_model = _paint_process(module, args).cuda()
+        elif args.sampler == "ilvr":
+            module.diffusion_model = _ilvr_process(module, args).cuda()
         module.eval()
         dm = module.diffusion_model
         if args.threshold is not None:
@@ -485,12 +544,14 @@ def main(argv=None):
                 count = dm._respaced_tables(args.sample_steps)[0]  # (Improved DDPM's strided chain)
             else:
                 count = dm.chain_length()
-            rec_shape = tuple(image.shape) if args.sampler in PAINT_SAMPLERS else shape
+            rec_shape = tuple(image.shape) if args.sampler in PAINT_SAMPLERS + ("ilvr",) else shape
             rec = HistoryRecorder(rec_shape[0], *rec_shape[1:], history_ordinals(count, args.vis_length), out_kind=1)
         if args.sampler == "repaint":
             imgs = dm.inpaint(image, mask, history=rec)
         elif args.sampler == "sdedit":
             imgs = dm.edit(image, args.strength, mask, history=rec)
+        elif args.sampler == "ilvr":
+            imgs = dm.sample_like(image, history=rec)
         elif getattr(module, "conditional", False):
             if args.steps is not None or args.sampler == "ddim-paper" or (args.sample_steps is not None and args.sampler != "dpm++"):
                 raise SystemExit("class-conditional configs sample whole chains: --labels / --guidance-scale only")

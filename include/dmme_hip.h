@@ -422,7 +422,7 @@ DMME_API int dmme_pred_to_eps(int pred, float* model_out, const float* x, const 
 
 /* host-only state of a plan: what its network predicts.  With DMME_PRED_X0 / DMME_PRED_V every capturable step over the plan
  * (dmme_chain_step, dmme_cfg_chain_step, dmme_dpmpp_chain_step, dmme_cfg_dpmpp_chain_step, dmme_repaint_chain_step,
- * dmme_guided_chain_step) launches dmme_pred_to_eps(pred, model_out, x, ab, T, &state.t, 1, plan batch, C*H*W) directly behind the
+ * dmme_ilvr_chain_step, dmme_guided_chain_step) launches dmme_pred_to_eps(pred, model_out, x, ab, T, &state.t, 1, plan batch, C*H*W) directly behind the
  * forward - over all 2B images of a classifier-free plan: the mixing weights 1 - s and s sum to one, so the affine map commutes
  * with e_u + s (e_c - e_u) - and in front of the classifier pass and the update.  `ab` stays the caller's and must outlive every launch and
  * every captured graph that holds its address.  A plan is shared by every process that wraps the same network: set the prediction in
@@ -671,6 +671,60 @@ DMME_API int dmme_chain_update_repaint(float* x, const float* model_out, const f
                                        const float* step_coef, const int64_t* t_table, void* state, int B, int64_t chw, int out_planes, void* stream);
 DMME_API int dmme_repaint_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* known,
                                      const float* mask, const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
+/* ---- ILVR (Choi et al. 2021): sampling that shares the coarse content of a reference image (csrc/ilvr.hip) ----------------------------
+ * Grid and levels as RePaint's; the walk goes straight down, n -> 0, one network evaluation and one table row per transition
+ * a -> b = a - 1.  With y the clean reference and phi a linear low-pass filter, a step is DDPM's reverse step followed by the
+ * refinement x' = phi(y_b) + u - phi(u) of the paper, written with ONE filter application because phi is linear:
+ *     u  = c0 (x - c1 e);      u = u + c2 z0          only where c2 != 0        DDPM's reverse step (sigma^2 = beta), DDPM's bits
+ *     if g != 0:
+ *         k  = ka y;           k = k + ks z1          only where ks != 0        the reference noised to level b
+ *         d  = k - u
+ *         x' = u + phi(d)                              phi(d) = Ph d Pw^T per channel plane of H x W
+ *     else x' = u
+ * Kind DMME_CHAIN_ILVR = 11 has entry points and a table layout of its own and no row in the kind table of the elementwise updates:
+ * dmme_chain_step and dmme_chain_update refuse it.
+ *   step_coef float[n+1][8], per loop index (alpha = abar_a / abar_b):
+ *             {c0 = 1/sqrt(alpha), c1 = (1 - alpha)/sqrt(1 - abar_a), c2 = sqrt(1 - alpha) (0 where b = 0), ka = sqrt(abar_b),
+ *              ks = sqrt(1 - abar_b) (0 at b = 0), g = 1 while the step is conditioned else 0, -, -}
+ *   t_table   int64[n+1]: t_table[i] = tau_a; t_table[0] = 0
+ *   ref       fp32, B * chw values in x's layout, read only
+ *   Ph, Pw    device fp32, [H][H] and [W][W] row-major: per axis of length n the product R(n/N -> n) R(n -> n/N) of the two bicubic
+ *             (a = -0.5) resize matrices, antialiased on the way down, windows clipped to the image and renormalised (rows sum to 1),
+ *             which the host builds in float64 and rounds once.  The library reads them as dense matrices and assumes nothing else.
+ *   rounding  the elementwise half rounds every product, sum and difference to fp32 on its own (no fma), so with g = 0 the step is
+ *             dmme_ddpm_step bit for bit.  The filter is T = d Pw^T, then F = Ph T: each value is the chain
+ *             acc = fma(a_k, b_k, acc), k = 0, 1, ... from acc = 0, in ONE device function that every form calls; x' = u + F is one
+ *             more rounded sum.  Hence |F - exact| <= (H + W + 8) 2^-24 (|Ph| |d| |Pw|^T) elementwise.
+ *   normals   a step owns TWO streams of B*chw normals: stream s of quad q is the draw at Philox counter offset + s * (B*chw/4) + q, so
+ *             dmme_randn(z2, 2*B*chw, seed, offset) writes exactly the [2][B*chw] block the eager form reads.  A stream whose
+ *             coefficient is zero is neither drawn nor read, and an unconditioned row never touches z1.  The chain form moves the
+ *             offset by 2 * B*chw/4 per step whatever the row used.
+ *   forms     fused: planes of H*W <= dmme_lowpass_lds_capacity() values whose tables fit beside them (64 x 64 and 32 x 32 do) take ONE
+ *             launch, one workgroup per plane: d, T and both tables in LDS, u in registers, x' stored 16 bytes at a time; in place is
+ *             safe because a plane is read completely before it is written.  Streaming: larger planes (256 x 256; H <= 384,
+ *             W <= 767) take two launches, a row pass that writes T to `scratch` (dmme_lowpass_scratch_bytes(B*C, H, W) bytes) and a
+ *             column pass that recomputes u from the same operands and Philox counters; the loop state advances at the end of the
+ *             second.  force_streaming != 0 sends a plane that fits the fused form through the streaming one: the same bits.
+ *   out_planes  1 (eps), or 2 (an IDDPM network's (eps, v): the eps plane is used).
+ * C*H*W and W must be multiples of 4.  dmme_lowpass applies phi alone to `planes` planes (dst may equal src).  dmme_ilvr_step: the eager
+ * twin (row: 8 floats in HOST memory; z2: the [2][B*chw] block, nullable only where the row uses no stream), bit-identical to
+ * dmme_chain_update_ilvr, the chain form (row from device memory at step_coef[8 i], normals drawn in the kernel; noise: nullable, a
+ * [2][B*chw] block used in place of the drawn normals - tests).  dmme_ilvr_chain_step = dmme_unet_forward (no-grad form) at t = state.t,
+ * the x0 / v adapter and x0 thresholding as every chain step has them, then dmme_chain_update_ilvr; an unconditional DMME_ARCH_DDPM or
+ * DMME_ARCH_IDDPM plan. */
+enum { DMME_CHAIN_ILVR = 11 };
+DMME_API int dmme_lowpass(const float* src, float* dst, int planes, int H, int W, const float* Ph, const float* Pw, float* scratch, int force_streaming,
+                          void* stream);
+DMME_API int dmme_lowpass_lds_capacity(void);
+DMME_API int64_t dmme_lowpass_scratch_bytes(int planes, int H, int W);
+DMME_API int dmme_ilvr_step(float* x, const float* model_out, const float* ref, const float* z2, const float* row, const float* Ph, const float* Pw,
+                            float* scratch, int B, int C, int H, int W, int out_planes, int force_streaming, void* stream);
+DMME_API int dmme_chain_update_ilvr(float* x, const float* model_out, const float* ref, const float* noise, const float* Ph, const float* Pw, float* scratch,
+                                    const float* step_coef, const int64_t* t_table, void* state, int B, int C, int H, int W, int out_planes,
+                                    int force_streaming, void* stream);
+DMME_API int dmme_ilvr_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* ref, const float* Ph,
+                                  const float* Pw, float* scratch, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
