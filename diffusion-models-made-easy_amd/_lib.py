@@ -120,6 +120,9 @@ PROTOTYPES = {
     "dmme_ilvr_step": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dmme_chain_update_ilvr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dmme_ilvr_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_distill_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_distill_mid": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "dmme_distill_target": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "dmme_unet_plan_num_ops": (_i, [_vp]),
     "dmme_unet_plan_level_info": (_i, [_vp, C.c_char_p, _i]),
     "dmme_unet_plan_check": (_i, [_vp]),

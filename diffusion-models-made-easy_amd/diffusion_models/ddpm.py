@@ -28,7 +28,7 @@ def _scalar_index(t: Tensor, what: str) -> int:
     return int(t.reshape(-1)[0].item())
 
 
-LOSS_WEIGHTS = ("uniform", "min-snr")
+LOSS_WEIGHTS = ("uniform", "min-snr", "truncated-snr")
 
 
 def prediction_table(alpha_bar, prediction: str) -> np.ndarray:
@@ -90,17 +90,26 @@ def _check_threshold(mode, percentile) -> Tuple[str, float]:
 def loss_weight_table(alpha_bar, prediction: str, loss_weight: str, snr_gamma: float = 5.0) -> np.ndarray:
     """float64 [T+1] weights of the per-timestep MSE.  "min-snr" (Hang et al. 2023) with snr = abar/(1-abar): min(snr, gamma)/snr for an
     eps network, min(snr, gamma) for x0, min(snr, gamma)/(snr + 1) for v - the same weight min(snr, gamma) on the x0 error each
-    loss implies.  Where abar = 1 (index 0, snr infinite: never drawn) the limits 0, gamma, 0.  "uniform": ones."""
+    loss implies.  Where abar = 1 (index 0, snr infinite: never drawn) the limits 0, gamma, 0.  "uniform": ones.  "truncated-snr" (Salimans
+    & Ho 2022, the weight progressive distillation trains under): max(snr, 1) on the x0 error, so max(snr, 1)/snr for eps, max(snr, 1)
+    for x0, max(snr, 1)/(snr + 1) for v; where abar = 1: 1, NaN (the weight is unbounded there), 1."""
     ab = np.asarray(alpha_bar, dtype=np.float64).reshape(-1)
     if prediction not in _lib.PREDICTIONS:
         raise ValueError(f"prediction = {prediction!r}; use one of {tuple(_lib.PREDICTIONS)}")
     if loss_weight == "uniform":
         return np.ones_like(ab)
-    if loss_weight != "min-snr":
+    if loss_weight not in LOSS_WEIGHTS:
         raise ValueError(f"loss_weight = {loss_weight!r}; use one of {LOSS_WEIGHTS}")
-    gamma = float(snr_gamma)
     one = ab >= 1.0
     snr = np.where(one, 1.0, ab) / np.where(one, 1.0, 1 - ab)
+    if loss_weight == "truncated-snr":
+        floored = np.maximum(snr, 1.0)
+        if prediction == "eps":
+            return np.where(one, 1.0, floored / snr)
+        if prediction == "x0":
+            return np.where(one, np.nan, floored)
+        return np.where(one, 1.0, floored / (snr + 1.0))
+    gamma = float(snr_gamma)
     clipped = np.minimum(snr, gamma)
     if prediction == "eps":
         return np.where(one, 0.0, clipped / snr)
@@ -118,8 +127,8 @@ class DDPM(nn.Module):
                  loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
         """`prediction`: what the network's output is - "eps" (the noise), "x0", or "v" = sqrt(abar_t) eps - sqrt(1 - abar_t) x0 (Salimans
         & Ho 2022).  Training regresses on that target; sampling turns the output into an eps prediction with one elementwise launch
-        behind the network (dmme_pred_to_eps) and runs today's updates on it.  `loss_weight`: "uniform" or "min-snr" (Hang et al.
-        2023, clipped at `snr_gamma`).  `threshold`: sampling clips the x0 each eps prediction implies, in front of the update
+        behind the network (dmme_pred_to_eps) and runs today's updates on it.  `loss_weight`: "uniform", "min-snr" (Hang et al.
+        2023, clipped at `snr_gamma`) or "truncated-snr" (Salimans & Ho 2022: max(snr, 1) on the x0 error).  `threshold`: sampling clips the x0 each eps prediction implies, in front of the update
         (dmme_x0_threshold) - "static" to [-1, 1] (the published samplers' clip_denoised), "dynamic" to the image's
         `threshold_percentile` quantile of |x0| where that exceeds 1, then rescaled (Saharia et al. 2022); see `set_threshold`."""
         super().__init__()

@@ -123,3 +123,56 @@ def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=N
 
         save_checkpoint(save_path, module, opt, sched, global_step=max(max_steps, first))
     return module
+
+
+def _batches(loader, batch_size, dev):
+    """endless (x0,) stream: synthetic batches, or epochs over the loader"""
+    while True:
+        if loader is None:
+            yield synthetic_batch(batch_size, dev)
+        else:
+            for batch in loader:
+                yield batch[0]
+
+
+def fit_distill(module, steps_from: int, steps_to: int, stage_steps: int, batch_size=128, clip=None, log_every=50, loader=None, save_path=None):
+    """progressive distillation behind `python -m dmme_amd.trainer distill`: stages N = steps_from, steps_from / 2, ..., steps_to of
+    `stage_steps` optimiser steps each, `halve()` between them, the optimiser and its schedule built fresh for every stage (`module`: a
+    lit_modules.LitDistill whose process stands at steps_from).  One JSON line per log interval: stage N, step, loss, images/s."""
+    dm = module.diffusion_model
+    if dm.steps != steps_from:
+        raise ValueError(f"fit_distill: the process stands at {dm.steps} steps, the first stage is {steps_from}")
+    dev = next(module.parameters()).device
+    model = dm.model
+    module.stage_steps = int(stage_steps)
+    stream = _batches(loader, batch_size, dev)
+    total = 0
+    while True:
+        module.train()
+        opts, scheds = module.configure_optimizers()
+        opt, sched = opts[0], scheds[0]["scheduler"]
+        if clip:
+            for g in opt.param_groups:
+                g["max_grad_norm"] = float(clip)
+        if D.sync_parameters(model, opt):
+            model._dp_synced = True
+        t0 = time.perf_counter()
+        for step in range(stage_steps):
+            loss = train_step(module, opt, sched, next(stream), clip)
+            if (step + 1) % log_every == 0 or step + 1 == stage_steps:
+                torch.cuda.synchronize()
+                if hasattr(model, "check_engine"):
+                    model.check_engine()
+                dm.check_indices()
+                dt = time.perf_counter() - t0
+                print(json.dumps({"stage": dm.steps, "step": step + 1, "train/loss": round(float(loss.detach()), 5),
+                                  "images_per_s": round((step + 1) * batch_size / dt, 1)}), flush=True)
+        total += stage_steps
+        if dm.steps <= steps_to:
+            break
+        dm.halve()
+    if save_path and D.env_rank_world()[0] == 0:
+        from .checkpoint import save_checkpoint
+
+        save_checkpoint(save_path, module, opt, sched, global_step=total)
+    return module

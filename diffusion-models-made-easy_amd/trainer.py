@@ -28,6 +28,9 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3 --guidance-scale 2.5 --threshold dynamic   (x0 thresholding in front of the update: none | static | dynamic [--threshold-percentile P]; any sampler)
   python -m dmme_amd.trainer fit    --config configs/vpred/cifar10.yaml   (a v-prediction network under min-SNR weights; --prediction / --loss-weight / --snr-gamma override any YAML)
   python -m dmme_amd.trainer fit    --config configs/ddpm/cifar10.yaml --preview-dir DIR --preview-every N   (a history grid DIR/step_<n>.png every N optimiser steps)
+  python -m dmme_amd.trainer distill --config configs/vpred/cifar10.yaml --ckpt-path TEACHER.ckpt --distill-from 1024 --distill-to 4 --stage-steps 50000 --save-checkpoint OUT.ckpt
+                                    (progressive distillation: a teacher sampled in 1024 DDIM steps becomes a 4-step student, one halving per stage; [--clip-x0] [--data config])
+  python -m dmme_amd.trainer sample --config configs/vpred/cifar10.yaml --ckpt-path OUT.ckpt   (a distilled checkpoint samples with the steps and the grid it was trained for)
 """
 
 from __future__ import annotations
@@ -251,8 +254,10 @@ def build_module(conf: Dict[str, Any]):
 
 def _check_solver_args(args) -> None:
     """what goes with --sampler dpm++ and what does not; exits with a message (before anything touches the GPU)"""
-    solver_flags = [f for f, given in (("--solver-order", args.solver_order is not None), ("--tau-schedule", args.tau_schedule is not None),
-                                       ("--clip-x0", args.clip_x0)) if given]
+    # (--tau-schedule linear / quadratic also goes with --sampler ddim-paper: the grid of GeneralizedDDIM; --clip-x0 also with `distill`)
+    paper_tau = args.sampler == "ddim-paper" and args.tau_schedule in ("linear", "quadratic")
+    solver_flags = [f for f, given in (("--solver-order", args.solver_order is not None), ("--tau-schedule", args.tau_schedule is not None and not paper_tau),
+                                       ("--clip-x0", args.clip_x0 and args.command != "distill")) if given]
     if args.sampler != "dpm++":
         if solver_flags:
             raise SystemExit(f"{', '.join(solver_flags)} belong{'s' if len(solver_flags) == 1 else ''} to --sampler dpm++")
@@ -278,6 +283,76 @@ def _check_threshold_args(args) -> None:
             raise SystemExit("--threshold-percentile belongs to --threshold dynamic")
         if not 0.0 <= args.threshold_percentile <= 1.0:
             raise SystemExit(f"--threshold-percentile {args.threshold_percentile} outside [0, 1]")
+
+
+DISTILL_FLAGS = (("--distill-from", "distill_from"), ("--distill-to", "distill_to"), ("--stage-steps", "stage_steps"))
+
+
+def _check_distill_args(args) -> None:
+    """what goes with `distill` and what does not; exits with a message (before anything touches the GPU)"""
+    given = [f for f, name in DISTILL_FLAGS if getattr(args, name) is not None]
+    if args.command != "distill":
+        if given:
+            raise SystemExit(f"{', '.join(given)} belong{'s' if len(given) == 1 else ''} to `distill`")
+        return
+    missing = [f for f, name in DISTILL_FLAGS if getattr(args, name) is None]
+    if missing:
+        raise SystemExit(f"distill needs {', '.join(missing)}")
+    if args.ckpt_path is None:
+        raise SystemExit("distill needs --ckpt-path TEACHER.ckpt: the trained network whose sampler is distilled")
+    if args.save_checkpoint is None:
+        raise SystemExit("distill needs --save-checkpoint OUT.ckpt: the student is its only result")
+    if args.sampler != "config" or args.max_steps is not None:
+        raise SystemExit("--sampler / --max-steps do not go with `distill`: --stage-steps K sets the length of every stage")
+    n0, n1 = args.distill_from, args.distill_to
+    if n1 < 1 or n0 <= n1:
+        raise SystemExit(f"--distill-from {n0} --distill-to {n1}: the teacher's steps must exceed the last student's, which are at least 1")
+    ratio = n0 // n1
+    if n0 % n1 != 0 or ratio & (ratio - 1) != 0:
+        raise SystemExit(f"--distill-from {n0} --distill-to {n1}: every stage halves the steps, so the first must be the last times a power of two")
+    if args.stage_steps < 1:
+        raise SystemExit("--stage-steps must be at least 1")
+
+
+def _distill(args, conf, B, rank_seed=None) -> int:
+    """`distill`: the YAML's network twice (teacher and student, both from --ckpt-path), then the stages of train_loop.fit_distill"""
+    from .checkpoint import load_checkpoint
+    from .diffusion_models import ProgressiveDistillation
+    from .lit_modules import LitDistill
+    from .train_loop import fit_distill
+
+    if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+        raise SystemExit("distill needs an unconditional config: classifier-free distillation is out of scope")
+    built = []
+    for _ in range(2):
+        module = build_module(conf).cuda()
+        load_checkpoint(args.ckpt_path, module, strict=False)
+        built.append(module)
+    if rank_seed is not None:
+        torch.manual_seed(rank_seed)
+    old = built[0].diffusion_model
+    if args.distill_from > old.timesteps:
+        raise SystemExit(f"--distill-from {args.distill_from}: the process has {old.timesteps} timesteps")
+    try:
+        process = ProgressiveDistillation(built[1].diffusion_model.model, old.model, old.timesteps, args.distill_from // 2, prediction=old.prediction,
+                                          clip_x0=args.clip_x0).cuda()
+    except NotImplementedError as exc:
+        raise SystemExit(str(exc))
+    lit = LitDistill(process, lr=built[0].lr, stage_steps=args.stage_steps).cuda()
+    loader = None
+    if args.data == "config" and conf["data_spec"]:
+        data = _instantiate(conf["data_spec"])
+        data.batch_size = B
+        try:
+            data.prepare_data()
+        except FileNotFoundError as e:
+            print(json.dumps({"data": "random bytes (dataset files absent)", "reason": str(e)[:160]}), flush=True)
+            data.synthetic = True
+        data.setup("fit")
+        loader = data.train_dataloader()
+    fit_distill(lit, args.distill_from // 2, args.distill_to, args.stage_steps, batch_size=B, clip=conf["gradient_clip_val"], log_every=conf["log_every_n_steps"],
+                loader=loader, save_path=args.save_checkpoint)
+    return 0
 
 
 def _dpm_solver(module, args):
@@ -405,7 +480,7 @@ def _paint_process(module, args):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="dmme_amd.trainer")
-    ap.add_argument("command", choices=["fit", "sample"])
+    ap.add_argument("command", choices=["fit", "sample", "distill"])
     ap.add_argument("--config", required=True)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
@@ -438,23 +513,27 @@ def main(argv=None):
                     help="fit --preview-dir: every N optimiser steps - steps, not the epochs of the YAML's GenerateImage entry: synthetic-data runs have no epochs")
     ap.add_argument("--eta", type=float, default=None, help="sample --sampler ddim-paper: 0 (default) deterministic ... 1 DDPM's posterior variance")
     ap.add_argument("--solver-order", type=int, default=None, choices=[1, 2], help="sample --sampler dpm++: 2 (default) multistep second order, 1 first order")
-    ap.add_argument("--tau-schedule", default=None, choices=["linear", "quadratic", "logsnr"], help="sample --sampler dpm++: the timestep grid (default logsnr)")
+    ap.add_argument("--tau-schedule", default=None, choices=["linear", "quadratic", "logsnr"], help="sample --sampler dpm++: the timestep grid (default logsnr); --sampler ddim-paper: linear | quadratic, over the YAML's")
     ap.add_argument("--clip-x0", action="store_true", help="sample --sampler dpm++: clamp every x0 prediction to [-1, 1] (wanted with the cosine schedule of the iddpm config, "
-                         "whose abar_T = 1.9e-15 scales the first x0 prediction by 2.3e7)")
+                         "whose abar_T = 1.9e-15 scales the first x0 prediction by 2.3e7); distill: clamp the teacher's two x0 estimates")
     ap.add_argument("--labels", default=None, help="sample, class-conditional configs: comma-separated class labels, one per image or one for all (e.g. 3,5,7)")
     ap.add_argument("--guidance-scale", type=float, default=None, help="sample, class-conditional configs: s of e_u + s (e_c - e_u); 1 = conditional, 0 = unconditional")
     ap.add_argument("--sample-steps", type=int, default=None,
                     help="sample, Improved DDPM configs: a strided chain over this many of the T timesteps, with the learned variance; "
                          "sample --sampler dpm++: the solver's steps")
     ap.add_argument("--prediction", default=None, choices=["eps", "x0", "v"], help="what the network predicts, over the YAML's `prediction` (default eps)")
-    ap.add_argument("--loss-weight", default=None, choices=["uniform", "min-snr"], help="fit: the loss's weight per timestep, over the YAML's `loss_weight`")
+    ap.add_argument("--loss-weight", default=None, choices=["uniform", "min-snr", "truncated-snr"], help="fit: the loss's weight per timestep, over the YAML's `loss_weight`")
     ap.add_argument("--snr-gamma", type=float, default=None, help="fit --loss-weight min-snr: the SNR the weight is clipped at (default 5)")
+    ap.add_argument("--distill-from", type=int, default=None, help="distill: the DDIM steps the teacher is sampled in (the first student takes half)")
+    ap.add_argument("--distill-to", type=int, default=None, help="distill: the steps of the last student; --distill-from is this times a power of two")
+    ap.add_argument("--stage-steps", type=int, default=None, help="distill: optimiser steps of every halving stage (the rate falls linearly to zero within each)")
     ap.add_argument("--threshold", default=None, choices=["none", "static", "dynamic"],
                     help="sample, every sampler: clip the x0 each noise prediction implies, in front of the update - static: to [-1, 1] (clip_denoised); "
                          "dynamic: to the image's --threshold-percentile quantile of |x0| where above 1, rescaled (wanted with --guidance-scale above 1)")
     ap.add_argument("--threshold-percentile", type=float, default=None, help="sample --threshold dynamic: the quantile, in [0, 1] (default 0.995)")
     args = ap.parse_args(argv)
     _check_solver_args(args)
+    _check_distill_args(args)
     _check_threshold_args(args)
     ilvr_image = _check_ilvr_args(args)
     _check_paint_args(args)
@@ -503,24 +582,37 @@ def main(argv=None):
     torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
     seed = conf["seed"] if isinstance(conf["seed"], int) and not isinstance(conf["seed"], bool) else 1337
     torch.manual_seed(seed)  # identical initial weights on every rank ...
+    if args.command == "distill":
+        # (builds the YAML's network twice, teacher and student; several ranks: each draws from its own stream afterwards, as below)
+        return _distill(args, conf, args.batch_size or conf["batch_size"], D.rank_seed(seed, rank) if world > 1 else None)
     module = build_module(conf).cuda()
     if world > 1:
         torch.manual_seed(D.rank_seed(seed, rank))  # ... then each rank's own stream for timesteps, noise and dropout masks
     B = args.batch_size or conf["batch_size"]
 
     ckpt_path = args.ckpt_path or conf.get("ckpt_path")
+    distilled = None
     if args.command == "sample":
         if ckpt_path:
             from .checkpoint import load_checkpoint
 
-            load_checkpoint(ckpt_path, module, strict=False)
+            distilled = load_checkpoint(ckpt_path, module, strict=False).get("distill")
+        if args.sampler != "config" or args.sample_steps is not None:
+            distilled = None  # (an explicit sampler wins over the checkpoint's)
+        if distilled is not None:
+            from .diffusion_models import GeneralizedDDIM
+
+            old = module.diffusion_model
+            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, int(distilled["steps"]), distilled.get("tau_schedule", "linear"), eta=0.0,
+                                                     prediction=distilled.get("prediction", old.prediction)).cuda()
         if args.sampler == "ddim-paper":
             from .diffusion_models import DDIM, GeneralizedDDIM
 
             old = module.diffusion_model
             if not isinstance(old, DDIM):
                 raise SystemExit("--sampler ddim-paper needs a DDIM config (sub_timesteps and a tau schedule)")
-            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, old.tau_schedule, eta=args.eta or 0.0, prediction=old.prediction).cuda()
+            module.diffusion_model = GeneralizedDDIM(old.model, old.timesteps, old.sub_timesteps, args.tau_schedule or old.tau_schedule, eta=args.eta or 0.0,
+                                                     prediction=old.prediction).cuda()
         elif args.sampler == "dpm++":
             module.diffusion_model = _dpm_solver(module, args).cuda()
         elif args.sampler in PAINT_SAMPLERS:
@@ -573,7 +665,7 @@ def main(argv=None):
             import dmme_amd
 
             imgs = dmme_amd.gaussian(shape, device="cuda")
-            first = dm.sub_timesteps if args.sampler == "ddim-paper" else dm.timesteps  # (the paper sampler's loop index counts sub-steps)
+            first = dm.sub_timesteps if args.sampler == "ddim-paper" or distilled is not None else dm.timesteps  # (the paper sampler's loop index counts sub-steps)
             for k in range(args.steps):
                 imgs = module(imgs, first - k)
         torch.cuda.synchronize()
@@ -585,8 +677,10 @@ def main(argv=None):
             from .common.vis import save_png
 
             save_png(args.grid, rec.canvas)
-        print(json.dumps({"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3),
-                          "finite": bool(torch.isfinite(imgs).all())}))
+        line = {"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3), "finite": bool(torch.isfinite(imgs).all())}
+        if distilled is not None:
+            line["distill"] = {"steps": int(distilled["steps"]), "tau_schedule": distilled.get("tau_schedule", "linear")}
+        print(json.dumps(line))
         return 0
 
     from .train_loop import fit

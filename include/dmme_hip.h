@@ -726,6 +726,37 @@ DMME_API int dmme_chain_update_ilvr(float* x, const float* model_out, const floa
 DMME_API int dmme_ilvr_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* ref, const float* Ph,
                                   const float* Pw, float* scratch, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
+/* ---- progressive distillation (Salimans & Ho, ICLR 2022, Algorithm 2): training an N-step sampler from a 2N-step one (csrc/distill.hip) ----
+ * The grid is the one of GeneralizedDDIM(..., "linear"): tau = linear_tau(T, 2N); student index i in 1..N stands for the timesteps
+ * t = tau[2i], m = tau[2i-1], e = tau[2i-2].  One training step: z_t = alpha_t x0 + sigma_t eps; the frozen teacher at (z_t, t) gives the x0
+ * estimate x1; one DDIM step z_m = alpha_m x1 + (sigma_m / sigma_t)(z_t - alpha_t x1); the teacher at (z_m, m) gives x2; the student
+ * regresses at (z_t, t) on the x~ for which ONE DDIM step from z_t lands where the teacher's second step does.  The paper's quotient
+ * (z_e - r z_t) / (alpha_e - r alpha_t), r = sigma_e / sigma_t, subtracts nearly equal numbers (1.3e-3 off in fp32 at T = 1000, N = 256) and
+ * is never formed, and neither is z_e: substituting the two steps gives x~ = w1 x1 + w2 x2, w1 = (s_m - s_t) / (s_e - s_t),
+ * w2 = (s_e - s_m) / (s_e - s_t), s = alpha / sigma, both positive with sum 1, (0, 1) where e = 0.
+ * rows: device fp32 table [N+1][12], folded by the host in float64 from alpha_bar and rounded once; row 0 is NaN; row i:
+ *   p0 p1    x1 = p0 o1 + p1 z_t    eps: (-sigma/alpha, 1/alpha), x0: (1, 0), v: (-sigma, alpha), all at t
+ *   p0' p1'  x2 = p0' o2 + p1' z_m  the same at m
+ *   m0 m1    z_m = m0 x1 + m1 z_t   m1 = sigma_m / sigma_t, m0 = alpha_m - m1 alpha_t
+ *   w1 w2    x~ = w1 x1 + w2 x2
+ *   q0 q1    target = q0 x~ + q1 z_t   eps: (-alpha/sigma, 1/sigma), x0: (1, 0), v: (-1/sigma, alpha/sigma), all at t
+ *   two spare floats (0)
+ * tt: device int64 table [N+1][2] = (t, m).  idx: int64[B] in DEVICE memory, one student index per image.  An index outside 1..N is never
+ * used as an address: its image comes out NaN.  Every product and sum is rounded to fp32 on its own (no fma).  16-byte accesses where
+ * chw % 4 == 0 and the image pointers are 16-byte aligned, element by element otherwise (any chw).
+ * dmme_distill_noise: z_t = (sqrt_abar[t] x0) + (sqrt_1m_abar[t] z) at t = tt[idx_b][0] - dmme_q_sample's x_t, the same bits - and the
+ *   two timestep vectors the teacher's forwards read, t_out[b] = t, m_out[b] = m (0 for a bad index); status[0] = 1 where an index lies
+ *   outside 1..N (never cleared here).
+ * dmme_distill_mid: x1 from the teacher's output out1 at (z_t, t), clamped to [-1, 1] iff clip; then z_m.
+ * dmme_distill_target: x1 by the same device function, x2 from out2 at (z_m, m) (clamped iff clip), x~ and the target of the
+ *   parameterisation: four reads, one write.  pred (DMME_PRED_*) names what the rows were folded for; the kernels read the rows only. */
+DMME_API int dmme_distill_noise(const float* x0, const float* z, const int64_t* idx, const int64_t* tt, const float* sqrt_abar, const float* sqrt_1m_abar,
+                                int N, int B, int64_t chw, float* z_t, int64_t* t_out, int64_t* m_out, int* status, void* stream);
+DMME_API int dmme_distill_mid(int pred, int clip, const float* z_t, const float* out1, const float* rows, const int64_t* idx, int N, int B, int64_t chw,
+                              float* z_m, void* stream);
+DMME_API int dmme_distill_target(int pred, int clip, const float* z_t, const float* out1, const float* z_m, const float* out2, const float* rows,
+                                 const int64_t* idx, int N, int B, int64_t chw, float* target, void* stream);
+
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
 
