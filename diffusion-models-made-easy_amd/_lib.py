@@ -21,6 +21,7 @@ CHAIN_DDPM_CFG, CHAIN_GDDIM_CFG = 6, 7  # classifier-free guidance: both halves 
 CHAIN_DPMPP, CHAIN_DPMPP_CFG = 8, 9  # DPM-Solver++(2M): tables of 8 floats per index, a history buffer, entry points of their own
 CHAIN_REPAINT = 10  # RePaint / SDEdit: tables of 8 floats per index, the known image and its mask, three normal streams per step
 CHAIN_ILVR = 11  # ILVR: tables of 8 floats per index, the reference image, two filter matrices, two normal streams per step; a plane-wise update
+CHAIN_DDNM = 12  # DDNM: tables of 8 floats per index, a measurement and its mask at measurement resolution, two normal streams per step; a cell-wise update
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2  # what the network predicts (include/dmme_hip.h: DMME_PRED_*)
 PREDICTIONS = {"eps": PRED_EPS, "x0": PRED_X0, "v": PRED_V}
 THRESHOLD_NONE, THRESHOLD_STATIC, THRESHOLD_DYNAMIC = 0, 1, 2  # x0 thresholding in front of the update (include/dmme_hip.h: DMME_THRESHOLD_*)
@@ -120,6 +121,11 @@ PROTOTYPES = {
     "dmme_ilvr_step": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_f), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dmme_chain_update_ilvr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dmme_ilvr_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_ddnm_band_capacity": (_i, []),
+    "dmme_ddnm_measure": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_ddnm_step": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_chain_update_ddnm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_ddnm_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "dmme_distill_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dmme_distill_mid": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "dmme_distill_target": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),

@@ -523,6 +523,12 @@ int launch_lowpass(const float* src, float* dst, int planes, int H, int W, const
 int launch_ilvr(const char* what, float* x, const float* model_out, const float* ref, const float* z2, const float* row, const float* Ph, const float* Pw,
                 float* scratch, const float* coef, const int64_t* t_table, void* state, int B, int C, int H, int W, int out_planes, int force_streaming,
                 hipStream_t s);
+// ddnm.hip: the DDNM update (the x0 prediction rectified against a measurement of the family M o Pool_s o Gray_g; kind DMME_CHAIN_DDNM has
+// no row in the table above: its update reduces over measurement cells) and the measurement on its own.  row: the eager form's 8 host
+// floats; coef / t_table / state: the chain form's; exactly one of the two is given.
+int launch_ddnm_measure(const float* x, const float* mask, float* y_out, int B, int C, int H, int W, int sc, int gray, hipStream_t s);
+int launch_ddnm(const char* what, float* x, const float* model_out, const float* y, const float* mask, const float* z2, const float* row, const float* coef,
+                const int64_t* t_table, void* state, int B, int C, int H, int W, int sc, int gray, int out_planes, hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient

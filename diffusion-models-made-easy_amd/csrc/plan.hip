@@ -1360,7 +1360,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 117; }  // 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 118; }  // 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1877,6 +1877,19 @@ DMME_API int dmme_ilvr_chain_step(const dmme_plan* plan, const void* packed, flo
         return rc;
     return launch_ilvr("ilvr_chain_step", x, model_out, ref, nullptr, nullptr, Ph, Pw, scratch, step_coef, t_table, state, plan->B, plan->cfg.in_channels, plan->H,
                        plan->W, planes, 0, (hipStream_t)stream);
+}
+
+// DDNM: kind DMME_CHAIN_DDNM, whose update reduces over measurement cells (csrc/ddnm.hip) behind the front half every chain step has
+DMME_API int dmme_ddnm_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* y, const float* mask,
+                                  int s, int gray, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && y && mask && step_coef && t_table && state, DMME_ERR_INVALID,
+                 "ddnm_chain_step: null argument");
+    int planes = 0;
+    if (int rc = chain_step_front("ddnm_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_DDNM, false, 0, nullptr, 8, 0, state,
+                                  stream, planes))
+        return rc;
+    return launch_ddnm("ddnm_chain_step", x, model_out, y, mask, nullptr, nullptr, step_coef, t_table, state, plan->B, plan->cfg.in_channels, plan->H, plan->W, s,
+                       gray, planes, (hipStream_t)stream);
 }
 
 // Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM): between the forward and the update, the classifier's forward, the log-softmax

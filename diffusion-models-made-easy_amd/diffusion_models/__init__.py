@@ -4,4 +4,5 @@ from .iddpm import IDDPM  # noqa: F401
 from .dpm_solver import DPMSolverPP  # noqa: F401
 from .repaint import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401
 from .ilvr import ILVR, LikeChainRunner, ilvr_rows, lowpass_matrix  # noqa: F401
+from .ddnm import DDNM, RestoreChainRunner, ddnm_rows  # noqa: F401
 from .distill import ProgressiveDistillation, distill_rows, distill_grid  # noqa: F401

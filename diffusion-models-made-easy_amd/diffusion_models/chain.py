@@ -37,6 +37,8 @@ def chain_draws(kind: int, rows) -> bool:
         return False
     if kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_GDDIM_CFG):
         return any(r[2] != 0.0 for r in rows)
+    if kind == _lib.CHAIN_DDNM:  # (cz of the posterior's noise, r1 of a folded jump)
+        return any(r[2] != 0.0 or r[7] != 0.0 for r in rows)
     return True
 
 

@@ -23,6 +23,7 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dpm++ --sample-steps 20   (DPM-Solver++(2M); any of the four configs)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler ilvr --image X.npy --down-factor 8 --save OUT.npy   (ILVR: samples that share X's coarse content)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler ddnm --measurement Y.npy --sr-scale 4 --save OUT.npy   (DDNM: 4x super-resolution of Y; --gray colourises, --mask inpaints)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3 --guidance-scale 2.5 --threshold dynamic   (x0 thresholding in front of the update: none | static | dynamic [--threshold-percentile P]; any sampler)
@@ -376,8 +377,8 @@ def _check_paint_args(args) -> None:
     """what goes with --sampler repaint / sdedit and what does not; exits with a message (before anything touches the GPU)"""
     given = [f for f, v in (("--image", args.image), ("--mask", args.mask), ("--strength", args.strength), ("--jump-length", args.jump_length),
                             ("--resamples", args.resamples)) if v is not None]
-    if args.sampler == "ilvr":
-        return  # (`_check_ilvr_args` has looked at all of these)
+    if args.sampler in ("ilvr", "ddnm"):
+        return  # (`_check_ilvr_args` / `_check_ddnm_args` have looked at all of these)
     if args.sampler not in PAINT_SAMPLERS:
         if given:
             raise SystemExit(f"{', '.join(given)} belong{'s' if len(given) == 1 else ''} to --sampler repaint / sdedit")
@@ -454,6 +455,68 @@ def _ilvr_process(module, args):
     return ILVR.from_process(old, sub_timesteps=sub, down_factor=args.down_factor or 4, range_level=r)
 
 
+def _check_ddnm_flags(args) -> None:
+    """the flags that only --sampler ddnm takes, in front of every check that opens a file"""
+    own = [f for f, v in (("--sr-scale", args.sr_scale), ("--gray", args.gray or None), ("--sigma-y", args.sigma_y), ("--measurement", args.measurement))
+           if v is not None]
+    if args.sampler != "ddnm" and own:
+        raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to --sampler ddnm")
+
+
+def _check_ddnm_args(args):
+    """what goes with --sampler ddnm and what does not; exits with a message (before anything touches the GPU).  Returns
+    (measurement or None, image or None, mask or None) for --sampler ddnm, else None."""
+    if args.sampler != "ddnm":
+        return None
+    name = "--sampler ddnm"
+    if args.command != "sample":
+        raise SystemExit(f"{name} belongs to `sample`: it restores images from a measurement with a trained network, training is the config's own")
+    for flag, v in (("--eta", args.eta), ("--steps", args.steps), ("--labels", args.labels), ("--guidance-scale", args.guidance_scale),
+                    ("--strength", args.strength)):
+        if v is not None:
+            raise SystemExit(f"{flag} does not go with {name}: it runs whole chains of an unconditional network (--sample-steps K sets the grid)")
+    if (args.measurement is None) == (args.image is None):
+        raise SystemExit(f"{name} needs exactly one of --measurement Y.npy (the degraded input) and --image X.npy (degraded here first: the demo path)")
+    if args.sample_steps is not None and args.sample_steps < 1:
+        raise SystemExit("--sample-steps must be at least 1")
+    S = 1 if args.sr_scale is None else args.sr_scale
+    if S < 1:
+        raise SystemExit("--sr-scale must be at least 1")
+    if args.sigma_y is not None and not args.sigma_y >= 0.0:
+        raise SystemExit("--sigma-y must be at least 0")
+    for flag, v in (("--jump-length", args.jump_length), ("--resamples", args.resamples)):
+        if v is not None and v < 1:
+            raise SystemExit(f"{flag} must be at least 1")
+    meas = image = None
+    if args.image is not None:
+        image = _load_npy(args.image, "--image")
+        H, W = image.shape[2:]
+        if H % S != 0 or W % S != 0:
+            raise SystemExit(f"--image {args.image}: the image size {H} x {W} is not divisible by --sr-scale {S}")
+        shape = (image.shape[0], 1 if args.gray else image.shape[1], H // S, W // S)
+    else:
+        meas = _load_npy(args.measurement, "--measurement")
+        if args.gray and meas.shape[1] != 1:
+            raise SystemExit(f"--measurement {args.measurement}: a --gray measurement has one channel, got {meas.shape[1]}")
+        shape = tuple(meas.shape)
+    mask = None if args.mask is None else _load_npy(args.mask, "--mask")
+    if mask is not None and (mask.shape[0] not in (1, shape[0]) or mask.shape[1] not in (1, shape[1]) or tuple(mask.shape[2:]) != shape[2:]):
+        raise SystemExit(f"--mask {args.mask}: shape {tuple(mask.shape)} does not broadcast to the measurement's {shape} (the mask is at measurement resolution)")
+    if mask is not None and not bool(((mask == 0) | (mask == 1)).all()):
+        raise SystemExit(f"--mask {args.mask}: values must be 0 or 1 (1: measured)")
+    return meas, image, mask
+
+
+def _ddnm_process(module, args):
+    """DDNM over the network and the noise schedule of the process the YAML built"""
+    from .diffusion_models import DDNM
+
+    old = module.diffusion_model
+    sub = min(100, old.timesteps) if args.sample_steps is None else args.sample_steps
+    return DDNM.from_process(old, sub_timesteps=sub, scale=args.sr_scale or 1, gray=bool(args.gray), sigma_y=args.sigma_y or 0.0,
+                             travel_length=args.jump_length or 1, travel_repeat=args.resamples or 1)
+
+
 def _load_npy(path: str, what: str) -> torch.Tensor:
     """a float image array (B, C, H, W) or (C, H, W) from a .npy file, as a 4-D fp32 tensor"""
     import numpy as np
@@ -492,11 +555,13 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
-    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr"],
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr", "ddnm"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table; "
                          "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20); "
                          "'repaint' inpaints --image where --mask is 0, 'sdedit' edits --image at --strength (any unconditional config; --sample-steps: grid levels, default 250); "
-                         "'ilvr' samples images that share the low frequencies of --image (any unconditional config; --down-factor N, --range-level R, --sample-steps)")
+                         "'ilvr' samples images that share the low frequencies of --image (any unconditional config; --down-factor N, --range-level R, --sample-steps); "
+                         "'ddnm' restores images from --measurement (or from --image, degraded first): super-resolution --sr-scale S, colourisation --gray, "
+                         "inpainting --mask, a noisy measurement --sigma-y (any unconditional config; --sample-steps, default 100; --jump-length / --resamples: time travel)")
     ap.add_argument("--image", default=None, help="sample --sampler repaint / sdedit: .npy, float32 in [-1, 1], (B, C, H, W) or (C, H, W)")
     ap.add_argument("--mask", default=None, help="sample --sampler repaint (needed) / sdedit (optional): .npy broadcastable to the image, 1 = keep the pixel, 0 = generate")
     ap.add_argument("--strength", type=float, default=None, help="sample --sampler sdedit: in (0, 1], the share of the noise levels the guide is pushed up before it is denoised")
@@ -504,6 +569,10 @@ def main(argv=None):
     ap.add_argument("--resamples", type=int, default=None, help="sample --sampler repaint: times each stretch of --jump-length levels is walked (default 10)")
     ap.add_argument("--down-factor", type=int, default=None, help="sample --sampler ilvr: N of the low-pass filter, at least 2 and a divisor of the image size (default 4); small N stays close to --image")
     ap.add_argument("--range-level", type=int, default=None, help="sample --sampler ilvr: steps that end below this grid level are not conditioned (default 0: every step is)")
+    ap.add_argument("--measurement", default=None, help="sample --sampler ddnm: .npy, the degraded input (B, Cm, h, w) or (Cm, h, w), float32 in [-1, 1]")
+    ap.add_argument("--sr-scale", type=int, default=None, help="sample --sampler ddnm: s of the s x s average pooling the measurement went through (default 1: none); a divisor of the image size")
+    ap.add_argument("--gray", action="store_true", help="sample --sampler ddnm: the measurement is the mean of the channels (colourisation)")
+    ap.add_argument("--sigma-y", type=float, default=None, help="sample --sampler ddnm: the noise level of the measurement (default 0); with --image, noise of this level is added to the degraded image")
     ap.add_argument("--save", default=None, help="sample: write the images to this .npy file (float32, (B, C, H, W))")
     ap.add_argument("--grid", default=None, help="sample: write the images to this PNG file as a grid (every sampler; goes with --save)")
     ap.add_argument("--vis-length", type=int, default=1,
@@ -535,7 +604,9 @@ def main(argv=None):
     _check_solver_args(args)
     _check_distill_args(args)
     _check_threshold_args(args)
+    _check_ddnm_flags(args)
     ilvr_image = _check_ilvr_args(args)
+    ddnm_inputs = _check_ddnm_args(args)
     _check_paint_args(args)
     if args.save is not None and args.command != "sample":
         raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
@@ -564,6 +635,10 @@ def main(argv=None):
         if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
             raise SystemExit("--sampler ilvr needs an unconditional config: guided ILVR is not implemented")
         image = ilvr_image
+    elif args.sampler == "ddnm":
+        if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+            raise SystemExit("--sampler ddnm needs an unconditional config: guided DDNM is not implemented")
+        measurement, image, mask = ddnm_inputs
     elif args.sample_steps is not None and args.sampler != "dpm++":
         from .lit_modules import LitIDDPM
 
@@ -619,6 +694,8 @@ def main(argv=None):
             module.diffusion_model = _paint_process(module, args).cuda()
         elif args.sampler == "ilvr":
             module.diffusion_model = _ilvr_process(module, args).cuda()
+        elif args.sampler == "ddnm":
+            module.diffusion_model = _ddnm_process(module, args).cuda()
         module.eval()
         dm = module.diffusion_model
         if args.threshold is not None:
@@ -627,6 +704,14 @@ def main(argv=None):
         hw = args.image_size or conf["image_size"]
         shape = (args.num_images, dm.model.in_channels, hw, hw)
         rec = None
+        if args.sampler == "ddnm":
+            if image is not None:  # (the demo path: the measurement is made here, with noise of the level the sampler is told)
+                import dmme_amd
+
+                measurement = dm.degrade(image, mask)
+                if dm.sigma_y > 0.0:
+                    measurement = measurement + dm.sigma_y * dmme_amd.gaussian(tuple(measurement.shape), device=measurement.device)
+            restored_shape = (measurement.shape[0], dm._channels(measurement.shape[1]), measurement.shape[2] * dm.scale, measurement.shape[3] * dm.scale)
         if args.grid is not None:
             from .diffusion_models import HistoryRecorder, history_ordinals
 
@@ -636,7 +721,7 @@ def main(argv=None):
                 count = dm._respaced_tables(args.sample_steps)[0]  # (Improved DDPM's strided chain)
             else:
                 count = dm.chain_length()
-            rec_shape = tuple(image.shape) if args.sampler in PAINT_SAMPLERS + ("ilvr",) else shape
+            rec_shape = restored_shape if args.sampler == "ddnm" else tuple(image.shape) if args.sampler in PAINT_SAMPLERS + ("ilvr",) else shape
             rec = HistoryRecorder(rec_shape[0], *rec_shape[1:], history_ordinals(count, args.vis_length), out_kind=1)
         if args.sampler == "repaint":
             imgs = dm.inpaint(image, mask, history=rec)
@@ -644,6 +729,8 @@ def main(argv=None):
             imgs = dm.edit(image, args.strength, mask, history=rec)
         elif args.sampler == "ilvr":
             imgs = dm.sample_like(image, history=rec)
+        elif args.sampler == "ddnm":
+            imgs = dm.restore(measurement, mask, history=rec)
         elif getattr(module, "conditional", False):
             if args.steps is not None or args.sampler == "ddim-paper" or (args.sample_steps is not None and args.sampler != "dpm++"):
                 raise SystemExit("class-conditional configs sample whole chains: --labels / --guidance-scale only")

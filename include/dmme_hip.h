@@ -422,7 +422,7 @@ DMME_API int dmme_pred_to_eps(int pred, float* model_out, const float* x, const 
 
 /* host-only state of a plan: what its network predicts.  With DMME_PRED_X0 / DMME_PRED_V every capturable step over the plan
  * (dmme_chain_step, dmme_cfg_chain_step, dmme_dpmpp_chain_step, dmme_cfg_dpmpp_chain_step, dmme_repaint_chain_step,
- * dmme_ilvr_chain_step, dmme_guided_chain_step) launches dmme_pred_to_eps(pred, model_out, x, ab, T, &state.t, 1, plan batch, C*H*W) directly behind the
+ * dmme_ilvr_chain_step, dmme_ddnm_chain_step, dmme_guided_chain_step) launches dmme_pred_to_eps(pred, model_out, x, ab, T, &state.t, 1, plan batch, C*H*W) directly behind the
  * forward - over all 2B images of a classifier-free plan: the mixing weights 1 - s and s sum to one, so the affine map commutes
  * with e_u + s (e_c - e_u) - and in front of the classifier pass and the update.  `ab` stays the caller's and must outlive every launch and
  * every captured graph that holds its address.  A plan is shared by every process that wraps the same network: set the prediction in
@@ -725,6 +725,57 @@ DMME_API int dmme_chain_update_ilvr(float* x, const float* model_out, const floa
                                     int force_streaming, void* stream);
 DMME_API int dmme_ilvr_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* ref, const float* Ph,
                                   const float* Pw, float* scratch, const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
+/* ---- DDNM (Wang, Yu, Zhang 2023): zero-shot restoration from a measurement y = A x (csrc/ddnm.hip) ------------------------------------
+ * The operator family is A = M o Pool_s o Gray_g on images (B, C, H, W): Gray_g the mean over the C channels where gray = 1 (Cm = 1),
+ * the identity where gray = 0 (Cm = C); Pool_s the mean over s x s blocks, to (B, Cm, h, w) = (B, Cm, H/s, W/s), s >= 1 a divisor of H
+ * and W; M a binary mask at measurement resolution, 1 = measured.  A cell is the n = (C if gray else 1) s s image elements one
+ * measurement value averages; the pseudo-inverse A+ y gives every element of a cell the value m y of the cell (A A+ A = A holds for a
+ * binary mask only).  Grid and levels as RePaint's, the walk that of repaint_levels ("time travel"); a downward transition
+ * a -> b = a - 1 is one network evaluation and one table row (DDNM+, eq. 17-19 of the paper; alpha = abar_a / abar_b, beta = 1 - alpha):
+ *     x0 = (A_t x) - (B_t e)                                         rounded like dmme_x0_threshold's x0
+ *     r  = mean_cell(x0) - y   where the cell's m != 0, else 0       one value per cell; y is not looked at where m == 0
+ *     xh = x0 - lambda r
+ *     u  = ca xh;   u = u + cb x   only where cb != 0;   u = u + cz z0   only where cz != 0
+ *     x' = u, or (r0 u) + (r1 z1)  only where r1 != 0                the walk's next upward run b -> c folded into one Gaussian, as RePaint's
+ * Kind DMME_CHAIN_DDNM = 12 has entry points and a table layout of its own and no row in the kind table of the elementwise updates:
+ * dmme_chain_step and dmme_chain_update refuse it.
+ *   step_coef float[n_rows+1][8], per loop index, with sigma_y the noise level of the measurement, var = beta (1 - abar_b)/(1 - abar_a):
+ *             {ca = sqrt(abar_b) beta/(1 - abar_a), cb = sqrt(alpha) (1 - abar_b)/(1 - abar_a), cz = sqrt(max(var - (ca lambda sigma_y)^2, 0)),
+ *              A_t = 1/sqrt(abar_a), B_t = sqrt(1 - abar_a)/sqrt(abar_a), lambda = 1 where sigma_y = 0 or sqrt(var) >= ca sigma_y, else
+ *              sqrt(var)/(ca sigma_y), r0 = sqrt(abar_c / abar_b), r1 = sqrt(1 - abar_c / abar_b) (1, 0 where no upward run follows)};
+ *             for b = 0 the row is exactly {1, 0, 0, A_t, B_t, lambda, 1, 0}: the last step returns xh bit for bit.  The host builds the
+ *             rows in float64 and rounds them once.
+ *   t_table   int64[n_rows+1]: t_table[i] = tau_a; t_table[0] = 0
+ *   y, mask   fp32, (B, Cm, h, w) contiguous, read only; the mask's values are 0 or 1
+ *   rounding  every product, sum and difference is rounded to fp32 on its own (no fma).  A cell's mean is ONE chain: acc = the cell's
+ *             first element, acc = acc + next in the order (channel,) row, column, then acc / n correctly rounded - in one device
+ *             function that dmme_ddnm_measure and both update forms call.  Hence |mean - exact| <= (n + 1) 2^-24 max|element|, the
+ *             same bits from every entry point, whatever B and the image's place in the batch.
+ *   normals   a step owns TWO streams of B*chw normals: stream s of the quad at element g is the draw at Philox counter
+ *             offset + s * (B*chw/4) + g/4, so dmme_randn(z2, 2*B*chw, seed, offset) writes exactly the [2][B*chw] block the eager form
+ *             reads.  A stream whose coefficient (cz, r1) is zero is neither drawn nor read.  The chain form moves the offset by
+ *             2 * B*chw/4 per step whatever the row used.
+ *   forms     quad (n == 1, plain inpainting): elementwise, no LDS.  Band (every other case): one workgroup per image and band of s rows
+ *             across all C channels, x0 staged in LDS, one launch; in place is safe because a band is read completely before it is
+ *             written.  A band holds C*s*W values, at most dmme_ddnm_band_capacity() (3 x 32 x 256 fits); a larger one is refused with
+ *             DMME_ERR_UNSUPPORTED, as is a band whose staging with one residual per cell exceeds 159 KiB of LDS.
+ *   out_planes  1 (eps), or 2 (an IDDPM network's (eps, v): the eps plane is used).
+ * W (and with it C*H*W) must be a multiple of 4 (DMME_ERR_UNSUPPORTED otherwise).  dmme_ddnm_measure: y_out = A x (mask nullable: all
+ * measured; an unmeasured cell gives 0).  dmme_ddnm_step: the eager twin (row: 8 floats in HOST memory; z2: the [2][B*chw] block,
+ * nullable only where the row uses no stream), bit-identical to dmme_chain_update_ddnm, the chain form (row from device memory at
+ * step_coef[8 i], normals drawn in the kernel; noise: nullable, a [2][B*chw] block used in place of the drawn normals - tests).
+ * dmme_ddnm_chain_step = dmme_unet_forward (no-grad form) at t = state.t, the x0 / v adapter and x0 thresholding as every chain step has
+ * them, then dmme_chain_update_ddnm; an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan. */
+enum { DMME_CHAIN_DDNM = 12 };
+DMME_API int dmme_ddnm_band_capacity(void);
+DMME_API int dmme_ddnm_measure(const float* x, const float* mask, float* y_out, int B, int C, int H, int W, int s, int gray, void* stream);
+DMME_API int dmme_ddnm_step(float* x, const float* model_out, const float* y, const float* mask, const float* z2, const float* row, int B, int C, int H, int W,
+                            int s, int gray, int out_planes, void* stream);
+DMME_API int dmme_chain_update_ddnm(float* x, const float* model_out, const float* y, const float* mask, const float* noise, const float* step_coef,
+                                    const int64_t* t_table, void* state, int B, int C, int H, int W, int s, int gray, int out_planes, void* stream);
+DMME_API int dmme_ddnm_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* y, const float* mask,
+                                  int s, int gray, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
 /* ---- progressive distillation (Salimans & Ho, ICLR 2022, Algorithm 2): training an N-step sampler from a 2N-step one (csrc/distill.hip) ----
  * The grid is the one of GeneralizedDDIM(..., "linear"): tau = linear_tau(T, 2N); student index i in 1..N stands for the timesteps
