@@ -24,6 +24,7 @@ CHAIN_ILVR = 11  # ILVR: tables of 8 floats per index, the reference image, two 
 CHAIN_DDNM = 12  # DDNM: tables of 8 floats per index, a measurement and its mask at measurement resolution, two normal streams per step; a cell-wise update
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2  # what the network predicts (include/dmme_hip.h: DMME_PRED_*)
 PREDICTIONS = {"eps": PRED_EPS, "x0": PRED_X0, "v": PRED_V}
+CM_METRICS = {"pseudo-huber": 0, "l2": 1}  # the consistency loss's metric (include/dmme_hip.h: DMME_CM_*)
 THRESHOLD_NONE, THRESHOLD_STATIC, THRESHOLD_DYNAMIC = 0, 1, 2  # x0 thresholding in front of the update (include/dmme_hip.h: DMME_THRESHOLD_*)
 THRESHOLDS = {"none": THRESHOLD_NONE, "static": THRESHOLD_STATIC, "dynamic": THRESHOLD_DYNAMIC}
 ARCH_DDPM, ARCH_IDDPM, ARCH_CLASSIFIER, ARCH_DDPM_COND = 0, 1, 2, 3
@@ -129,6 +130,9 @@ PROTOTYPES = {
     "dmme_distill_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dmme_distill_mid": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "dmme_distill_target": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "dmme_cm_target": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "dmme_cm_loss": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _f, _vp, _vp, _vp, _f, _vp, _vp]),
+    "dmme_ema_lerp": (_i, [_vp, _vp, _i64, _f, _vp]),
     "dmme_unet_plan_num_ops": (_i, [_vp]),
     "dmme_unet_plan_level_info": (_i, [_vp, C.c_char_p, _i]),
     "dmme_unet_plan_check": (_i, [_vp]),

@@ -161,3 +161,40 @@ def iddpm_loss_rows_apply(model_out: Tensor, x_t: Tensor, x_0: Tensor, target: T
         weight = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
     return _IDDPMLossRowsFunction.apply(model_out, x_t, x_0, target, t, coef.to(device=dev, dtype=torch.float32).contiguous(), timesteps, weight,
                                         w_simple, w_vlb, status)
+
+
+class _ConsistencyLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out: Tensor, z_t: Tensor, f_target: Tensor, rows: Tensor, idx: Tensor, steps: int, metric: int, c: float):
+        o = out.detach().to(torch.float32).contiguous()
+        B = o.size(0)
+        loss = torch.empty(1, dtype=torch.float32, device=o.device)
+        scratch = torch.empty(65 * B, dtype=torch.float32, device=o.device)
+        d_out = torch.empty_like(o) if out.requires_grad else None
+        _lib.check(_lib.lib().dmme_cm_loss(int(metric), _lib.ptr(z_t), _lib.ptr(o), _lib.ptr(f_target), _lib.ptr(rows), _lib.ptr(idx), int(steps), B, o[0].numel(),
+                                           float(c), _lib.ptr(loss), _lib.ptr(None), _lib.ptr(d_out), 1.0, _lib.ptr(scratch), _lib.stream_ptr()), "dmme_cm_loss")
+        ctx.d_out = d_out
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor):
+        d = ctx.d_out
+        ctx.d_out = None
+        return (d * grad_out if d is not None else None), None, None, None, None, None, None, None
+
+
+def consistency_loss_apply(out: Tensor, z_t: Tensor, f_target: Tensor, rows: Tensor, idx: Tensor, steps: int, metric: int, c: float) -> Tensor:
+    """the consistency-distillation loss (1/B) sum_b d(f(z_t, t; out)_b, f_target_b) with a HIP gradient with respect to the student's raw
+    output `out` (dmme_cm_loss): f is the boundary-conditioned consistency function of the table row of image b's grid index, d the
+    pseudo-Huber metric (metric 0, constant c > 0) or the per-image mean of squares (metric 1).  rows: the fp32 device table
+    [steps+1][12] of diffusion_models.consistency_rows; idx: one grid index per image (an index outside 1..steps gives a NaN loss)."""
+    dev = out.device
+    if z_t.shape != out.shape or f_target.shape != out.shape or idx.numel() != out.shape[0]:
+        raise ValueError(f"consistency_loss_apply: output {tuple(out.shape)}, images {tuple(z_t.shape)}, target {tuple(f_target.shape)}, {idx.numel()} indices")
+    if rows.numel() != 12 * (int(steps) + 1):
+        raise ValueError(f"consistency_loss_apply: a table of {rows.numel()} floats for {steps} steps")
+    if not idx.is_cuda and idx.numel() and not (1 <= int(idx.min()) and int(idx.max()) <= int(steps)):
+        raise ValueError(f"consistency_loss_apply: a grid index outside 1..{int(steps)}")
+    prep = lambda v: v.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    return _ConsistencyLossFunction.apply(out, prep(z_t), prep(f_target), prep(rows).reshape(-1), idx.detach().reshape(-1).to(device=dev, dtype=torch.int64).contiguous(),
+                                          int(steps), int(metric), float(c))

@@ -24,6 +24,9 @@ def checkpoint_dict(module, optimizer=None, scheduler=None, global_step: int = 0
     meta = getattr(getattr(module, "diffusion_model", None), "distill_meta", None)
     if callable(meta):  # a progressively distilled student: the steps and the grid it samples on, for `trainer sample`
         ckpt["distill"] = meta()
+    meta = getattr(getattr(module, "diffusion_model", None), "consistency_meta", None)
+    if callable(meta):  # a consistency-distilled student: the training grid and the boundary scalings, for `trainer sample`
+        ckpt["consistency"] = meta()
     if optimizer is not None:
         sd = optimizer.state_dict()
         to_cpu = lambda t: t.detach().cpu() if torch.is_tensor(t) else t  # noqa: E731

@@ -5,34 +5,13 @@
 // z_e).  All HBM-bound, fp32, NCHW.  Like prediction.hip the translation unit is compiled with -ffp-contract=off (csrc/Makefile) and every
 // product and sum below is explicitly rounded on its own (never an fma): z_t carries dmme_q_sample's bits, and a numpy float32
 // restatement reproduces the rest bit for bit.
-#include "plan.h"
+#include "distill_dev.h"  // distill_index, distill_pair, distill_axpby, distill_x0: shared with consistency.hip
 
 namespace dmme {
 
 static inline unsigned grid_for(int64_t work) {
     int64_t b = (work + 255) / 256;
     return (unsigned)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
-constexpr int kDistillRow = 12;  // floats per row of the table: p0 p1 | p0' p1' | m0 m1 | w1 w2 | q0 q1 | two spare
-
-// the student index of image b, or 0 where it lies outside 1..N: index 0 stands for "no row" (the table's row 0 is NaN)
-__device__ __forceinline__ int64_t distill_index(const int64_t* __restrict__ idx, int N, int64_t b) {
-    const int64_t i = idx[b];
-    return (i < 1 || i > N) ? 0 : i;
-}
-// slots k, k + 1 of row i.  Index 0 is never used as an address: its pair comes out NaN.
-__device__ __forceinline__ float2 distill_pair(const float* __restrict__ rows, int64_t i, int k) {
-    if (i == 0) return make_float2(__builtin_nanf(""), __builtin_nanf(""));
-    return make_float2(rows[kDistillRow * i + k], rows[kDistillRow * i + k + 1]);
-}
-__device__ __forceinline__ float distill_axpby(float2 c, float a, float b) { return __fadd_rn(__fmul_rn(c.x, a), __fmul_rn(c.y, b)); }
-// the teacher's x0 estimate from its output o at the image z it saw: p.x o + p.y z, clamped to [-1, 1] iff clip (a NaN stays a NaN).
-// distill_mid and distill_target both form x1 here, so the target's x1 is the one z_m was built from.
-__device__ __forceinline__ float distill_x0(float2 p, float o, float z, int clip) {
-    const float x = distill_axpby(p, o, z);
-    if (!clip) return x;
-    return x < -1.f ? -1.f : (x > 1.f ? 1.f : x);
 }
 
 // ------------------------------------------------------------------ z_t at t = tt[idx][0], and the timestep vectors of the two forwards

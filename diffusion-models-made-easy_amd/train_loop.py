@@ -86,7 +86,10 @@ def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=N
         from .checkpoint import load_checkpoint
 
         first = int(load_checkpoint(ckpt_path, module, opt, sched).get("global_step", 0))
+        if hasattr(module.diffusion_model, "reset_target"):
+            module.diffusion_model.reset_target()  # (consistency distillation: the target network is not in a checkpoint and restarts from the student)
     model = module.diffusion_model.model
+    after_step = getattr(module.diffusion_model, "after_step", None)  # (consistency distillation: the target network's moving average)
     if D.sync_parameters(model, opt):  # several ranks: start from rank 0's weights (after a resume too)
         model._dp_synced = True
     t0 = time.perf_counter()
@@ -108,6 +111,8 @@ def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=N
             if conditional:
                 y = batch[1]
         loss = train_step(module, opt, sched, x0, clip, y=y)
+        if after_step is not None:
+            after_step()
         if preview is not None and (step + 1) % preview[2] == 0 and D.env_rank_world()[0] == 0:
             print(json.dumps({"step": step + 1, "preview": write_preview(module, preview[0], preview[1], step + 1)}), flush=True)
         if (step + 1) % log_every == 0 or step + 1 == max_steps:
@@ -116,6 +121,8 @@ def fit(module, batch_size=128, max_steps=100, clip=None, log_every=50, loader=N
                 model.check_engine()  # a level-engine hand-off that timed out since the last log line: stop, do not train on it
             if conditional:
                 model.check_labels()  # a label outside [0, num_classes] that reached the device since the last log line
+            if after_step is not None:
+                module.diffusion_model.check_indices()  # a grid index outside 1..N that reached the device since the last log line
             dt = time.perf_counter() - t0
             print(json.dumps({"step": step + 1, "train/loss": round(float(loss.detach()), 5), "images_per_s": round((step + 1 - first) * batch_size / dt, 1)}), flush=True)
     if save_path and D.env_rank_world()[0] == 0:

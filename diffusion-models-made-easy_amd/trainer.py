@@ -32,6 +32,9 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer distill --config configs/vpred/cifar10.yaml --ckpt-path TEACHER.ckpt --distill-from 1024 --distill-to 4 --stage-steps 50000 --save-checkpoint OUT.ckpt
                                     (progressive distillation: a teacher sampled in 1024 DDIM steps becomes a 4-step student, one halving per stage; [--clip-x0] [--data config])
   python -m dmme_amd.trainer sample --config configs/vpred/cifar10.yaml --ckpt-path OUT.ckpt   (a distilled checkpoint samples with the steps and the grid it was trained for)
+  python -m dmme_amd.trainer consistency --config configs/vpred/cifar10.yaml --ckpt-path TEACHER.ckpt --consistency-steps 50 --max-steps M --save-checkpoint OUT.ckpt
+                                    (consistency distillation: one run, then 1-, 2- or 4-step samples; [--metric l2] [--huber-c C] [--target-decay 0.95] [--clip-x0] [--data config])
+  python -m dmme_amd.trainer sample --config configs/vpred/cifar10.yaml --ckpt-path OUT.ckpt --sample-steps 2   (a consistency checkpoint samples in K steps, K a divisor of its grid; default 1)
 """
 
 from __future__ import annotations
@@ -258,7 +261,7 @@ def _check_solver_args(args) -> None:
     # (--tau-schedule linear / quadratic also goes with --sampler ddim-paper: the grid of GeneralizedDDIM; --clip-x0 also with `distill`)
     paper_tau = args.sampler == "ddim-paper" and args.tau_schedule in ("linear", "quadratic")
     solver_flags = [f for f, given in (("--solver-order", args.solver_order is not None), ("--tau-schedule", args.tau_schedule is not None and not paper_tau),
-                                       ("--clip-x0", args.clip_x0 and args.command != "distill")) if given]
+                                       ("--clip-x0", args.clip_x0 and args.command not in ("distill", "consistency"))) if given]
     if args.sampler != "dpm++":
         if solver_flags:
             raise SystemExit(f"{', '.join(solver_flags)} belong{'s' if len(solver_flags) == 1 else ''} to --sampler dpm++")
@@ -315,6 +318,72 @@ def _check_distill_args(args) -> None:
         raise SystemExit("--stage-steps must be at least 1")
 
 
+CONSISTENCY_FLAGS = (("--consistency-steps", "consistency_steps"), ("--metric", "metric"), ("--huber-c", "huber_c"), ("--target-decay", "target_decay"))
+
+
+def _check_consistency_args(args) -> None:
+    """what goes with `consistency` and what does not; exits with a message (before anything touches the GPU)"""
+    given = [f for f, name in CONSISTENCY_FLAGS if getattr(args, name) is not None]
+    if args.command != "consistency":
+        if given:
+            raise SystemExit(f"{', '.join(given)} belong{'s' if len(given) == 1 else ''} to `consistency`")
+        return
+    if args.consistency_steps is None or args.max_steps is None:
+        raise SystemExit("consistency needs --consistency-steps N (the training grid) and --max-steps M (the optimiser steps of its one run)")
+    if args.ckpt_path is None:
+        raise SystemExit("consistency needs --ckpt-path TEACHER.ckpt: the trained network that is distilled")
+    if args.save_checkpoint is None:
+        raise SystemExit("consistency needs --save-checkpoint OUT.ckpt: the student is its only result")
+    if args.sampler != "config" or args.sample_steps is not None:
+        raise SystemExit("--sampler / --sample-steps do not go with `consistency`: `sample --ckpt-path OUT.ckpt --sample-steps K` samples its student")
+    if args.consistency_steps < 1 or args.max_steps < 1:
+        raise SystemExit("--consistency-steps and --max-steps must be at least 1")
+    if args.huber_c is not None and (args.metric == "l2" or not args.huber_c > 0.0):
+        raise SystemExit("--huber-c C > 0 belongs to the pseudo-Huber metric")
+    if args.target_decay is not None and not 0.0 <= args.target_decay <= 1.0:
+        raise SystemExit(f"--target-decay {args.target_decay} outside [0, 1]")
+
+
+def _consistency(args, conf, B, rank_seed=None) -> int:
+    """`consistency`: the YAML's network twice (teacher and student, both from --ckpt-path), then one run of train_loop.fit"""
+    from .checkpoint import load_checkpoint
+    from .diffusion_models import ConsistencyDistillation
+    from .lit_modules import LitConsistency
+    from .train_loop import fit
+
+    if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+        raise SystemExit("consistency needs an unconditional config: guided consistency distillation is out of scope")
+    built = []
+    for _ in range(2):
+        module = build_module(conf).cuda()
+        load_checkpoint(args.ckpt_path, module, strict=False)
+        built.append(module)
+    if rank_seed is not None:
+        torch.manual_seed(rank_seed)
+    old = built[0].diffusion_model
+    try:
+        process = ConsistencyDistillation(built[1].diffusion_model.model, old.model, old.timesteps, args.consistency_steps, prediction=old.prediction,
+                                          clip_x0=args.clip_x0, metric=args.metric or "pseudo-huber", huber_c=args.huber_c,
+                                          target_decay=args.target_decay or 0.0).cuda()
+    except (NotImplementedError, ValueError) as exc:
+        raise SystemExit(str(exc))
+    lit = LitConsistency(process, lr=built[0].lr).cuda()
+    loader = None
+    if args.data == "config" and conf["data_spec"]:
+        data = _instantiate(conf["data_spec"])
+        data.batch_size = B
+        try:
+            data.prepare_data()
+        except FileNotFoundError as e:
+            print(json.dumps({"data": "random bytes (dataset files absent)", "reason": str(e)[:160]}), flush=True)
+            data.synthetic = True
+        data.setup("fit")
+        loader = data.train_dataloader()
+    fit(lit, batch_size=B, max_steps=args.max_steps, clip=conf["gradient_clip_val"], log_every=conf["log_every_n_steps"], loader=loader,
+        save_path=args.save_checkpoint)
+    return 0
+
+
 def _distill(args, conf, B, rank_seed=None) -> int:
     """`distill`: the YAML's network twice (teacher and student, both from --ckpt-path), then the stages of train_loop.fit_distill"""
     from .checkpoint import load_checkpoint
@@ -354,6 +423,17 @@ def _distill(args, conf, B, rank_seed=None) -> int:
     fit_distill(lit, args.distill_from // 2, args.distill_to, args.stage_steps, batch_size=B, clip=conf["gradient_clip_val"], log_every=conf["log_every_n_steps"],
                 loader=loader, save_path=args.save_checkpoint)
     return 0
+
+
+def _consistency_entry(args, conf):
+    """the "consistency" entry of the checkpoint `sample` is given, or None (read on the host, before anything touches the GPU)"""
+    path = args.ckpt_path or conf.get("ckpt_path")
+    if not path:
+        return None
+    try:
+        return torch.load(path, map_location="cpu", weights_only=False).get("consistency")
+    except (OSError, RuntimeError, AttributeError):
+        return None
 
 
 def _dpm_solver(module, args):
@@ -543,7 +623,7 @@ def _paint_process(module, args):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="dmme_amd.trainer")
-    ap.add_argument("command", choices=["fit", "sample", "distill"])
+    ap.add_argument("command", choices=["fit", "sample", "distill", "consistency"])
     ap.add_argument("--config", required=True)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
@@ -596,6 +676,11 @@ def main(argv=None):
     ap.add_argument("--distill-from", type=int, default=None, help="distill: the DDIM steps the teacher is sampled in (the first student takes half)")
     ap.add_argument("--distill-to", type=int, default=None, help="distill: the steps of the last student; --distill-from is this times a power of two")
     ap.add_argument("--stage-steps", type=int, default=None, help="distill: optimiser steps of every halving stage (the rate falls linearly to zero within each)")
+    ap.add_argument("--consistency-steps", type=int, default=None, help="consistency: N of the training grid linear_tau(T, N); the student samples in any K that divides it")
+    ap.add_argument("--metric", default=None, choices=["pseudo-huber", "l2"], help="consistency: the loss's metric per image (default pseudo-huber)")
+    ap.add_argument("--huber-c", type=float, default=None, help="consistency: c of the pseudo-Huber metric (default 0.00054 sqrt(C H W))")
+    ap.add_argument("--target-decay", type=float, default=None,
+                    help="consistency: 0 (default) the target network is the student itself; in (0, 1] a third network that follows the student at this moving-average rate")
     ap.add_argument("--threshold", default=None, choices=["none", "static", "dynamic"],
                     help="sample, every sampler: clip the x0 each noise prediction implies, in front of the update - static: to [-1, 1] (clip_denoised); "
                          "dynamic: to the image's --threshold-percentile quantile of |x0| where above 1, rescaled (wanted with --guidance-scale above 1)")
@@ -603,6 +688,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     _check_solver_args(args)
     _check_distill_args(args)
+    _check_consistency_args(args)
     _check_threshold_args(args)
     _check_ddnm_flags(args)
     ilvr_image = _check_ilvr_args(args)
@@ -639,6 +725,8 @@ def main(argv=None):
         if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
             raise SystemExit("--sampler ddnm needs an unconditional config: guided DDNM is not implemented")
         measurement, image, mask = ddnm_inputs
+    elif args.sample_steps is not None and args.sampler == "config" and args.command == "sample" and args.steps is None and _consistency_entry(args, conf) is not None:
+        pass  # (a consistency checkpoint: --sample-steps K is the K of its sampler)
     elif args.sample_steps is not None and args.sampler != "dpm++":
         from .lit_modules import LitIDDPM
 
@@ -657,6 +745,8 @@ def main(argv=None):
     torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
     seed = conf["seed"] if isinstance(conf["seed"], int) and not isinstance(conf["seed"], bool) else 1337
     torch.manual_seed(seed)  # identical initial weights on every rank ...
+    if args.command == "consistency":
+        return _consistency(args, conf, args.batch_size or conf["batch_size"], D.rank_seed(seed, rank) if world > 1 else None)
     if args.command == "distill":
         # (builds the YAML's network twice, teacher and student; several ranks: each draws from its own stream afterwards, as below)
         return _distill(args, conf, args.batch_size or conf["batch_size"], D.rank_seed(seed, rank) if world > 1 else None)
@@ -666,14 +756,27 @@ def main(argv=None):
     B = args.batch_size or conf["batch_size"]
 
     ckpt_path = args.ckpt_path or conf.get("ckpt_path")
-    distilled = None
+    distilled = consistency = None
     if args.command == "sample":
         if ckpt_path:
             from .checkpoint import load_checkpoint
 
-            distilled = load_checkpoint(ckpt_path, module, strict=False).get("distill")
+            ckpt = load_checkpoint(ckpt_path, module, strict=False)
+            distilled, consistency = ckpt.get("distill"), ckpt.get("consistency")
         if args.sampler != "config" or args.sample_steps is not None:
             distilled = None  # (an explicit sampler wins over the checkpoint's)
+        if args.sampler != "config":
+            consistency = None
+        if consistency is not None:
+            from .diffusion_models import ConsistencySampler
+
+            old = module.diffusion_model
+            try:
+                module.diffusion_model = ConsistencySampler(old.model, old.timesteps, args.sample_steps or 1, int(consistency["steps"]),
+                                                            prediction=consistency.get("prediction", old.prediction), sigma_data=consistency.get("sigma_data", 0.5),
+                                                            timestep_scaling=consistency.get("timestep_scaling", 10.0)).cuda()
+            except ValueError as exc:
+                raise SystemExit(str(exc))
         if distilled is not None:
             from .diffusion_models import GeneralizedDDIM
 
@@ -717,7 +820,7 @@ def main(argv=None):
 
             if args.sampler == "sdedit":
                 count = dm.edit_level(args.strength)
-            elif args.sample_steps is not None and args.sampler == "config":
+            elif args.sample_steps is not None and args.sampler == "config" and consistency is None:
                 count = dm._respaced_tables(args.sample_steps)[0]  # (Improved DDPM's strided chain)
             else:
                 count = dm.chain_length()
@@ -744,7 +847,7 @@ def main(argv=None):
             raise SystemExit("--labels / --guidance-scale need a class-conditional config (LitClassifierFreeDDPM)")
         elif args.sampler == "dpm++":
             imgs = dm.generate(shape, history=rec)
-        elif args.sample_steps is not None:
+        elif args.sample_steps is not None and consistency is None:
             imgs = dm.generate(shape, sample_steps=args.sample_steps, history=rec)
         elif args.steps is None:
             imgs = dm.generate(shape, history=rec)
@@ -752,7 +855,7 @@ def main(argv=None):
             import dmme_amd
 
             imgs = dmme_amd.gaussian(shape, device="cuda")
-            first = dm.sub_timesteps if args.sampler == "ddim-paper" or distilled is not None else dm.timesteps  # (the paper sampler's loop index counts sub-steps)
+            first = dm.sub_timesteps if args.sampler == "ddim-paper" or distilled is not None or consistency is not None else dm.timesteps  # (the paper sampler's loop index counts sub-steps)
             for k in range(args.steps):
                 imgs = module(imgs, first - k)
         torch.cuda.synchronize()
@@ -767,6 +870,8 @@ def main(argv=None):
         line = {"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3), "finite": bool(torch.isfinite(imgs).all())}
         if distilled is not None:
             line["distill"] = {"steps": int(distilled["steps"]), "tau_schedule": distilled.get("tau_schedule", "linear")}
+        if consistency is not None:
+            line["consistency"] = {"steps": int(consistency["steps"]), "sample_steps": int(dm.sub_timesteps)}
         print(json.dumps(line))
         return 0
 

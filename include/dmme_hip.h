@@ -808,6 +808,44 @@ DMME_API int dmme_distill_mid(int pred, int clip, const float* z_t, const float*
 DMME_API int dmme_distill_target(int pred, int clip, const float* z_t, const float* out1, const float* z_m, const float* out2, const float* rows,
                                  const int64_t* idx, int N, int B, int64_t chw, float* target, void* stream);
 
+/* ---- consistency distillation (Song, Dhariwal, Chen & Sutskever 2023, Algorithm 2; the discrete grid and boundary scalings of Latent
+ * Consistency Models, Luo et al. 2023): one training run, then 1-, 2- or 4-step samplers from the same weights (csrc/consistency.hip) ----
+ * The grid is tau = linear_tau(T, N); index i in 1..N stands for t = tau[i], m = tau[i-1] (m = 0 exactly when i = 1).  With
+ * sd = sigma_data, s = timestep_scaling:  cs(t) = sd^2 / ((s t)^2 + sd^2),  co(t) = s t / sqrt((s t)^2 + sd^2),  cs(0) = 1, co(0) = 0;
+ *   x0(z, t; o) = p0 o + p1 z                     the x0 estimate of a network output o at the image z (clamped to [-1, 1] iff clip)
+ *   f(z, t; o)  = cs(t) z + co(t) x0(z, t; o)      the consistency function: f(z, 0; .) = z
+ * One step: z_t and the two timestep vectors (dmme_distill_noise), the frozen teacher at (z_t, t), one DDIM step to zh_m
+ * (dmme_distill_mid), the target network at (zh_m, max(m, 1)), f_target = f(zh_m, m; .) (dmme_cm_target), the student at (z_t, t), and
+ * loss = (1/B) sum_b d(f(z_t, t; student)_b, f_target_b) with its gradient with respect to the student's raw output (dmme_cm_loss).
+ * rows: device fp32 table [N+1][12], folded by the host in float64 from alpha_bar and rounded once; row 0 is NaN; row i:
+ *   p0 p1    x0 at t:  eps: (-sigma/alpha, 1/alpha), x0: (1, 0), v: (-sigma, alpha)
+ *   p0' p1'  the same at the true m; (-0 or 0, 1) at m = 0, with no division by sigma anywhere
+ *   m0 m1    zh_m = m0 x1 + m1 z_t   m1 = sigma_m / sigma_t, m0 = alpha_m - m1 alpha_t; (1, 0) at m = 0
+ *   cs co    at t
+ *   cs' co'  at the true m; (1, 0) at m = 0
+ *   two spare floats (0)
+ * The first six slots and tt, int64 [N+1][2] = (t, max(m, 1)), have the layout dmme_distill_noise and dmme_distill_mid read; column 1 is
+ * the timestep the target network is evaluated at, the rows are what carry m = 0.  idx: int64[B] in DEVICE memory.  An index outside 1..N
+ * is never used as an address: its image of f_target and d_out comes out NaN, and so does the loss.  Every fp32 product and sum is rounded
+ * on its own (no fma); both sides of the loss go through one device function f.  16-byte accesses where chw % 4 == 0 and the image
+ * pointers are 16-byte aligned, element by element otherwise (any chw).
+ * dmme_cm_target: f_target = (cs' z_m) + (co' x0'), x0' = (p0' out_m) + (p1' z_m) clamped iff clip.
+ * dmme_cm_loss: S_b = sum_j (f - f_target)_j^2 over image b, f = (cs z_t) + (co x0) from the student's raw output `out` (never clamped).
+ *   metric DMME_CM_PSEUDO_HUBER: d_b = sqrt(S_b + c^2) - c,  g_b = grad_scale co p0 / (B sqrt(S_b + c^2))      (c > 0)
+ *   metric DMME_CM_L2:           d_b = S_b / chw,           g_b = 2 grad_scale co p0 / (B chw)                  (c unused)
+ *   loss[0] = (1/B) sum_b d_b;  sumsq (nullable, float[B]) = S_b;  d_out (nullable) = g_b (f - f_target).
+ *   d_b and g_b are formed once per image from the device's own S_b, in double ((grad_scale co) p0 over B times the root), rounded once.
+ *   Three plain launches, no atomics and no workgroup waiting for another: up to 64 workgroups per image leave partial sums in
+ *   `scratch`, one workgroup adds them in index order and forms d_b, g_b and the loss, the gradient launch (only with d_out) reads g_b.
+ *   `scratch` needs 65 * B floats.  B <= 65535.
+ * dmme_ema_lerp: dst = (dst decay) + (src one_minus), one_minus = (float)(1.0 - (double)decay) formed on the host; decay in [0, 1]. */
+enum { DMME_CM_PSEUDO_HUBER = 0, DMME_CM_L2 = 1 };
+DMME_API int dmme_cm_target(int clip, const float* z_m, const float* out_m, const float* rows, const int64_t* idx, int N, int B, int64_t chw, float* f_target,
+                            void* stream);
+DMME_API int dmme_cm_loss(int metric, const float* z_t, const float* out, const float* f_target, const float* rows, const int64_t* idx, int N, int B,
+                          int64_t chw, float c, float* loss, float* sumsq, float* d_out, float grad_scale, float* scratch, void* stream);
+DMME_API int dmme_ema_lerp(float* dst, const float* src, int64_t numel, float decay, void* stream);
+
 /* ---- Improved DDPM (learned variance): model_out is (B, 2C, H, W), channels [0, C) = eps, [C, 2C) = v
  * (IDDPM.forward_model, diffusion_models/iddpm.py:152-164); chw = C*H*W of ONE image of x. */
 
