@@ -17,6 +17,7 @@ from .diffusion_models import DDPM, DDIM, IDDPM, GeneralizedDDIM, DPMSolverPP  #
 from .diffusion_models import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # noqa: F401
 from .diffusion_models import ILVR, LikeChainRunner, ilvr_rows, lowpass_matrix  # noqa: F401
 from .diffusion_models import DDNM, RestoreChainRunner, ddnm_rows  # noqa: F401
+from .diffusion_models import DPS, PosteriorChainRunner, SeparableOperator, dps_rows  # noqa: F401
 from .diffusion_models import ProgressiveDistillation, distill_rows, distill_grid  # noqa: F401
 from .diffusion_models import ConsistencyDistillation, ConsistencySampler, consistency_rows, consistency_sampler_rows, consistency_grid  # noqa: F401
 from .lit_modules import LitDDPM, LitDDIM, LitIDDPM, LitClassifierFreeDDPM, LitDistill, LitConsistency  # noqa: F401
@@ -30,5 +31,5 @@ from .guidance import ClassifierFreeDDPM, ClassifierFreeDDIM, ClassifierFreeDPMS
 __all__ = ["gaussian", "gaussian_like", "uniform_int", "pad", "denorm", "norm", "UNet", "DDPM", "DDIM", "LitDDPM", "LitDDIM", "IDDPM", "LitIDDPM", "CIFAR10", "GeneralizedDDIM",
            "ConditionalUNet", "ClassifierFreeDDPM", "ClassifierFreeDDIM", "LitClassifierFreeDDPM", "DPMSolverPP", "ClassifierFreeDPMSolver",
            "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows", "ILVR", "LikeChainRunner", "ilvr_rows", "lowpass_matrix", "make_history", "save_png", "HistoryRecorder", "history_ordinals", "GenerateImage",
-           "ProgressiveDistillation", "distill_rows", "distill_grid", "LitDistill", "LinearDecayLR", "DDNM", "RestoreChainRunner", "ddnm_rows",
+           "ProgressiveDistillation", "distill_rows", "distill_grid", "LitDistill", "LinearDecayLR", "DDNM", "RestoreChainRunner", "ddnm_rows", "DPS", "PosteriorChainRunner", "SeparableOperator", "dps_rows",
            "ConsistencyDistillation", "ConsistencySampler", "consistency_rows", "consistency_sampler_rows", "consistency_grid", "LitConsistency"]

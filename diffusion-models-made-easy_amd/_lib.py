@@ -22,6 +22,7 @@ CHAIN_DPMPP, CHAIN_DPMPP_CFG = 8, 9  # DPM-Solver++(2M): tables of 8 floats per 
 CHAIN_REPAINT = 10  # RePaint / SDEdit: tables of 8 floats per index, the known image and its mask, three normal streams per step
 CHAIN_ILVR = 11  # ILVR: tables of 8 floats per index, the reference image, two filter matrices, two normal streams per step; a plane-wise update
 CHAIN_DDNM = 12  # DDNM: tables of 8 floats per index, a measurement and its mask at measurement resolution, two normal streams per step; a cell-wise update
+CHAIN_DPS = 13  # DPS: tables of 8 floats per index, a measurement and its mask, two operator matrices, one normal stream per step; a keep-forward and an input-backward inside the step
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2  # what the network predicts (include/dmme_hip.h: DMME_PRED_*)
 PREDICTIONS = {"eps": PRED_EPS, "x0": PRED_X0, "v": PRED_V}
 CM_METRICS = {"pseudo-huber": 0, "l2": 1}  # the consistency loss's metric (include/dmme_hip.h: DMME_CM_*)
@@ -127,6 +128,13 @@ PROTOTYPES = {
     "dmme_ddnm_step": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dmme_chain_update_ddnm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dmme_ddnm_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmme_dps_capacity": (_i, []),
+    "dmme_dps_measure": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_dps_adjoint": (_i, [_vp, _vp, _i, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_chain_adjoint_dps": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dmme_dps_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _vp]),
+    "dmme_chain_update_dps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "dmme_dps_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmme_distill_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dmme_distill_mid": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "dmme_distill_target": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),

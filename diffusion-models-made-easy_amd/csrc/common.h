@@ -529,6 +529,15 @@ int launch_ilvr(const char* what, float* x, const float* model_out, const float*
 int launch_ddnm_measure(const float* x, const float* mask, float* y_out, int B, int C, int H, int W, int sc, int gray, hipStream_t s);
 int launch_ddnm(const char* what, float* x, const float* model_out, const float* y, const float* mask, const float* z2, const float* row, const float* coef,
                 const int64_t* t_table, void* state, int B, int C, int H, int W, int sc, int gray, int out_planes, hipStream_t s);
+// dps.hip: the DPS step's own launches (the operator M o (Kh . Kw^T) per channel plane, its adjoint applied to the residual of the x0
+// prediction, and the update that consumes the network's input gradient; kind DMME_CHAIN_DPS has no row in the table above: its adjoint
+// works on whole planes).  row: the eager form's 8 host floats; coef / t_table / state: the chain form's; exactly one of the two is given.
+int launch_dps_measure(const float* x, const float* Kh, const float* Kw, const float* mask, float* y_out, int B, int C, int H, int W, int h, int w, hipStream_t s);
+int launch_dps_adjoint(const char* what, const float* x, const float* model_out, const float* y, const float* mask, const float* Kh, const float* Kw,
+                       const float* row, const float* coef, const void* state, float* g, float* d_out, float* sumsq, int B, int C, int H, int W, int h, int w,
+                       int out_planes, hipStream_t s);
+int launch_dps_update(const char* what, float* x, const float* model_out, const float* g, const float* dx, const float* sumsq, const float* z, const float* row,
+                      const float* coef, const int64_t* t_table, void* state, int B, int C, int H, int W, int out_planes, hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient

@@ -1360,7 +1360,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 119; }  // 119: dmme_cm_target, dmme_cm_loss, dmme_ema_lerp; 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 120; }  // 120: DMME_CHAIN_DPS, dmme_dps_capacity, dmme_dps_measure, dmme_dps_adjoint, dmme_chain_adjoint_dps, dmme_dps_step, dmme_chain_update_dps, dmme_dps_chain_step; 119: dmme_cm_target, dmme_cm_loss, dmme_ema_lerp; 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1776,10 +1776,11 @@ DMME_API int dmme_chain_update_repaint(float* x, const float* model_out, const f
 
 // The front half of a capturable step, shared by every kind: the checks of the plan (`cfg`: a classifier-free kind; want_planes: the
 // output planes per image the kind takes, 0 = one or two), the forward, the x0 / v adapter, x0 thresholding (row, scol: where a
-// classifier-free kind's table holds its scale).  planes: the network's output planes per image.
+// classifier-free kind's table holds its scale).  planes: the network's output planes per image.  keep: the forward is the form a
+// backward can follow (dmme_dps_chain_step); every other step runs the no-grad form.
 static int chain_step_front(const char* what, const dmme_plan* plan, const void* packed, float* x, const int64_t* labels, int* status, float* model_out,
                             void* workspace, int kind, bool cfg, int want_planes, const float* step_coef, int row, int scol, void* state, void* stream,
-                            int& planes) {
+                            int& planes, bool keep = false) {
     if (cfg)
         DMME_REQUIRE(plan->cond && plan->B % 2 == 0, DMME_ERR_INVALID,
                      "%s: needs a class-conditional plan (DMME_ARCH_DDPM_COND) of even batch: conditional half, unconditional half (B = %d)", what, plan->B);
@@ -1793,7 +1794,7 @@ static int chain_step_front(const char* what, const dmme_plan* plan, const void*
     if (!cfg)
         if (int rc = lvl_check(plan, what, (hipStream_t)stream, true)) return rc;
     const int64_t* t_dev = (const int64_t*)state + 1;
-    if (int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, false, labels, status)) return rc;
+    if (int rc = unet_forward_impl(plan, packed, x, t_dev, 1, model_out, workspace, nullptr, stream, keep, labels, status)) return rc;
     // an x0 / v network: its output becomes an eps prediction here, over the plan's whole batch (a classifier-free plan's 2B images: the
     // affine map commutes with the guidance mix), and everything behind this line is the eps code
     if (plan->pred != DMME_PRED_EPS)
@@ -1890,6 +1891,35 @@ DMME_API int dmme_ddnm_chain_step(const dmme_plan* plan, const void* packed, flo
         return rc;
     return launch_ddnm("ddnm_chain_step", x, model_out, y, mask, nullptr, nullptr, step_coef, t_table, state, plan->B, plan->cfg.in_channels, plan->H, plan->W, s,
                        gray, planes, (hipStream_t)stream);
+}
+
+// DPS: kind DMME_CHAIN_DPS, which differentiates the denoiser itself: the keep form of the forward, the adjoint kernel (csrc/dps.hip) that
+// leaves d ||y - A x0|| / d eps (up to the per-image 1 / ||r||) in d_out, the input-only backward, the update that consumes both
+DMME_API int dmme_dps_chain_step(const dmme_plan* plan, const void* packed, const void* packed_bwd, float* x, float* model_out, void* workspace,
+                                 void* bwd_workspace, const float* y, const float* mask, const float* Kh, const float* Kw, int h, int w, float* g, float* d_out,
+                                 float* dx, float* sumsq, const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && packed_bwd && x && model_out && workspace && bwd_workspace && y && Kh && Kw && g && d_out && dx && sumsq && step_coef &&
+                     t_table && state,
+                 DMME_ERR_INVALID, "dps_chain_step: null argument");
+    DMME_REQUIRE(!plan->cond && (plan->cfg.arch == DMME_ARCH_DDPM || plan->cfg.arch == DMME_ARCH_IDDPM), DMME_ERR_INVALID,
+                 "dps_chain_step: needs an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan (got architecture %d%s)", plan->cfg.arch,
+                 plan->cond ? ", class-conditional" : "");
+    DMME_REQUIRE(plan->pred == DMME_PRED_EPS, DMME_ERR_UNSUPPORTED,
+                 "dps_chain_step: the plan's network predicts %s; the derivative of the x0 / v adapter is not built: an eps network only",
+                 plan->pred == DMME_PRED_X0 ? "x0" : "v");
+    DMME_REQUIRE(plan->thr_mode == DMME_THRESHOLD_NONE, DMME_ERR_UNSUPPORTED,
+                 "dps_chain_step: the plan thresholds x0 (mode %d); the derivative of the clip is not built: threshold none only", plan->thr_mode);
+    int planes = 0;
+    if (int rc = chain_step_front("dps_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_DPS, false, 0, nullptr, 8, 0, state, stream,
+                                  planes, true))
+        return rc;
+    const int B = plan->B, C = plan->cfg.in_channels, H = plan->H, W = plan->W;
+    if (int rc = launch_dps_adjoint("dps_chain_step", x, model_out, y, mask, Kh, Kw, nullptr, step_coef, state, g, d_out, sumsq, B, C, H, W, h, w, planes,
+                                    (hipStream_t)stream))
+        return rc;
+    const int64_t* t_dev = (const int64_t*)state + 1;
+    if (int rc = dmme_unet_backward_input(plan, packed, packed_bwd, x, t_dev, 1, d_out, workspace, bwd_workspace, nullptr, dx, stream)) return rc;
+    return launch_dps_update("dps_chain_step", x, model_out, g, dx, sumsq, nullptr, nullptr, step_coef, t_table, state, B, C, H, W, planes, (hipStream_t)stream);
 }
 
 // Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM): between the forward and the update, the classifier's forward, the log-softmax

@@ -39,6 +39,8 @@ def chain_draws(kind: int, rows) -> bool:
         return any(r[2] != 0.0 for r in rows)
     if kind == _lib.CHAIN_DDNM:  # (cz of the posterior's noise, r1 of a folded jump)
         return any(r[2] != 0.0 or r[7] != 0.0 for r in rows)
+    if kind == _lib.CHAIN_DPS:  # (c2 of the reverse step's noise)
+        return any(r[2] != 0.0 for r in rows)
     return True
 
 
@@ -232,11 +234,17 @@ class ChainRunner(ChainTables):
         """identifies the packed weights the captured graph reads"""
         return (self.plan.packed_version, self.plan.fold_version, self.plan.packed.data_ptr())
 
+    def _packed(self):
+        """the packed weights the step's forward reads, brought up to date outside any capture: the no-grad form's, re-packed (and the
+        attention blocks re-folded) when the parameters changed.  A runner whose step keeps the forward's context for a backward
+        (PosteriorChainRunner) hands over the unfolded weights and the backward's buffers instead."""
+        return self.model._packed_for(self.plan, fold=True)
+
     def step(self):
         model = self.model
         if model.training:
             raise RuntimeError("ChainRunner: sampling chains run in eval mode (no dropout masks inside the replayed step)")
-        packed = model._packed_for(self.plan, fold=True)  # re-packs (and re-folds the attention blocks) when the parameters changed
+        packed = self._packed()
         wkey = self._weights_key()
         if not self.use_graph or self.capture_error is not None:
             self._launch(packed)

@@ -24,7 +24,8 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler repaint --image X.npy --mask M.npy --save OUT.npy   (RePaint inpainting)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler ilvr --image X.npy --down-factor 8 --save OUT.npy   (ILVR: samples that share X's coarse content)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler ddnm --measurement Y.npy --sr-scale 4 --save OUT.npy   (DDNM: 4x super-resolution of Y; --gray colourises, --mask inpaints)
-  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit --image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dps --operator blur --blur-size 9 --blur-sigma 2 --zeta 1 --sigma-y 0.05 --image X.npy --save OUT.npy   (DPS: deblurring a noisy measurement; --operator identity | blur | bicubic | average [--down-scale s], --measurement Y.npy, --mask inpaints)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit--image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3 --guidance-scale 2.5 --threshold dynamic   (x0 thresholding in front of the update: none | static | dynamic [--threshold-percentile P]; any sampler)
   python -m dmme_amd.trainer fit    --config configs/vpred/cifar10.yaml   (a v-prediction network under min-SNR weights; --prediction / --loss-weight / --snr-gamma override any YAML)
@@ -457,8 +458,8 @@ def _check_paint_args(args) -> None:
     """what goes with --sampler repaint / sdedit and what does not; exits with a message (before anything touches the GPU)"""
     given = [f for f, v in (("--image", args.image), ("--mask", args.mask), ("--strength", args.strength), ("--jump-length", args.jump_length),
                             ("--resamples", args.resamples)) if v is not None]
-    if args.sampler in ("ilvr", "ddnm"):
-        return  # (`_check_ilvr_args` / `_check_ddnm_args` have looked at all of these)
+    if args.sampler in ("ilvr", "ddnm", "dps"):
+        return  # (`_check_ilvr_args` / `_check_ddnm_args` / `_check_dps_args` have looked at all of these)
     if args.sampler not in PAINT_SAMPLERS:
         if given:
             raise SystemExit(f"{', '.join(given)} belong{'s' if len(given) == 1 else ''} to --sampler repaint / sdedit")
@@ -539,6 +540,8 @@ def _check_ddnm_flags(args) -> None:
     """the flags that only --sampler ddnm takes, in front of every check that opens a file"""
     own = [f for f, v in (("--sr-scale", args.sr_scale), ("--gray", args.gray or None), ("--sigma-y", args.sigma_y), ("--measurement", args.measurement))
            if v is not None]
+    if args.sampler == "dps":  # (shares --sigma-y and --measurement; the operator has flags of its own)
+        own = [f for f in own if f in ("--sr-scale", "--gray")]
     if args.sampler != "ddnm" and own:
         raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to --sampler ddnm")
 
@@ -597,6 +600,89 @@ def _ddnm_process(module, args):
                              travel_length=args.jump_length or 1, travel_repeat=args.resamples or 1)
 
 
+DPS_OPERATORS = ("identity", "blur", "bicubic", "average")
+
+
+def _check_dps_flags(args) -> None:
+    """the flags that only --sampler dps takes, in front of every check that opens a file"""
+    own = [f for f, v in (("--operator", args.operator), ("--blur-size", args.blur_size), ("--blur-sigma", args.blur_sigma), ("--down-scale", args.down_scale),
+                          ("--zeta", args.zeta)) if v is not None]
+    if args.sampler != "dps" and own:
+        raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to --sampler dps")
+
+
+def _check_dps_args(args):
+    """what goes with --sampler dps and what does not; exits with a message (before anything touches the GPU).  Returns
+    (measurement or None, image or None, mask or None) for --sampler dps, else None."""
+    if args.sampler != "dps":
+        return None
+    name = "--sampler dps"
+    if args.command != "sample":
+        raise SystemExit(f"{name} belongs to `sample`: it restores images from a measurement with a trained network, training is the config's own")
+    for flag, v in (("--eta", args.eta), ("--steps", args.steps), ("--labels", args.labels), ("--guidance-scale", args.guidance_scale),
+                    ("--strength", args.strength), ("--jump-length", args.jump_length), ("--resamples", args.resamples)):
+        if v is not None:
+            raise SystemExit(f"{flag} does not go with {name}: it runs whole chains of an unconditional network (--sample-steps K sets the grid)")
+    if args.prediction not in (None, "eps"):
+        raise SystemExit(f"--prediction {args.prediction} does not go with {name}: the derivative of the x0 / v adapter is not built (an eps network only)")
+    if args.threshold not in (None, "none"):
+        raise SystemExit(f"--threshold {args.threshold} does not go with {name}: the derivative of the clip is not built")
+    if (args.measurement is None) == (args.image is None):
+        raise SystemExit(f"{name} needs exactly one of --measurement Y.npy (the degraded input) and --image X.npy (degraded here first: the demo path)")
+    if args.sample_steps is not None and args.sample_steps < 1:
+        raise SystemExit("--sample-steps must be at least 1")
+    op = args.operator or "identity"
+    if op != "blur" and (args.blur_size is not None or args.blur_sigma is not None):
+        raise SystemExit("--blur-size / --blur-sigma belong to --operator blur")
+    if op not in ("bicubic", "average") and args.down_scale is not None:
+        raise SystemExit("--down-scale belongs to --operator bicubic / average")
+    if args.blur_size is not None and (args.blur_size < 1 or args.blur_size % 2 != 1):
+        raise SystemExit("--blur-size must be an odd number of taps, at least 1")
+    if args.blur_sigma is not None and not args.blur_sigma > 0.0:
+        raise SystemExit("--blur-sigma must be positive")
+    s = _dps_scale(args)
+    if s < 1:
+        raise SystemExit("--down-scale must be at least 1")
+    if args.zeta is not None and not args.zeta >= 0.0:
+        raise SystemExit("--zeta must be at least 0")
+    if args.sigma_y is not None and not args.sigma_y >= 0.0:
+        raise SystemExit("--sigma-y must be at least 0")
+    meas = image = None
+    if args.image is not None:
+        image = _load_npy(args.image, "--image")
+        H, W = image.shape[2:]
+        if H % s != 0 or W % s != 0:
+            raise SystemExit(f"--image {args.image}: the image size {H} x {W} is not divisible by --down-scale {s}")
+        shape = (image.shape[0], image.shape[1], H // s, W // s)
+    else:
+        meas = _load_npy(args.measurement, "--measurement")
+        shape = tuple(meas.shape)
+    mask = None if args.mask is None else _load_npy(args.mask, "--mask")
+    if mask is not None and (mask.shape[0] not in (1, shape[0]) or mask.shape[1] not in (1, shape[1]) or tuple(mask.shape[2:]) != shape[2:]):
+        raise SystemExit(f"--mask {args.mask}: shape {tuple(mask.shape)} does not broadcast to the measurement's {shape} (the mask is at measurement resolution)")
+    if mask is not None and not bool(((mask == 0) | (mask == 1)).all()):
+        raise SystemExit(f"--mask {args.mask}: values must be 0 or 1 (1: measured)")
+    return meas, image, mask
+
+
+def _dps_scale(args) -> int:
+    """s of the down-sampling operators (default 4), 1 for the ones that keep the size"""
+    return (4 if args.down_scale is None else args.down_scale) if (args.operator or "identity") in ("bicubic", "average") else 1
+
+
+def _dps_process(module, args, H: int, W: int):
+    """DPS over the network and the noise schedule of the process the YAML built, with the operator for images of H x W"""
+    from .diffusion_models import DPS, SeparableOperator
+
+    old = module.diffusion_model
+    sub = min(100, old.timesteps) if args.sample_steps is None else args.sample_steps
+    try:
+        op = SeparableOperator.preset(args.operator or "identity", H, W, blur_size=args.blur_size or 9, blur_sigma=args.blur_sigma or 2.0, scale=_dps_scale(args))
+        return DPS.from_process(old, sub_timesteps=sub, operator=op, zeta=1.0 if args.zeta is None else args.zeta, sigma_y=args.sigma_y or 0.0)
+    except (ValueError, NotImplementedError) as exc:
+        raise SystemExit(f"--sampler dps: {exc}")
+
+
 def _load_npy(path: str, what: str) -> torch.Tensor:
     """a float image array (B, C, H, W) or (C, H, W) from a .npy file, as a 4-D fp32 tensor"""
     import numpy as np
@@ -635,13 +721,15 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
-    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr", "ddnm"],
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr", "ddnm", "dps"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table; "
                          "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20); "
                          "'repaint' inpaints --image where --mask is 0, 'sdedit' edits --image at --strength (any unconditional config; --sample-steps: grid levels, default 250); "
                          "'ilvr' samples images that share the low frequencies of --image (any unconditional config; --down-factor N, --range-level R, --sample-steps); "
                          "'ddnm' restores images from --measurement (or from --image, degraded first): super-resolution --sr-scale S, colourisation --gray, "
-                         "inpainting --mask, a noisy measurement --sigma-y (any unconditional config; --sample-steps, default 100; --jump-length / --resamples: time travel)")
+                         "inpainting --mask, a noisy measurement --sigma-y (any unconditional config; --sample-steps, default 100; --jump-length / --resamples: time travel); "
+                         "'dps' restores images from a noisy --measurement (or from --image, degraded first) by posterior sampling: --operator identity | blur | bicubic | "
+                         "average, step size --zeta, inpainting --mask, noise level --sigma-y (any unconditional eps config; --sample-steps, default 100)")
     ap.add_argument("--image", default=None, help="sample --sampler repaint / sdedit: .npy, float32 in [-1, 1], (B, C, H, W) or (C, H, W)")
     ap.add_argument("--mask", default=None, help="sample --sampler repaint (needed) / sdedit (optional): .npy broadcastable to the image, 1 = keep the pixel, 0 = generate")
     ap.add_argument("--strength", type=float, default=None, help="sample --sampler sdedit: in (0, 1], the share of the noise levels the guide is pushed up before it is denoised")
@@ -653,6 +741,11 @@ def main(argv=None):
     ap.add_argument("--sr-scale", type=int, default=None, help="sample --sampler ddnm: s of the s x s average pooling the measurement went through (default 1: none); a divisor of the image size")
     ap.add_argument("--gray", action="store_true", help="sample --sampler ddnm: the measurement is the mean of the channels (colourisation)")
     ap.add_argument("--sigma-y", type=float, default=None, help="sample --sampler ddnm: the noise level of the measurement (default 0); with --image, noise of this level is added to the degraded image")
+    ap.add_argument("--operator", default=None, choices=list(DPS_OPERATORS), help="sample --sampler dps: the measurement operator per channel plane (default identity)")
+    ap.add_argument("--blur-size", type=int, default=None, help="sample --sampler dps --operator blur: taps of the Gaussian kernel, odd (default 9)")
+    ap.add_argument("--blur-sigma", type=float, default=None, help="sample --sampler dps --operator blur: standard deviation of the Gaussian kernel in pixels (default 2)")
+    ap.add_argument("--down-scale", type=int, default=None, help="sample --sampler dps --operator bicubic / average: the down-sampling factor, a divisor of the image size (default 4)")
+    ap.add_argument("--zeta", type=float, default=None, help="sample --sampler dps: the step size of the gradient step on the measurement's residual (default 1; 0: the unconditioned chain)")
     ap.add_argument("--save", default=None, help="sample: write the images to this .npy file (float32, (B, C, H, W))")
     ap.add_argument("--grid", default=None, help="sample: write the images to this PNG file as a grid (every sampler; goes with --save)")
     ap.add_argument("--vis-length", type=int, default=1,
@@ -691,8 +784,10 @@ def main(argv=None):
     _check_consistency_args(args)
     _check_threshold_args(args)
     _check_ddnm_flags(args)
+    _check_dps_flags(args)
     ilvr_image = _check_ilvr_args(args)
     ddnm_inputs = _check_ddnm_args(args)
+    dps_inputs = _check_dps_args(args)
     _check_paint_args(args)
     if args.save is not None and args.command != "sample":
         raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
@@ -725,6 +820,10 @@ def main(argv=None):
         if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
             raise SystemExit("--sampler ddnm needs an unconditional config: guided DDNM is not implemented")
         measurement, image, mask = ddnm_inputs
+    elif args.sampler == "dps":
+        if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+            raise SystemExit("--sampler dps needs an unconditional config: guided DPS is not implemented")
+        measurement, image, mask = dps_inputs
     elif args.sample_steps is not None and args.sampler == "config" and args.command == "sample" and args.steps is None and _consistency_entry(args, conf) is not None:
         pass  # (a consistency checkpoint: --sample-steps K is the K of its sampler)
     elif args.sample_steps is not None and args.sampler != "dpm++":
@@ -799,6 +898,10 @@ def main(argv=None):
             module.diffusion_model = _ilvr_process(module, args).cuda()
         elif args.sampler == "ddnm":
             module.diffusion_model = _ddnm_process(module, args).cuda()
+        elif args.sampler == "dps":
+            s = _dps_scale(args)
+            H, W = tuple(image.shape[2:]) if image is not None else (measurement.shape[2] * s, measurement.shape[3] * s)
+            module.diffusion_model = _dps_process(module, args, H, W).cuda()
         module.eval()
         dm = module.diffusion_model
         if args.threshold is not None:
@@ -815,6 +918,10 @@ def main(argv=None):
                 if dm.sigma_y > 0.0:
                     measurement = measurement + dm.sigma_y * dmme_amd.gaussian(tuple(measurement.shape), device=measurement.device)
             restored_shape = (measurement.shape[0], dm._channels(measurement.shape[1]), measurement.shape[2] * dm.scale, measurement.shape[3] * dm.scale)
+        if args.sampler == "dps":
+            if image is not None:  # (the demo path: the measurement is made here, with noise of the level the sampler is told)
+                measurement = dm.degrade(image, mask)
+            restored_shape = (measurement.shape[0], measurement.shape[1], dm.operator.H, dm.operator.W)
         if args.grid is not None:
             from .diffusion_models import HistoryRecorder, history_ordinals
 
@@ -824,7 +931,7 @@ def main(argv=None):
                 count = dm._respaced_tables(args.sample_steps)[0]  # (Improved DDPM's strided chain)
             else:
                 count = dm.chain_length()
-            rec_shape = restored_shape if args.sampler == "ddnm" else tuple(image.shape) if args.sampler in PAINT_SAMPLERS + ("ilvr",) else shape
+            rec_shape = restored_shape if args.sampler in ("ddnm", "dps") else tuple(image.shape) if args.sampler in PAINT_SAMPLERS + ("ilvr",) else shape
             rec = HistoryRecorder(rec_shape[0], *rec_shape[1:], history_ordinals(count, args.vis_length), out_kind=1)
         if args.sampler == "repaint":
             imgs = dm.inpaint(image, mask, history=rec)
@@ -832,7 +939,7 @@ def main(argv=None):
             imgs = dm.edit(image, args.strength, mask, history=rec)
         elif args.sampler == "ilvr":
             imgs = dm.sample_like(image, history=rec)
-        elif args.sampler == "ddnm":
+        elif args.sampler in ("ddnm", "dps"):
             imgs = dm.restore(measurement, mask, history=rec)
         elif getattr(module, "conditional", False):
             if args.steps is not None or args.sampler == "ddim-paper" or (args.sample_steps is not None and args.sampler != "dpm++"):

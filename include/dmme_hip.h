@@ -777,6 +777,71 @@ DMME_API int dmme_chain_update_ddnm(float* x, const float* model_out, const floa
 DMME_API int dmme_ddnm_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, const float* y, const float* mask,
                                   int s, int gray, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
+/* ---- DPS (Chung et al., ICLR 2023, Algorithm 1): posterior sampling for noisy linear inverse problems (csrc/dps.hip) ------------------
+ * The operator family acts on each channel plane of images (B, C, H, W): A x = M o (Kh x_c Kw^T), to (B, C, h, w), with Kh [h][H] and
+ * Kw [w][W] dense fp32 row-major device matrices, h <= H, w <= W, and M a binary mask at measurement resolution, 1 = measured.  The
+ * library reads the matrices as dense and assumes nothing else (the host builds identity, Gaussian blur, bicubic and average presets in
+ * float64 and rounds them once).  Grid and levels as RePaint's; the walk goes straight down, n -> 0, one network evaluation, one input
+ * gradient and one table row per transition a -> b = a - 1 (alpha = abar_a / abar_b).  A step is DDPM's reverse step followed by a
+ * gradient step on ||y - A x0^(x_t)|| taken through the network:
+ *     x0 = (A_t x) - (B_t e)                                          rounded like dmme_x0_threshold's x0
+ *     T  = x0 Kw^T;  Y = Kh T                                         per plane
+ *     r  = y - Y   where the cell's m != 0, else 0                    a select: y is not looked at where m == 0 (a NaN there stays out)
+ *     U  = r Kw;   g = Kh^T U                                         g = A^T r
+ *     d_out = B_t g  (the eps plane; an IDDPM output's v plane: 0);   sumsq[b][c] = sum r^2 over the plane
+ *     dx = J_eps(x_t)^T d_out                                         dmme_unet_backward_input behind the keep form of the forward
+ *     u  = c0 (x - c1 e);      u = u + c2 z   only where c2 != 0      DDPM's reverse step (sigma^2 = 1 - alpha), DDPM's bits
+ *     n_b = sqrt(sum_c sumsq[b][c])                                   in channel order; per image
+ *     x' = u + (zeta / n_b)((A_t g) - dx)   where zeta != 0 and n_b != 0, else x' = u (g, dx and sumsq are not read where zeta == 0)
+ * The sign: grad_{x_t} ||r|| = (-A_t g + J_eps^T (B_t g)) / ||r||.  The backward is linear in d_y and independent per image, so the factor
+ * 1 / ||r_b|| is applied in the update and no grid-wide reduction sits between the adjoint kernel and the backward.
+ * Kind DMME_CHAIN_DPS = 13 has entry points and a table layout of its own and no row in the kind table of the elementwise updates:
+ * dmme_chain_step and dmme_chain_update refuse it.
+ *   step_coef float[n+1][8], per loop index: {c0 = 1/sqrt(alpha), c1 = (1 - alpha)/sqrt(1 - abar_a), c2 = sqrt(1 - alpha) (0 where b = 0),
+ *             A_t = 1/sqrt(abar_a), B_t = sqrt(1 - abar_a)/sqrt(abar_a), zeta, -, -}; built in float64, rounded once
+ *   t_table   int64[n+1]: t_table[i] = tau_a; t_table[0] = 0
+ *   y, mask   fp32, (B, C, h, w) contiguous, read only; the mask's values are 0 or 1 (mask nullable: everything is measured)
+ *   g, dx     fp32 (B, C, H, W);  d_out: fp32 in the network output's layout (B, out_planes * C, H, W);  sumsq: fp32 [B][C]
+ *   rounding  the elementwise parts round every product, sum, difference, quotient and root to fp32 on its own (no fma), so with
+ *             zeta = 0 the update is dmme_ddpm_step bit for bit.  Each of the four matrix products is the chain
+ *             acc = fma(a_k, b_k, acc), k = 0, 1, ... from acc = 0, in ONE device function that dmme_dps_measure and both adjoint forms
+ *             call: |Y - exact| <= (H + W + 8) 2^-24 (|Kh| |x0| |Kw|^T) elementwise, and so on stage by stage.  sumsq is each thread's
+ *             cells in ascending order, then a fixed tree over the workgroup's 256 partial sums: no atomics, the same bits every run,
+ *             whatever B and the image's place in the batch.
+ *   normals   a step owns ONE stream of B*chw normals: the quad at element e is the draw at Philox counter offset + e/4, what
+ *             dmme_randn(z, B*chw, seed, offset) writes.  Where c2 == 0 nothing is drawn or read.  The chain form moves the offset by
+ *             B*chw/4 per step whatever the row used.
+ *   form      one workgroup per (image, channel) plane with the plane, T, r and both tables in LDS
+ *             (H W + H w + h w + h (H + 1) + w (W + 1) + 256 floats, at most 96 KiB: 32 x 32 and 64 x 64 with h = H, w = W fit).  A plane
+ *             of more than dmme_dps_capacity() values, or one whose tables do not fit beside it, is refused with DMME_ERR_UNSUPPORTED
+ *             before any launch; a streaming form is not built.  C*H*W and W must be multiples of 4 (DMME_ERR_UNSUPPORTED).
+ *   out_planes  1 (eps), or 2 (an IDDPM network's (eps, v): the eps plane is used, the v plane's gradient is 0).
+ * dmme_dps_measure: y_out = A x (an unmeasured cell is exactly 0).  dmme_dps_adjoint: g, d_out and sumsq from (x, model_out) with the row
+ * (8 floats) in HOST memory; dmme_chain_adjoint_dps: the same bits with the row read at step_coef[8 state.i] (the state is only read).
+ * dmme_dps_step: the eager update (row in HOST memory; z nullable only where c2 == 0; g, dx, sumsq nullable only where zeta == 0),
+ * bit-identical to dmme_chain_update_dps, the chain form (row from device memory, normals drawn in the kernel; noise: nullable, B*chw
+ * normals used in place of the drawn ones - tests; the last block advances the loop state).
+ * dmme_dps_chain_step = dmme_unet_forward (the KEEP form: `packed` holds the unfolded weights) at t = state.t, dmme_chain_adjoint_dps,
+ * dmme_unet_backward_input (packed_bwd, bwd_workspace: as there), dmme_chain_update_dps: one keep-forward plus one input-backward per step.
+ * An unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan (DMME_ERR_INVALID otherwise) whose prediction is eps and whose threshold mode
+ * is none (DMME_ERR_UNSUPPORTED otherwise: the derivative of the adapter and of the clip is not built). */
+enum { DMME_CHAIN_DPS = 13 };
+DMME_API int dmme_dps_capacity(void);
+DMME_API int dmme_dps_measure(const float* x, const float* Kh, const float* Kw, const float* mask, float* y_out, int B, int C, int H, int W, int h, int w,
+                              void* stream);
+DMME_API int dmme_dps_adjoint(const float* x, const float* model_out, int out_planes, const float* row, const float* y, const float* mask, const float* Kh,
+                              const float* Kw, float* g, float* d_out, float* sumsq, int B, int C, int H, int W, int h, int w, void* stream);
+DMME_API int dmme_chain_adjoint_dps(const float* x, const float* model_out, int out_planes, const float* step_coef, const void* state, const float* y,
+                                    const float* mask, const float* Kh, const float* Kw, float* g, float* d_out, float* sumsq, int B, int C, int H, int W, int h,
+                                    int w, void* stream);
+DMME_API int dmme_dps_step(float* x, const float* model_out, const float* g, const float* dx, const float* sumsq, const float* z, const float* row, int B, int C,
+                           int H, int W, int out_planes, void* stream);
+DMME_API int dmme_chain_update_dps(float* x, const float* model_out, const float* g, const float* dx, const float* sumsq, const float* noise,
+                                   const float* step_coef, const int64_t* t_table, void* state, int B, int C, int H, int W, int out_planes, void* stream);
+DMME_API int dmme_dps_chain_step(const dmme_plan* plan, const void* packed, const void* packed_bwd, float* x, float* model_out, void* workspace,
+                                 void* bwd_workspace, const float* y, const float* mask, const float* Kh, const float* Kw, int h, int w, float* g, float* d_out,
+                                 float* dx, float* sumsq, const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
 /* ---- progressive distillation (Salimans & Ho, ICLR 2022, Algorithm 2): training an N-step sampler from a 2N-step one (csrc/distill.hip) ----
  * The grid is the one of GeneralizedDDIM(..., "linear"): tau = linear_tau(T, 2N); student index i in 1..N stands for the timesteps
  * t = tau[2i], m = tau[2i-1], e = tau[2i-2].  One training step: z_t = alpha_t x0 + sigma_t eps; the frozen teacher at (z_t, t) gives the x0
