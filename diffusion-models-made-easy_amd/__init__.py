@@ -18,6 +18,7 @@ from .diffusion_models import RePaint, PaintChainRunner, repaint_levels, repaint
 from .diffusion_models import ILVR, LikeChainRunner, ilvr_rows, lowpass_matrix  # noqa: F401
 from .diffusion_models import DDNM, RestoreChainRunner, ddnm_rows  # noqa: F401
 from .diffusion_models import DPS, PosteriorChainRunner, SeparableOperator, dps_rows  # noqa: F401
+from .diffusion_models import ProbabilityFlow, FlowChainRunner, LikelihoodChainRunner, LogLikelihood, pf_rows, pf_grid  # noqa: F401
 from .diffusion_models import ProgressiveDistillation, distill_rows, distill_grid  # noqa: F401
 from .diffusion_models import ConsistencyDistillation, ConsistencySampler, consistency_rows, consistency_sampler_rows, consistency_grid  # noqa: F401
 from .lit_modules import LitDDPM, LitDDIM, LitIDDPM, LitClassifierFreeDDPM, LitDistill, LitConsistency  # noqa: F401
@@ -32,4 +33,5 @@ __all__ = ["gaussian", "gaussian_like", "uniform_int", "pad", "denorm", "norm", 
            "ConditionalUNet", "ClassifierFreeDDPM", "ClassifierFreeDDIM", "LitClassifierFreeDDPM", "DPMSolverPP", "ClassifierFreeDPMSolver",
            "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows", "ILVR", "LikeChainRunner", "ilvr_rows", "lowpass_matrix", "make_history", "save_png", "HistoryRecorder", "history_ordinals", "GenerateImage",
            "ProgressiveDistillation", "distill_rows", "distill_grid", "LitDistill", "LinearDecayLR", "DDNM", "RestoreChainRunner", "ddnm_rows", "DPS", "PosteriorChainRunner", "SeparableOperator", "dps_rows",
-           "ConsistencyDistillation", "ConsistencySampler", "consistency_rows", "consistency_sampler_rows", "consistency_grid", "LitConsistency"]
+           "ConsistencyDistillation", "ConsistencySampler", "consistency_rows", "consistency_sampler_rows", "consistency_grid", "LitConsistency",
+           "ProbabilityFlow", "FlowChainRunner", "LikelihoodChainRunner", "LogLikelihood", "pf_rows", "pf_grid"]

@@ -23,6 +23,7 @@ CHAIN_REPAINT = 10  # RePaint / SDEdit: tables of 8 floats per index, the known 
 CHAIN_ILVR = 11  # ILVR: tables of 8 floats per index, the reference image, two filter matrices, two normal streams per step; a plane-wise update
 CHAIN_DDNM = 12  # DDNM: tables of 8 floats per index, a measurement and its mask at measurement resolution, two normal streams per step; a cell-wise update
 CHAIN_DPS = 13  # DPS: tables of 8 floats per index, a measurement and its mask, two operator matrices, one normal stream per step; a keep-forward and an input-backward inside the step
+CHAIN_PFODE = 14  # probability-flow ODE: tables of 8 floats per index, one Heun stage per index, two saved buffers; the likelihood's stage holds a keep-forward, a Rademacher probe and an input-backward
 PRED_EPS, PRED_X0, PRED_V = 0, 1, 2  # what the network predicts (include/dmme_hip.h: DMME_PRED_*)
 PREDICTIONS = {"eps": PRED_EPS, "x0": PRED_X0, "v": PRED_V}
 CM_METRICS = {"pseudo-huber": 0, "l2": 1}  # the consistency loss's metric (include/dmme_hip.h: DMME_CM_*)
@@ -135,6 +136,18 @@ PROTOTYPES = {
     "dmme_dps_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f), _i, _i, _i, _i, _i, _vp]),
     "dmme_chain_update_dps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dmme_dps_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_rademacher": (_i, [_vp, _i64, _u64, _u64, _vp]),
+    "dmme_pf_probe": (_i, [_vp, _i, _i64, _i, _u64, _u64, _vp]),
+    "dmme_chain_probe_pf": (_i, [_vp, _vp, _i, _i64, _i, _vp]),
+    "dmme_pf_dequantize": (_i, [_vp, _i64, _u64, _u64, _vp]),
+    "dmme_pf_scratch_floats": (_i64, [_i, _i64]),
+    "dmme_pf_dot": (_i, [_vp, _i, _vp, C.POINTER(_f), _i, _i64, _vp, _vp, _vp, _vp]),
+    "dmme_chain_dot_pf": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    "dmme_pf_prior": (_i, [_vp, _i, _i64, _vp, _vp, _vp]),
+    "dmme_pf_stage": (_i, [_vp, _vp, _i, _vp, _vp, C.POINTER(_f), _i, _i64, _vp]),
+    "dmme_chain_stage_pf": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp]),
+    "dmme_pf_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_pf_ll_chain_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmme_distill_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dmme_distill_mid": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "dmme_distill_target": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),

@@ -538,6 +538,15 @@ int launch_dps_adjoint(const char* what, const float* x, const float* model_out,
                        int out_planes, hipStream_t s);
 int launch_dps_update(const char* what, float* x, const float* model_out, const float* g, const float* dx, const float* sumsq, const float* z, const float* row,
                       const float* coef, const int64_t* t_table, void* state, int B, int C, int H, int W, int out_planes, hipStream_t s);
+// pfode.hip: the probability-flow ODE's launches (the Rademacher probe in the network output's layout, the per-image probe dot with its
+// double accumulator, the four-term stage update; kind DMME_CHAIN_PFODE has no row in the table above: a stage carries two saved
+// buffers).  row: the eager form's 8 host floats (the probe: seed / offset); coef / state: the chain form's; exactly one of the two is given.
+int64_t pf_scratch_floats(int B, int64_t chw);
+int launch_pf_probe(const char* what, float* d_out, const void* state, uint64_t seed, uint64_t offset, int B, int64_t chw, int out_planes, hipStream_t s);
+int launch_pf_dot(const char* what, const float* d_out, int out_planes, const float* dx, const float* row, const float* coef, const void* state, int B, int64_t chw,
+                  float* scratch, float* s_out, double* acc, hipStream_t s);
+int launch_pf_stage(const char* what, float* x, const float* model_out, int out_planes, float* xs, float* es, const float* row, const float* coef,
+                    const int64_t* t_table, void* state, int advance_offset, int B, int64_t chw, hipStream_t s);
 int launch_label_dropout(const int64_t* labels, int B, int K, float p, uint64_t seed, uint64_t offset, int64_t* out, int* status, hipStream_t s);
 // guidance.hip: the classifier head (forward; backward into the top map's gradient + the per-image rows of its parameter gradients;
 // the batch reduction of those rows) and the row-wise log-softmax of the classifier's loss / guidance gradient

@@ -1360,7 +1360,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 120; }  // 120: DMME_CHAIN_DPS, dmme_dps_capacity, dmme_dps_measure, dmme_dps_adjoint, dmme_chain_adjoint_dps, dmme_dps_step, dmme_chain_update_dps, dmme_dps_chain_step; 119: dmme_cm_target, dmme_cm_loss, dmme_ema_lerp; 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 121; }  // 121: DMME_CHAIN_PFODE, dmme_rademacher, dmme_pf_probe, dmme_chain_probe_pf, dmme_pf_dequantize, dmme_pf_scratch_floats, dmme_pf_dot, dmme_chain_dot_pf, dmme_pf_prior, dmme_pf_stage, dmme_chain_stage_pf, dmme_pf_chain_step, dmme_pf_ll_chain_step; 120: DMME_CHAIN_DPS, dmme_dps_capacity, dmme_dps_measure, dmme_dps_adjoint, dmme_chain_adjoint_dps, dmme_dps_step, dmme_chain_update_dps, dmme_dps_chain_step; 119: dmme_cm_target, dmme_cm_loss, dmme_ema_lerp; 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1920,6 +1920,49 @@ DMME_API int dmme_dps_chain_step(const dmme_plan* plan, const void* packed, cons
     const int64_t* t_dev = (const int64_t*)state + 1;
     if (int rc = dmme_unet_backward_input(plan, packed, packed_bwd, x, t_dev, 1, d_out, workspace, bwd_workspace, nullptr, dx, stream)) return rc;
     return launch_dps_update("dps_chain_step", x, model_out, g, dx, sumsq, nullptr, nullptr, step_coef, t_table, state, B, C, H, W, planes, (hipStream_t)stream);
+}
+
+// Probability-flow ODE: kind DMME_CHAIN_PFODE, one Heun STAGE per loop index (csrc/pfode.hip).  The sampling / encoding step is the front
+// half every chain step has and the four-term stage update; the tables alone say which way the walk goes.
+DMME_API int dmme_pf_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, float* xs, float* es,
+                                const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && x && model_out && workspace && xs && es && step_coef && t_table && state, DMME_ERR_INVALID, "pf_chain_step: null argument");
+    int planes = 0;
+    if (int rc = chain_step_front("pf_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_PFODE, false, 0, nullptr, 8, 0, state, stream,
+                                  planes))
+        return rc;
+    return launch_pf_stage("pf_chain_step", x, model_out, planes, xs, es, nullptr, step_coef, t_table, state, 0, plan->B,
+                           (int64_t)plan->cfg.in_channels * plan->H * plan->W, (hipStream_t)stream);
+}
+
+// ... and the likelihood's stage, which differentiates the denoiser as DPS does: the keep form of the forward, the Rademacher probe z
+// written as d_out, the input-only backward (dx = J^T z), the probe dot into the per-image double accumulator, the stage update
+DMME_API int dmme_pf_ll_chain_step(const dmme_plan* plan, const void* packed, const void* packed_bwd, float* x, float* model_out, void* workspace,
+                                   void* bwd_workspace, float* xs, float* es, float* d_out, float* dx, float* scratch, float* s_out, double* acc,
+                                   const float* step_coef, const int64_t* t_table, void* state, void* stream) {
+    DMME_REQUIRE(plan && packed && packed_bwd && x && model_out && workspace && bwd_workspace && xs && es && d_out && dx && scratch && s_out && acc && step_coef &&
+                     t_table && state,
+                 DMME_ERR_INVALID, "pf_ll_chain_step: null argument");
+    DMME_REQUIRE(!plan->cond && (plan->cfg.arch == DMME_ARCH_DDPM || plan->cfg.arch == DMME_ARCH_IDDPM), DMME_ERR_INVALID,
+                 "pf_ll_chain_step: needs an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan (got architecture %d%s)", plan->cfg.arch,
+                 plan->cond ? ", class-conditional" : "");
+    DMME_REQUIRE(plan->pred == DMME_PRED_EPS, DMME_ERR_UNSUPPORTED,
+                 "pf_ll_chain_step: the plan's network predicts %s; the derivative of the x0 / v adapter is not built: an eps network only",
+                 plan->pred == DMME_PRED_X0 ? "x0" : "v");
+    DMME_REQUIRE(plan->thr_mode == DMME_THRESHOLD_NONE, DMME_ERR_UNSUPPORTED,
+                 "pf_ll_chain_step: the plan thresholds x0 (mode %d); the derivative of the clip is not built: threshold none only", plan->thr_mode);
+    DMME_REQUIRE(!plan->mix, DMME_ERR_UNSUPPORTED, "pf_ll_chain_step: precision fp16r32 is an inference mode (no backward)");
+    int planes = 0;
+    if (int rc = chain_step_front("pf_ll_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_PFODE, false, 0, nullptr, 8, 0, state,
+                                  stream, planes, true))
+        return rc;
+    const int B = plan->B;
+    const int64_t chw = (int64_t)plan->cfg.in_channels * plan->H * plan->W;
+    if (int rc = launch_pf_probe("pf_ll_chain_step", d_out, state, 0, 0, B, chw, planes, (hipStream_t)stream)) return rc;
+    const int64_t* t_dev = (const int64_t*)state + 1;
+    if (int rc = dmme_unet_backward_input(plan, packed, packed_bwd, x, t_dev, 1, d_out, workspace, bwd_workspace, nullptr, dx, stream)) return rc;
+    if (int rc = launch_pf_dot("pf_ll_chain_step", d_out, planes, dx, nullptr, step_coef, state, B, chw, scratch, s_out, acc, (hipStream_t)stream)) return rc;
+    return launch_pf_stage("pf_ll_chain_step", x, model_out, planes, xs, es, nullptr, step_coef, t_table, state, 1, B, chw, (hipStream_t)stream);
 }
 
 // Dhariwal & Nichol 2021, Algorithm 1 (DDPM) / 2 (DDIM): between the forward and the update, the classifier's forward, the log-softmax

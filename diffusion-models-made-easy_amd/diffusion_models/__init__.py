@@ -6,5 +6,6 @@ from .repaint import RePaint, PaintChainRunner, repaint_levels, repaint_rows  # 
 from .ilvr import ILVR, LikeChainRunner, ilvr_rows, lowpass_matrix  # noqa: F401
 from .ddnm import DDNM, RestoreChainRunner, ddnm_rows  # noqa: F401
 from .dps import DPS, PosteriorChainRunner, SeparableOperator, dps_rows  # noqa: F401
+from .pfode import ProbabilityFlow, FlowChainRunner, LikelihoodChainRunner, LogLikelihood, pf_rows, pf_grid  # noqa: F401
 from .distill import ProgressiveDistillation, distill_rows, distill_grid  # noqa: F401
 from .consistency import ConsistencyDistillation, ConsistencySampler, consistency_rows, consistency_sampler_rows, consistency_grid  # noqa: F401

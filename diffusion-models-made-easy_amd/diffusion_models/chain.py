@@ -41,6 +41,8 @@ def chain_draws(kind: int, rows) -> bool:
         return any(r[2] != 0.0 or r[7] != 0.0 for r in rows)
     if kind == _lib.CHAIN_DPS:  # (c2 of the reverse step's noise)
         return any(r[2] != 0.0 for r in rows)
+    if kind == _lib.CHAIN_PFODE:  # (w of the likelihood's trace term: a stage that carries one draws a Rademacher probe)
+        return any(r[4] != 0.0 for r in rows)
     return True
 
 

@@ -842,6 +842,72 @@ DMME_API int dmme_dps_chain_step(const dmme_plan* plan, const void* packed, cons
                                  void* bwd_workspace, const float* y, const float* mask, const float* Kh, const float* Kw, int h, int w, float* g, float* d_out,
                                  float* dx, float* sumsq, const float* step_coef, const int64_t* t_table, void* state, void* stream);
 
+/* ---- probability-flow ODE (Song et al., ICLR 2021, section 4.3 and appendix D.2): Heun sampler, latent encoding, log-likelihood
+ * (csrc/pfode.hip) ---------------------------------------------------------------------------------------------------------------------
+ * With sig(t) = sqrt((1 - abar_t) / abar_t) and xbar = x / sqrt(abar) the ODE is d xbar / d sig = eps(x, t), and along a solution
+ * d log pbar / d sig = -sqrt(abar) tr(d eps / d x).  The nodes are integer timesteps g_0 < ... < g_n.  A Heun (trapezoid) step a -> b, in
+ * either direction, has k0 = sqrt(abar_b / abar_a), k1 = sqrt(1 - abar_b) - k0 sqrt(1 - abar_a), h = sig(b) - sig(a) and two stages:
+ *     A (at x_a, t = a):  e_a = eps(x_a, a);  x' = k0 x_a + k1 e_a                       the paper-form DDIM step, eta = 0
+ *     B (at x', t = b):   e_b = eps(x', b);   x_b = k0 x_a + (k1 / 2)(e_a + e_b)
+ * With the likelihood on, a stage also draws a Rademacher probe z, forms s[img] = sum z (J^T z) with J^T z from dmme_unet_backward_input
+ * (d_out = z in the eps plane, 0 in the v plane of a two-plane output) and adds w s to a per-image double: w_A = (h / 2) sqrt(abar_a),
+ * w_B = (h / 2) sqrt(abar_b).  Walking up from x_{g_0} := x_0:  log p(x_0) = log N(x_T; 0, I) + (D / 2)(ln abar_{g_n} - ln abar_{g_0}) + acc.
+ * Kind DMME_CHAIN_PFODE = 14 has entry points and a table layout of its own: dmme_chain_step and dmme_chain_update refuse it.
+ *   step_coef float[n+1][8], per loop index (one STAGE per index, the index runs down): {c0, c1, c2, c3, w, save, 0, 0}, folded by the
+ *             host in float64 and rounded once.  A: (k0, 0, k1, 0, w_A, 1); B: (0, k0, k1/2, k1/2, w_B, 0); the closing Euler stage
+ *             g_0 -> 0 of a decoding walk: (1/sqrt(abar), 0, -sqrt(1 - abar)/sqrt(abar), 0, 0, 0) at g_0.  Row 0 is never stepped from.
+ *   t_table   int64[n+1]: the timestep the network is evaluated at from loop index i
+ *   update    THE stage update, one device function (pf_update) that the eager and the chain form both call, in this order:
+ *                 r = 0;  r = c0 * x (rounded);  r = fma(c1, xs, r);  r = fma(c2, e, r);  r = fma(c3, es, r);  x_new = r
+ *             a term whose coefficient is 0 is skipped and its operand is not read (xs and es may hold anything in front of a stage A).
+ *             Where save != 0, xs <- x and es <- e take the values from before the update.  e is the eps plane of model_out
+ *             (out_planes 1 or 2).  |x_new - exact| <= 4 * 2^-24 (|c0 x| + |c1 xs| + |c2 e| + |c3 es|).  Quads where chw % 4 == 0 (or
+ *             B = 1 with one plane) and every pointer is 16-byte aligned, the last numel % 4 elements one by one; else element by element.
+ *   probe     the span contract of the Philox section above holds unchanged: quad q uses counter offset + q and fills elements
+ *             4q .. 4q+3 of the B*chw values, the last quad cut off at numel; element i is -1.0f where bit 31 of its word is set, else
+ *             +1.0f.  dmme_pf_probe writes it into a buffer of the network output's layout (B, out_planes * chw): the eps plane = z,
+ *             the v plane = 0; the dot reads z back from there.  dmme_rademacher(out, numel, ...) is the same launch with one plane.
+ *             A likelihood chain moves the offset by B*chw/4 per stage.
+ *   dot       s[img] = sum z dx: block (p, img) of a grid (parts, B) sums its share (each thread its elements in ascending order by fma,
+ *             the wave by a butterfly, the waves in index order) into scratch[img * parts + p]; parts depends on chw alone.  ONE
+ *             finishing launch adds the partials in index order in double, writes s_out[img] = (float)S and does
+ *             acc[img] += (double)w * (double)s_out[img] (two roundings).  No atomics, no workgroup waits for another: equal inputs give
+ *             equal bits, and an image's value does not depend on its place in a larger batch.
+ *             |s - exact| <= (chw + 8) 2^-24 sum |z dx|.  scratch: dmme_pf_scratch_floats(B, chw) floats.
+ *   prior     dmme_pf_prior: out[img] = -(1/2) sum x^2 - (chw / 2) ln(2 pi) in double, the same two launches over (x, x).
+ *   dequantize  dmme_pf_dequantize: x += (u - 0.5) * fp32(2 / 255) with the contract's u of the span (seed, offset, numel); the difference is
+ *             exact, the product and the sum round once each.
+ * dmme_pf_stage / dmme_pf_dot take their row (8 floats) from HOST memory; dmme_chain_stage_pf / dmme_chain_dot_pf / dmme_chain_probe_pf
+ * read it (and the probe's seed and offset) at the loop state, give the same bits, and only the stage advances the state (i -= 1,
+ * t = t_table[i]; the offset by B*chw/4 where advance_offset != 0).
+ * dmme_pf_chain_step = the no-grad forward at t = state.t behind the front every chain step has (the x0 / v adapter, x0 thresholding), then
+ * dmme_chain_stage_pf: encoding and decoding differ only in their tables.  dmme_pf_ll_chain_step = dmme_unet_forward (the KEEP form:
+ * `packed` holds the unfolded weights), dmme_chain_probe_pf, dmme_unet_backward_input, dmme_chain_dot_pf, dmme_chain_stage_pf: one
+ * keep-forward plus one input-backward per stage; plans as dmme_dps_chain_step's (unconditional, eps, no threshold).  Both are capturable
+ * and never synchronise with the host.
+ * dmme_unet_backward_input leaves the forward's saved context intact: it reads the forward's workspace, writes its gradients into
+ * bwd_workspace and d_x, and the only part of `workspace` it writes is the split-K scratch of the small-map convolutions, which
+ * holds no saved activation (the forward uses it the same way).  A second probe of the same forward would cost one more input-backward and no forward (not built: tile the batch). */
+enum { DMME_CHAIN_PFODE = 14 };
+DMME_API int dmme_rademacher(float* out, int64_t numel, uint64_t seed, uint64_t offset, void* stream);
+DMME_API int dmme_pf_probe(float* d_out, int B, int64_t chw, int out_planes, uint64_t seed, uint64_t offset, void* stream);
+DMME_API int dmme_chain_probe_pf(float* d_out, const void* state, int B, int64_t chw, int out_planes, void* stream);
+DMME_API int dmme_pf_dequantize(float* x, int64_t numel, uint64_t seed, uint64_t offset, void* stream);
+DMME_API int64_t dmme_pf_scratch_floats(int B, int64_t chw);
+DMME_API int dmme_pf_dot(const float* d_out, int out_planes, const float* dx, const float* row, int B, int64_t chw, float* scratch, float* s_out, double* acc,
+                         void* stream);
+DMME_API int dmme_chain_dot_pf(const float* d_out, int out_planes, const float* dx, const float* step_coef, const void* state, int B, int64_t chw,
+                               float* scratch, float* s_out, double* acc, void* stream);
+DMME_API int dmme_pf_prior(const float* x, int B, int64_t chw, float* scratch, double* out, void* stream);
+DMME_API int dmme_pf_stage(float* x, const float* model_out, int out_planes, float* xs, float* es, const float* row, int B, int64_t chw, void* stream);
+DMME_API int dmme_chain_stage_pf(float* x, const float* model_out, int out_planes, float* xs, float* es, const float* step_coef, const int64_t* t_table,
+                                 void* state, int advance_offset, int B, int64_t chw, void* stream);
+DMME_API int dmme_pf_chain_step(const dmme_plan* plan, const void* packed, float* x, float* model_out, void* workspace, float* xs, float* es,
+                                const float* step_coef, const int64_t* t_table, void* state, void* stream);
+DMME_API int dmme_pf_ll_chain_step(const dmme_plan* plan, const void* packed, const void* packed_bwd, float* x, float* model_out, void* workspace,
+                                   void* bwd_workspace, float* xs, float* es, float* d_out, float* dx, float* scratch, float* s_out, double* acc,
+                                   const float* step_coef, const int64_t* t_table, void* state, void* stream);
+
 /* ---- progressive distillation (Salimans & Ho, ICLR 2022, Algorithm 2): training an N-step sampler from a 2N-step one (csrc/distill.hip) ----
  * The grid is the one of GeneralizedDDIM(..., "linear"): tau = linear_tau(T, 2N); student index i in 1..N stands for the timesteps
  * t = tau[2i], m = tau[2i-1], e = tau[2i-2].  One training step: z_t = alpha_t x0 + sigma_t eps; the frozen teacher at (z_t, t) gives the x0
