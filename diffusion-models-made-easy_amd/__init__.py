@@ -21,6 +21,7 @@ from .diffusion_models import DPS, PosteriorChainRunner, SeparableOperator, dps_
 from .diffusion_models import ProbabilityFlow, FlowChainRunner, LikelihoodChainRunner, LogLikelihood, pf_rows, pf_grid  # noqa: F401
 from .diffusion_models import ProgressiveDistillation, distill_rows, distill_grid  # noqa: F401
 from .diffusion_models import ConsistencyDistillation, ConsistencySampler, consistency_rows, consistency_sampler_rows, consistency_grid  # noqa: F401
+from .diffusion_models import AnalyticDPM, analytic_rows, moment_schedule  # noqa: F401
 from .lit_modules import LitDDPM, LitDDIM, LitIDDPM, LitClassifierFreeDDPM, LitDistill, LitConsistency  # noqa: F401
 from .lr_scheduler import LinearDecayLR  # noqa: F401
 from .models.ddpm import UNet  # noqa: F401
@@ -34,4 +35,5 @@ __all__ = ["gaussian", "gaussian_like", "uniform_int", "pad", "denorm", "norm", 
            "RePaint", "PaintChainRunner", "repaint_levels", "repaint_rows", "ILVR", "LikeChainRunner", "ilvr_rows", "lowpass_matrix", "make_history", "save_png", "HistoryRecorder", "history_ordinals", "GenerateImage",
            "ProgressiveDistillation", "distill_rows", "distill_grid", "LitDistill", "LinearDecayLR", "DDNM", "RestoreChainRunner", "ddnm_rows", "DPS", "PosteriorChainRunner", "SeparableOperator", "dps_rows",
            "ConsistencyDistillation", "ConsistencySampler", "consistency_rows", "consistency_sampler_rows", "consistency_grid", "LitConsistency",
-           "ProbabilityFlow", "FlowChainRunner", "LikelihoodChainRunner", "LogLikelihood", "pf_rows", "pf_grid"]
+           "ProbabilityFlow", "FlowChainRunner", "LikelihoodChainRunner", "LogLikelihood", "pf_rows", "pf_grid",
+           "AnalyticDPM", "analytic_rows", "moment_schedule"]

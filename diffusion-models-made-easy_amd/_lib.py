@@ -208,6 +208,8 @@ PROTOTYPES = {
     "dmme_iddpm_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _f, _f, _vp, _vp, _f, _vp, _vp]),
     "dmme_iddpm_loss_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _f, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "dmme_iddpm_prior_rows": (_i, [_vp, _i, _i64, _f, _vp, _vp]),
+    "dmme_analytic_moment": (_i, [_vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmme_analytic_vlb_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp]),
     "dmme_tsampler_draw": (_i, [_vp, _vp, _i, _i, _f, _u64, _u64, _i, _vp, _vp, _vp, _vp]),
     "dmme_tsampler_update": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "dmme_conv2d": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),

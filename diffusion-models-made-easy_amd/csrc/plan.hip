@@ -1360,7 +1360,7 @@ static int upload_tables(dmme_plan* P) {
 extern "C" {
 
 DMME_API const char* dmme_last_error(void) { return g_err; }
-DMME_API int dmme_version(void) { return 121; }  // 121: DMME_CHAIN_PFODE, dmme_rademacher, dmme_pf_probe, dmme_chain_probe_pf, dmme_pf_dequantize, dmme_pf_scratch_floats, dmme_pf_dot, dmme_chain_dot_pf, dmme_pf_prior, dmme_pf_stage, dmme_chain_stage_pf, dmme_pf_chain_step, dmme_pf_ll_chain_step; 120: DMME_CHAIN_DPS, dmme_dps_capacity, dmme_dps_measure, dmme_dps_adjoint, dmme_chain_adjoint_dps, dmme_dps_step, dmme_chain_update_dps, dmme_dps_chain_step; 119: dmme_cm_target, dmme_cm_loss, dmme_ema_lerp; 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
+DMME_API int dmme_version(void) { return 122; }  // 122: dmme_analytic_moment, dmme_analytic_vlb_rows; 121: DMME_CHAIN_PFODE, dmme_rademacher, dmme_pf_probe, dmme_chain_probe_pf, dmme_pf_dequantize, dmme_pf_scratch_floats, dmme_pf_dot, dmme_chain_dot_pf, dmme_pf_prior, dmme_pf_stage, dmme_chain_stage_pf, dmme_pf_chain_step, dmme_pf_ll_chain_step; 120: DMME_CHAIN_DPS, dmme_dps_capacity, dmme_dps_measure, dmme_dps_adjoint, dmme_chain_adjoint_dps, dmme_dps_step, dmme_chain_update_dps, dmme_dps_chain_step; 119: dmme_cm_target, dmme_cm_loss, dmme_ema_lerp; 118: DMME_CHAIN_DDNM, dmme_ddnm_measure, dmme_ddnm_step, dmme_chain_update_ddnm, dmme_ddnm_chain_step, dmme_ddnm_band_capacity; 117: dmme_distill_noise, dmme_distill_mid, dmme_distill_target; 116: DMME_CHAIN_ILVR, dmme_lowpass (+ _lds_capacity, _scratch_bytes), dmme_ilvr_step, dmme_chain_update_ilvr, dmme_ilvr_chain_step; 115: dmme_unet_pack_folded, dmme_unet_plan_num_launches_nograd / _num_folded, dmme_attention_fold, dmme_attention_block; 114: DMME_PRED_*, dmme_pred_to_eps, dmme_unet_plan_set_prediction, dmme_q_sample_pred, dmme_mse_loss_rows; 113: dmme_grid_tile; 112: DMME_CHAIN_REPAINT, dmme_repaint_step, dmme_chain_update_repaint, dmme_repaint_chain_step; 111: DMME_CHAIN_DPMPP / _DPMPP_CFG, dmme_dpmpp_step, dmme_chain_update_dpmpp, dmme_dpmpp_chain_step and their cfg forms, the loop state's history-valid word; 110: DMME_ARCH_DDPM_COND, dmme_unet_forward_cond / _backward_cond / _backward_input_cond, DMME_CHAIN_DDPM_CFG / _GDDIM_CFG, dmme_cfg_step, dmme_chain_update_cfg, dmme_cfg_chain_step, dmme_label_dropout; 109: dmme_iddpm_loss_rows, dmme_iddpm_prior_rows, dmme_tsampler_draw, dmme_tsampler_update; 108: DMME_CHAIN_GDDIM, dmme_gddim_step, dmme_chain_update_gddim, dmme_slerp; 107: DMME_ARCH_CLASSIFIER, dmme_unet_backward_input, guided chain; 106: dmme_unet_debug_read_grad; 105: dmme_attention_proj, dmme_unet_forward_nograd
 DMME_API int dmme_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

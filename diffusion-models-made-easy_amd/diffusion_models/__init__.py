@@ -9,3 +9,4 @@ from .dps import DPS, PosteriorChainRunner, SeparableOperator, dps_rows  # noqa:
 from .pfode import ProbabilityFlow, FlowChainRunner, LikelihoodChainRunner, LogLikelihood, pf_rows, pf_grid  # noqa: F401
 from .distill import ProgressiveDistillation, distill_rows, distill_grid  # noqa: F401
 from .consistency import ConsistencyDistillation, ConsistencySampler, consistency_rows, consistency_sampler_rows, consistency_grid  # noqa: F401
+from .analytic import AnalyticDPM, analytic_rows, moment_schedule  # noqa: F401

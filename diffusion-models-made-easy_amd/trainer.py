@@ -27,6 +27,10 @@ checkpoint callbacks, ...):
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler dps --operator blur --blur-size 9 --blur-sigma 2 --zeta 1 --sigma-y 0.05 --image X.npy --save OUT.npy   (DPS: deblurring a noisy measurement; --operator identity | blur | bicubic | average [--down-scale s], --measurement Y.npy, --mask inpaints)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler heun --sample-steps 30 [--tau-schedule logsnr]   (the Heun walk on the probability-flow ODE: two network evaluations per node)
   python -m dmme_amd.trainer evaluate --config configs/ddpm/cifar10.yaml --ckpt-path OUT.ckpt --nodes 100 --image X.npy [--dequantize] [--num-images K]   (bits/dim under the probability-flow ODE, mean and per image; --data config: the YAML's data module)
+  python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler analytic --sample-steps 20 [--eta 1] [--tau-schedule linear] [--moments G.npy | --data config [--moment-images 64]] [--save-checkpoint OUT.ckpt]
+                                    (Analytic-DPM: the optimal reverse variance on a K-step grid; the moments come from G.npy, from the checkpoint, or are estimated first on the YAML's data module)
+  python -m dmme_amd.trainer evaluate --config configs/ddpm/cifar10.yaml --ckpt-path OUT.ckpt --sampler analytic --variance analytic --sample-steps 100 --image X.npy
+                                    (bits/dim by the K-step variational bound, with its prior, KL sum and decoder parts; --variance analytic | beta | beta-tilde)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --sampler sdedit--image X.npy --strength 0.5 --save OUT.npy   (SDEdit editing)
   python -m dmme_amd.trainer sample --config configs/ddpm/cifar10.yaml --num-images 8 --vis-length 20 --grid OUT.png   (the denoising history as a PNG; any sampler)
   python -m dmme_amd.trainer sample --config configs/cfg/cifar10.yaml --labels 3 --guidance-scale 2.5 --threshold dynamic   (x0 thresholding in front of the update: none | static | dynamic [--threshold-percentile P]; any sampler)
@@ -264,6 +268,7 @@ def _check_solver_args(args) -> None:
     # (--tau-schedule linear / quadratic also goes with --sampler ddim-paper: the grid of GeneralizedDDIM; --clip-x0 also with `distill`)
     paper_tau = args.sampler == "ddim-paper" and args.tau_schedule in ("linear", "quadratic")
     paper_tau = paper_tau or args.sampler == "heun" or args.command == "evaluate"  # (the probability-flow ODE's grid takes all three)
+    paper_tau = paper_tau or args.sampler == "analytic"  # (`_check_analytic_args`: linear | quadratic)
     solver_flags = [f for f, given in (("--solver-order", args.solver_order is not None), ("--tau-schedule", args.tau_schedule is not None and not paper_tau),
                                        ("--clip-x0", args.clip_x0 and args.command not in ("distill", "consistency"))) if given]
     if args.sampler != "dpm++":
@@ -458,6 +463,10 @@ def _check_flow_args(args) -> None:
     """what goes with --sampler heun and with `evaluate` (the probability-flow ODE: diffusion_models/pfode.py) and what does not; exits
     with a message (before anything touches the GPU)"""
     own = [f for f, given in (("--nodes", args.nodes is not None), ("--dequantize", args.dequantize)) if given]
+    if args.command == "evaluate" and args.sampler == "analytic":
+        if own:
+            raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to the probability-flow likelihood, not to --sampler analytic (--sample-steps K sets its grid)")
+        return  # (`_check_analytic_args` has looked at the rest)
     if args.command != "evaluate":
         if own:
             raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to `evaluate`")
@@ -503,22 +512,130 @@ def _flow_process(module, args, nodes_default: int):
         raise SystemExit(f"{'--sampler heun' if args.command == 'sample' else 'evaluate'}: {exc}")
 
 
+def _data_loader(conf, batch_size: int):
+    """the train loader of the YAML's data module at this batch size (random bytes where the dataset files are absent)"""
+    dm = _instantiate(conf["data_spec"])
+    dm.batch_size = batch_size
+    try:
+        dm.prepare_data()
+    except FileNotFoundError as e:
+        print(json.dumps({"data": "random bytes (dataset files absent)", "reason": str(e)[:160]}), flush=True)
+        dm.synthetic = True
+    dm.setup("fit")
+    return dm.train_dataloader()
+
+
+def _evaluate_images(args, conf) -> torch.Tensor:
+    """the images `evaluate` scores: --image X.npy, or the first batch of the YAML's data module"""
+    if args.image is not None:
+        return _load_npy(args.image, "--image")[: args.num_images]
+    return next(iter(_data_loader(conf, args.num_images)))[0][: args.num_images]
+
+
+def _check_analytic_args(args) -> None:
+    """what goes with --sampler analytic (Analytic-DPM: diffusion_models/analytic.py) and what does not; exits with a message (before
+    anything touches the GPU)"""
+    own = [f for f, v in (("--variance", args.variance), ("--moments", args.moments), ("--moment-images", args.moment_images)) if v is not None]
+    if args.sampler != "analytic":
+        if own:
+            raise SystemExit(f"{', '.join(own)} belong{'s' if len(own) == 1 else ''} to --sampler analytic")
+        return
+    name = "--sampler analytic"
+    if args.command not in ("sample", "evaluate"):
+        raise SystemExit(f"{name} belongs to `sample` and `evaluate`: it needs no training, the network is the config's own")
+    for flag, v in (("--steps", args.steps), ("--labels", args.labels), ("--guidance-scale", args.guidance_scale), ("--max-steps", args.max_steps)):
+        if v is not None:
+            raise SystemExit(f"{flag} does not go with {name}: it runs whole chains of an unconditional network (--sample-steps K sets the grid)")
+    if args.sample_steps is not None and args.sample_steps < 1:
+        raise SystemExit("--sample-steps must be at least 1")
+    if args.tau_schedule == "logsnr":
+        raise SystemExit(f"--tau-schedule logsnr does not go with {name}: its grid is GeneralizedDDIM's (linear | quadratic)")
+    if args.eta is not None and not 0.0 <= args.eta <= 1.0:
+        raise SystemExit(f"--eta {args.eta} outside [0, 1]")
+    if args.moments is not None and args.moment_images is not None:
+        raise SystemExit("--moments G.npy installs a table, --moment-images M estimates one: give one of them")
+    if args.moment_images is not None and args.moment_images < 1:
+        raise SystemExit("--moment-images must be at least 1")
+    if args.moment_images is not None and args.data != "config":
+        raise SystemExit("--moment-images estimates the moments on data: it needs --data config (the YAML's data module)")
+    if args.command == "sample":
+        if args.variance is not None:
+            raise SystemExit("--variance belongs to `evaluate`: sampling uses the analytic variance")
+        return
+    if args.eta not in (None, 1.0):
+        raise SystemExit(f"--eta {args.eta} does not go with `evaluate`: the bound needs eta = 1 (the KL against a narrower posterior grows without limit)")
+    if args.num_images < 1:
+        raise SystemExit("--num-images must be at least 1")
+    if args.image is None and args.data != "config":
+        raise SystemExit("`evaluate` needs --image X.npy (float32 in [-1, 1]) or --data config (the YAML's data module)")
+
+
+def _analytic_process(module, args, conf, B: int, ckpt):
+    """AnalyticDPM over the network, the prediction and the thresholding of the process the YAML built, with its moments: --moments G.npy,
+    else the checkpoint's where they cover the grid, else estimated here on the YAML's data module (--data config; --moment-images M per
+    timestep, default 64).  Nothing is estimated on made-up images: such moments would travel in a checkpoint looking like any others.
+    The module goes into eval mode first: the statistic is that of the network that samples, not of one that draws dropout masks."""
+    import numpy as np
+
+    from .diffusion_models import AnalyticDPM
+
+    module.eval()
+    old = module.diffusion_model
+    K = min(50, old.timesteps) if args.sample_steps is None else args.sample_steps
+    try:
+        proc = AnalyticDPM(old.model, old.timesteps, K, args.tau_schedule or "linear", 1.0 if args.eta is None else args.eta, prediction=getattr(old, "prediction", "eps"),
+                           threshold=getattr(old, "threshold", "none"), threshold_percentile=getattr(old, "threshold_percentile", 0.995))
+    except ValueError as exc:
+        raise SystemExit(f"--sampler analytic: {exc}")
+    if not torch.equal(proc.alpha_bar.reshape(-1).cpu(), old.alpha_bar.reshape(-1).to(torch.float32).cpu()):
+        raise SystemExit("--sampler analytic runs on the linear noise schedule of the DDPM / DDIM configs; this config's process has another one")
+    proc = proc.cuda()
+    tau = proc._tau_host[1:]
+    state = (ckpt or {}).get("state_dict") or {}
+    g_sum, g_count = state.get("diffusion_model._g_sum"), state.get("diffusion_model._g_count")
+    source = None
+    if args.moments is not None:
+        try:
+            proc.set_moments(np.load(args.moments, allow_pickle=False))
+        except (OSError, ValueError) as exc:
+            raise SystemExit(f"--moments {args.moments}: {exc}")
+        source = "file"
+    elif args.moment_images is None and g_sum is not None and g_count is not None and tuple(g_sum.shape) == tuple(proc._g_sum.shape) and bool((g_count[tau] > 0).all()):
+        proc._g_sum.copy_(g_sum)
+        proc._g_count.copy_(g_count)
+        proc._moments_changed()
+        source = "checkpoint"
+    else:
+        if args.data != "config" or not conf["data_spec"]:
+            raise SystemExit("--sampler analytic: no moments for this grid in the checkpoint; give --moments G.npy, or --data config to estimate them on the YAML's data module")
+        proc.estimate_moments(_data_loader(conf, B), images_per_timestep=args.moment_images or 64, batch_size=B, seed=None)
+        source = "estimated on the data module"
+    return proc, source
+
+
+def _evaluate_analytic(module, args, conf, B: int, ckpt) -> int:
+    """`evaluate --sampler analytic`: bits/dim by the K-step variational bound under --variance, with its three parts, as one JSON line"""
+    module.eval()
+    proc, source = _analytic_process(module, args, conf, B, ckpt)
+    images = _evaluate_images(args, conf)
+    t0 = time.perf_counter()
+    parts = [proc.bits_per_dim(images[k:k + B].cuda(), variance=args.variance or "analytic") for k in range(0, images.shape[0], B)]
+    torch.cuda.synchronize()
+    total = torch.cat([p.total for p in parts]).cpu()
+    prior = torch.cat([p.prior for p in parts]).cpu()
+    terms = torch.cat([p.terms for p in parts]).cpu()
+    mean = lambda v: round(float(v.mean()), 6)
+    print(json.dumps({"images": list(images.shape), "precision": conf["precision"], "sample_steps": proc.sub_timesteps, "tau_schedule": proc.tau_schedule,
+                      "variance": args.variance or "analytic", "moments": source, "bits_per_dim": mean(total), "prior": mean(prior), "kl_sum": mean(terms[:, 1:].sum(dim=1)),
+                      "decoder": mean(terms[:, 0]), "per_image": [round(float(v), 6) for v in total], "seconds": round(time.perf_counter() - t0, 3)}))
+    return 0
+
+
 def _evaluate(module, args, conf, B: int) -> int:
     """`evaluate`: bits/dim of images under the probability-flow ODE of the checkpoint's network, mean and per image, as one JSON line"""
     module.eval()
     flow = _flow_process(module, args, 100).cuda()
-    if args.image is not None:
-        images = _load_npy(args.image, "--image")[: args.num_images]
-    else:
-        dm = _instantiate(conf["data_spec"])
-        dm.batch_size = args.num_images
-        try:
-            dm.prepare_data()
-        except FileNotFoundError as e:
-            print(json.dumps({"data": "random bytes (dataset files absent)", "reason": str(e)[:160]}), flush=True)
-            dm.synthetic = True
-        dm.setup("fit")
-        images = next(iter(dm.train_dataloader()))[0][: args.num_images]
+    images = _evaluate_images(args, conf)
     t0 = time.perf_counter()
     try:
         bpd = torch.cat([flow.bits_per_dim(images[k:k + B].cuda(), dequantize=args.dequantize) for k in range(0, images.shape[0], B)])
@@ -803,7 +920,7 @@ def main(argv=None):
     ap.add_argument("--image-size", type=int, default=None, help="sample: image height = width (default: what the YAML's data module yields)")
     ap.add_argument("--precision", default=None, help="override the YAML's trainer.precision (fp32 | bf16 | fp16 | bf16x3)")
     ap.add_argument("--steps", type=int, default=None, help="sample: stop after this many denoising steps")
-    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr", "ddnm", "dps", "heun"],
+    ap.add_argument("--sampler", default="config", choices=["config", "ddim-paper", "dpm++", "repaint", "sdedit", "ilvr", "ddnm", "dps", "heun", "analytic"],
                     help="sample: 'ddim-paper' swaps the YAML's DDIM for GeneralizedDDIM (the published update) over the same network and tau table; "
                          "'dpm++' samples the YAML's network and noise schedule with DPM-Solver++(2M) in --sample-steps steps (default 20); "
                          "'repaint' inpaints --image where --mask is 0, 'sdedit' edits --image at --strength (any unconditional config; --sample-steps: grid levels, default 250); "
@@ -813,7 +930,13 @@ def main(argv=None):
                          "'dps' restores images from a noisy --measurement (or from --image, degraded first) by posterior sampling: --operator identity | blur | bicubic | "
                          "average, step size --zeta, inpainting --mask, noise level --sigma-y (any unconditional eps config; --sample-steps, default 100); "
                          "'heun' samples with the second-order Heun walk on the probability-flow ODE (any unconditional config; --sample-steps N nodes, default 50, two "
-                         "network evaluations per node; --tau-schedule linear (default) | quadratic | logsnr)")
+                         "network evaluations per node; --tau-schedule linear (default) | quadratic | logsnr); "
+                         "'analytic' samples with Analytic-DPM's optimal reverse variance on GeneralizedDDIM's grid (any unconditional config on the linear noise schedule; "
+                         "--sample-steps K, default 50; --eta, default 1; --tau-schedule linear (default) | quadratic; the moments: --moments G.npy, the checkpoint's, or "
+                         "with --data config estimated first, --moment-images M per timestep); evaluate --sampler analytic: bits/dim by the K-step variational bound under --variance")
+    ap.add_argument("--variance", default=None, choices=["analytic", "beta", "beta-tilde"], help="evaluate --sampler analytic: the reverse variance of the bound (default analytic)")
+    ap.add_argument("--moments", default=None, help="--sampler analytic: .npy, float64[T+1], the table G_t = E mean eps_theta^2 (entry 0 unused)")
+    ap.add_argument("--moment-images", type=int, default=None, help="--sampler analytic --data config: estimate the moments on this many images per timestep, whatever the checkpoint holds (default 64 where none are at hand)")
     ap.add_argument("--nodes", type=int, default=None, help="evaluate: nodes of the likelihood's grid (default 100; two network evaluations and two input gradients per node)")
     ap.add_argument("--dequantize", action="store_true", help="evaluate: add uniform noise of one pixel step (2/255) to the images first, as published bits/dim figures do")
     ap.add_argument("--image", default=None, help="sample --sampler repaint / sdedit: .npy, float32 in [-1, 1], (B, C, H, W) or (C, H, W)")
@@ -875,6 +998,7 @@ def main(argv=None):
     ddnm_inputs = _check_ddnm_args(args)
     dps_inputs = _check_dps_args(args)
     _check_paint_args(args)
+    _check_analytic_args(args)
     _check_flow_args(args)
     if args.save is not None and args.command != "sample":
         raise SystemExit("--save belongs to `sample` (fit: --save-checkpoint)")
@@ -911,6 +1035,9 @@ def main(argv=None):
         if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
             raise SystemExit("--sampler dps needs an unconditional config: guided DPS is not implemented")
         measurement, image, mask = dps_inputs
+    elif args.sampler == "analytic":
+        if getattr(_resolve(conf["model_spec"]["class_path"]), "conditional", False):
+            raise SystemExit("--sampler analytic needs an unconditional config: guided Analytic-DPM is not implemented")
     elif args.sample_steps is not None and args.sampler == "config" and args.command == "sample" and args.steps is None and _consistency_entry(args, conf) is not None:
         pass  # (a consistency checkpoint: --sample-steps K is the K of its sampler)
     elif args.sampler == "heun" or args.command == "evaluate":
@@ -947,12 +1074,16 @@ def main(argv=None):
     ckpt_path = args.ckpt_path or conf.get("ckpt_path")
     distilled = consistency = None
     if args.command == "evaluate":
+        ckpt = None
         if ckpt_path:
             from .checkpoint import load_checkpoint
 
-            load_checkpoint(ckpt_path, module, strict=False)
+            ckpt = load_checkpoint(ckpt_path, module, strict=False)
+        if args.sampler == "analytic":
+            return _evaluate_analytic(module, args, conf, B, ckpt)
         return _evaluate(module, args, conf, B)
     if args.command == "sample":
+        ckpt = None
         if ckpt_path:
             from .checkpoint import load_checkpoint
 
@@ -996,6 +1127,12 @@ def main(argv=None):
             module.diffusion_model = _ddnm_process(module, args).cuda()
         elif args.sampler == "heun":
             module.diffusion_model = _flow_process(module, args, 50).cuda()
+        elif args.sampler == "analytic":
+            module.diffusion_model, moment_source = _analytic_process(module, args, conf, B, ckpt)
+            if args.save_checkpoint is not None:  # (the moments travel in the state_dict: the next run finds them)
+                from .checkpoint import save_checkpoint
+
+                save_checkpoint(args.save_checkpoint, module)
         elif args.sampler == "dps":
             s = _dps_scale(args)
             H, W = tuple(image.shape[2:]) if image is not None else (measurement.shape[2] * s, measurement.shape[3] * s)
@@ -1050,7 +1187,7 @@ def main(argv=None):
             imgs = dm.generate(shape, labels, history=rec)
         elif args.labels is not None or args.guidance_scale is not None:
             raise SystemExit("--labels / --guidance-scale need a class-conditional config (LitClassifierFreeDDPM)")
-        elif args.sampler in ("dpm++", "heun"):
+        elif args.sampler in ("dpm++", "heun", "analytic"):
             imgs = dm.generate(shape, history=rec)
         elif args.sample_steps is not None and consistency is None:
             imgs = dm.generate(shape, sample_steps=args.sample_steps, history=rec)
@@ -1073,6 +1210,8 @@ def main(argv=None):
 
             save_png(args.grid, rec.canvas)
         line = {"images": list(imgs.shape), "precision": conf["precision"], "seconds": round(time.perf_counter() - t0, 3), "finite": bool(torch.isfinite(imgs).all())}
+        if args.sampler == "analytic":
+            line["analytic"] = {"sample_steps": int(dm.sub_timesteps), "eta": dm.eta, "tau_schedule": dm.tau_schedule, "moments": moment_source}
         if distilled is not None:
             line["distill"] = {"steps": int(distilled["steps"]), "tau_schedule": distilled.get("tau_schedule", "linear")}
         if consistency is not None:

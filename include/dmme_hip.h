@@ -1041,6 +1041,32 @@ DMME_API int dmme_tsampler_draw(const float* hist, const int* count, int T, int 
  * whose L[b] is not finite is skipped (a NaN in the history would poison p for good) and sets *status (nullable, device int) to 1. */
 DMME_API int dmme_tsampler_update(float* hist, int* count, int T, int H, const int64_t* t, const float* L, int B, int* status, void* stream);
 
+/* ---- Analytic-DPM (Bao et al., ICLR 2022): the statistic behind the optimal reverse variance of a fixed-variance noise prediction network,
+ * and the rows of the K-step variational bound of such a network.  Both entry points follow dmme_iddpm_loss_rows and dmme_pf_dot: two plain
+ * launches, no atomics; up to 32 workgroups per image leave partial sums in `scratch` (32 * B floats), one workgroup adds them in index
+ * order in double, so equal inputs give equal bits.  chw is free (no multiple of 4 needed).  model_out holds image b's noise prediction in
+ * the first chw values from b * image_stride: image_stride = chw for a DDPM network, 2 chw for an IDDPM network (the eps plane; v is not read).
+ * A device-side index is checked before it indexes anything; a bad one sets *status (nullable, device int) to 1 and poisons its image only. */
+
+/* m_b = (1/chw) sum_j eps[b][j]^2: fp32 products summed by fma, the partial sums and the division in double.  Then ONE thread walks
+ * b = 0 .. B-1 in order: sum[t_b] += m_b, count[t_b] += 1 (sum: double[T+1], count: int64[T+1], entry 0 unused), so a timestep that occurs
+ * twice in a batch has one well-defined result.  rows (nullable, float[B]) = (float) m_b.  A t_b outside [1, T] adds nothing, gives
+ * rows[b] = NaN and sets *status. */
+DMME_API int dmme_analytic_moment(const float* model_out, int64_t image_stride, const int64_t* t, int T, int B, int64_t chw, double* sum, int64_t* count,
+                                  float* rows, int* status, float* scratch, void* stream);
+
+/* rows[b] = term idx_b of the variational bound of the reverse process  p(x_{tau_{i-1}} | x_{tau_i}) = N(k0 x_t + k1 eps_theta, sigma_i^2 I)
+ * against the posterior  q = N(k0 x_t + k1 eps, lambda_i^2 I), per image in nats/dim.  coef: device fp32 table of 8 floats per index
+ * i = 0 .. S (row 0 unused): {k0_i, k1_i, log sigma_i^2, log lambda_i^2, sqrt(abar_tau_i), sqrt(1 - abar_tau_i), 0, 0}.
+ * eps is re-derived from x_t and x_0 by dmme_q_sample's own expression, (x_t - sqrt(abar) x_0) / sqrt(1 - abar), from columns 4 and 5.
+ *   idx_b >= 2: 0.5 (log sigma^2 - log lambda^2 + (lambda^2 + m_b) / sigma^2 - 1), m_b the mean over the image of (k1 (eps - eps_theta))^2:
+ *               fp32 per element, summed by fma; the mean and the closing expression in double from the fp32 columns, rounded once.
+ *   idx_b == 1: the mean of the discretised-Gaussian NLL of x_0, bins of width 2/255, open at +-1: per element the fp32 expressions of
+ *               dmme_iddpm_loss at t == 1, in its order, with mean = (k0 x_t) + (k1 eps_theta) and sd = sqrt(exp(log sigma^2)).
+ * An idx_b outside [1, S] reads no row, gives rows[b] = NaN and sets *status.  log lambda^2 = -inf (eta = 0) gives +inf above index 1. */
+DMME_API int dmme_analytic_vlb_rows(const float* model_out, int64_t image_stride, const float* x_t, const float* x_0, const int64_t* idx, const float* coef, int S,
+                                    int B, int64_t chw, float* rows, int* status, float* scratch, void* stream);
+
 /* ---- single-op entry points used by the unit parity tests ---------------------------
  * Activations here are NHWC in the compute dtype; weights in the packed layout
  * [Cout][taps][Cin]; they exercise exactly the kernels the plan launches.
