@@ -42,16 +42,12 @@ struct DdnmRow {
     unsigned long long seed, off;
 };
 
-// the step's row, from the arguments (eager) or from the table at the loop state's index (chain); every thread reads the state here, in
-// front of the block's first barrier, which is what chain_advance relies on
+// the step's row (chain_cursor: called at the top of each kernel)
 __device__ __forceinline__ DdnmRow ddnm_row(const DdnmArgs& a) {
+    const ChainCursor k = chain_cursor(a.st, a.coef, a.row);
+    const float* c = k.row;
     DdnmRow r;
-    const float* c = a.row;
-    r.i = 0, r.seed = 0, r.off = 0;
-    if (a.st) {
-        r.i = a.st->i, r.seed = a.st->seed, r.off = a.st->offset;
-        c = a.coef + 8 * r.i;
-    }
+    r.i = k.i, r.seed = k.seed, r.off = k.off;
     r.ca = c[0], r.cb = c[1], r.cz = c[2], r.A = c[3], r.B = c[4], r.lam = c[5], r.r0 = c[6], r.r1 = c[7];
     return r;
 }
@@ -70,16 +66,6 @@ __device__ __forceinline__ float ddnm_x0(const DdnmRow& r, float x, float e) { r
 // the residual of a cell: zero where it is not measured, and y is not looked at there
 __device__ __forceinline__ float ddnm_residual(float mean, float m, const float* y) { return m != 0.0f ? __fsub_rn(mean, *y) : 0.0f; }
 
-// the normals of stream s for the quad at element g: from memory where given, else the draw at Philox counter off + s n4 + g / 4
-__device__ __forceinline__ void ddnm_noise(const DdnmArgs& a, const DdnmRow& r, int s, int64_t g, float (&z)[4]) {
-    if (a.zin) {
-        const float4 v = load4(a.zin + s * a.numel + g);
-        z[0] = v.x, z[1] = v.y, z[2] = v.z, z[3] = v.w;
-    } else {
-        normal4(r.seed, r.off + (uint64_t)s * (uint64_t)a.n4 + (uint64_t)(g >> 2), z);
-    }
-}
-
 // the elementwise tail for the quad at element g, from x, x0 and the residual of each element's cell; a stream whose coefficient is
 // zero is neither drawn nor read
 __device__ __forceinline__ void ddnm_finish(const DdnmArgs& a, const DdnmRow& r, int64_t g, const float (&xs)[4], const float (&x0)[4], const float (&res)[4]) {
@@ -91,19 +77,17 @@ __device__ __forceinline__ void ddnm_finish(const DdnmArgs& a, const DdnmRow& r,
         if (r.cb != 0.0f) u[j] = __fadd_rn(u[j], __fmul_rn(r.cb, xs[j]));
     }
     if (r.cz != 0.0f) {
-        ddnm_noise(a, r, 0, g, z);
+        chain_noise4(a.zin, a.numel, a.n4, r.seed, r.off, 0, g, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) u[j] = __fadd_rn(u[j], __fmul_rn(r.cz, z[j]));
     }
     if (r.r1 != 0.0f) {
-        ddnm_noise(a, r, 1, g, z);
+        chain_noise4(a.zin, a.numel, a.n4, r.seed, r.off, 1, g, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) u[j] = __fadd_rn(__fmul_rn(r.r0, u[j]), __fmul_rn(r.r1, z[j]));
     }
     *reinterpret_cast<float4*>(a.x + g) = make_float4(u[0], u[1], u[2], u[3]);
 }
-
-__device__ __forceinline__ int64_t ddnm_eps_index(const DdnmArgs& a, int64_t g) { return a.out_planes == 2 ? g + (g / a.chw) * a.chw : g; }
 
 // ---- quad form: n == 1, the measurement has x's layout
 __global__ void __launch_bounds__(kDdnmThreads) ddnm_quad_kernel(DdnmArgs a) {
@@ -124,7 +108,7 @@ __global__ void __launch_bounds__(kDdnmThreads) ddnm_quad_kernel(DdnmArgs a) {
             for (int j = 0; j < 4; ++j) o[j] = ms[j] != 0.0f ? ddnm_cell_mean(&xs[j], 1, 0) : 0.0f;
             *reinterpret_cast<float4*>(a.y_out + g) = make_float4(o[0], o[1], o[2], o[3]);
         } else {
-            const float4 ev = load4(a.out + ddnm_eps_index(a, g));
+            const float4 ev = load4(a.out + eps_index(g, a.chw, a.out_planes));
             const float es[4] = {ev.x, ev.y, ev.z, ev.w};
             float x0[4], res[4];
 #pragma unroll
@@ -165,7 +149,7 @@ __global__ void __launch_bounds__(kDdnmThreads) ddnm_band_kernel(DdnmArgs a) {
         const float4 xv = load4(xin + g);
         float v[4] = {xv.x, xv.y, xv.z, xv.w};
         if (!a.src) {
-            const float4 ev = load4(a.out + ddnm_eps_index(a, g));
+            const float4 ev = load4(a.out + eps_index(g, a.chw, a.out_planes));
             v[0] = ddnm_x0(r, v[0], ev.x), v[1] = ddnm_x0(r, v[1], ev.y), v[2] = ddnm_x0(r, v[2], ev.z), v[3] = ddnm_x0(r, v[3], ev.w);
         }
 #pragma unroll

@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(kDpsThreads) dps_adjoint_kernel(DpsArgs a) {
     const DpsLds l = dps_carve(reinterpret_cast<float*>(dps_lds4), H, W, h, w);
     const int tid = threadIdx.x, hw = H * W, cells = h * w, plane = blockIdx.x;
     const int b = plane / a.C, c = plane - b * a.C;
-    const float* row = a.st ? a.coef + 8 * a.st->i : a.row;
+    const float* row = chain_cursor(a.st, a.coef, a.row).row;
     const float At = row[3], Bt = row[4];
     const int64_t base = (int64_t)plane * hw, cbase = (int64_t)plane * cells;
     const int64_t obase = ((int64_t)b * a.out_planes * a.C + c) * hw;  // this plane of the eps half of the network output / of d_out
@@ -170,29 +170,16 @@ struct DpsUpdArgs {
 };
 
 __global__ void __launch_bounds__(kDpsThreads) dps_update_kernel(DpsUpdArgs a) {
-    const float* row = a.row;
-    long long i = 0;
-    unsigned long long seed = 0, off = 0;
-    if (a.st) {  // every thread reads the state here, in front of the block's barrier: what chain_advance relies on
-        i = a.st->i, seed = a.st->seed, off = a.st->offset;
-        row = a.coef + 8 * i;
-    }
+    const ChainCursor k = chain_cursor(a.st, a.coef, a.row);
+    const float* row = k.row;
     const float c0 = row[0], c1 = row[1], c2 = row[2], At = row[3], zeta = row[5];
     const int64_t q = (int64_t)blockIdx.x * kDpsThreads + threadIdx.x;
     if (q < a.n4) {
         const int64_t e0 = 4 * q, b = e0 / a.chw;
-        const int64_t eo = a.out_planes == 2 ? e0 + b * a.chw : e0;
-        const float4 xv = load4(a.x + e0), ev = load4(a.out + eo);
+        const float4 xv = load4(a.x + e0), ev = load4(a.out + eps_index(e0, a.chw, a.out_planes));
         const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
         float u[4], z[4];
-        if (c2 != 0.0f) {
-            if (a.zin) {
-                const float4 v = load4(a.zin + e0);
-                z[0] = v.x, z[1] = v.y, z[2] = v.z, z[3] = v.w;
-            } else {
-                normal4(seed, off + (uint64_t)q, z);
-            }
-        }
+        if (c2 != 0.0f) chain_noise4(a.zin, a.numel, a.n4, k.seed, k.off, 0, e0, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             u[j] = ddpm_mean(xs[j], es[j], c0, c1);
@@ -214,7 +201,7 @@ __global__ void __launch_bounds__(kDpsThreads) dps_update_kernel(DpsUpdArgs a) {
     }
     if (a.st) {
         __syncthreads();
-        chain_advance(a.st, a.t_table, i, (unsigned long long)a.n4, false);
+        chain_advance(a.st, a.t_table, k.i, (unsigned long long)a.n4, false);
     }
 }
 

@@ -45,30 +45,16 @@ struct LpRow {
     unsigned long long seed, off;
 };
 
-// the step's row, from the arguments (eager) or from the table at the loop state's index (chain); every thread reads the state here, in
-// front of the block's first barrier, which is what chain_advance relies on
+// the step's row (chain_cursor: called at the top of each kernel)
 __device__ __forceinline__ LpRow lp_row(const LpArgs& a) {
+    const ChainCursor k = chain_cursor(a.st, a.coef, a.row);
+    const float* c = k.row;
     LpRow r;
-    const float* c = a.row;
-    r.i = 0, r.seed = 0, r.off = 0;
-    if (a.st) {
-        r.i = a.st->i, r.seed = a.st->seed, r.off = a.st->offset;
-        c = a.coef + 8 * r.i;
-    }
+    r.i = k.i, r.seed = k.seed, r.off = k.off;
     r.c0 = c[0], r.c1 = c[1], r.c2 = c[2], r.ka = c[3], r.ks = c[4];
     const bool cond = c[5] != 0.0f;
     r.used = (r.c2 != 0.0f ? 1 : 0) | (cond && r.ks != 0.0f ? 2 : 0) | (cond ? 4 : 0);
     return r;
-}
-
-// the normals of stream s for the quad at element b: from memory where given, else the draw at Philox counter off + s n4 + b / 4
-__device__ __forceinline__ void lp_noise(const LpArgs& a, const LpRow& r, int s, int64_t b, float (&z)[4]) {
-    if (a.zin) {
-        const float4 v = load4(a.zin + s * a.numel + b);
-        z[0] = v.x, z[1] = v.y, z[2] = v.z, z[3] = v.w;
-    } else {
-        normal4(r.seed, r.off + (uint64_t)s * (uint64_t)a.n4 + (uint64_t)(b >> 2), z);
-    }
 }
 
 // the elementwise half for the quad at element b: u, and d = k - u where want_d (dmme_lowpass: u = 0, d = src)
@@ -80,9 +66,8 @@ __device__ __forceinline__ void lp_quad(const LpArgs& a, const LpRow& r, int64_t
         return;
     }
     float z[4];
-    if (r.used & 1) lp_noise(a, r, 0, b, z);
-    const int64_t eo = a.out_planes == 2 ? b + (b / a.chw) * a.chw : b;
-    const float4 xv = load4(a.x + b), ev = load4(a.out + eo);
+    if (r.used & 1) chain_noise4(a.zin, a.numel, a.n4, r.seed, r.off, 0, b, z);
+    const float4 xv = load4(a.x + b), ev = load4(a.out + eps_index(b, a.chw, a.out_planes));
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -90,7 +75,7 @@ __device__ __forceinline__ void lp_quad(const LpArgs& a, const LpRow& r, int64_t
         if (r.used & 1) u[j] = __fadd_rn(u[j], __fmul_rn(r.c2, z[j]));
     }
     if (!want_d) return;
-    if (r.used & 2) lp_noise(a, r, 1, b, z);
+    if (r.used & 2) chain_noise4(a.zin, a.numel, a.n4, r.seed, r.off, 1, b, z);
     const float4 yv = load4(a.ref + b);
     const float ys[4] = {yv.x, yv.y, yv.z, yv.w};
 #pragma unroll

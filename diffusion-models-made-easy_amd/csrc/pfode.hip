@@ -29,8 +29,6 @@ static inline bool pf_aligned(std::initializer_list<const void*> ptrs) {
 static inline bool pf_quads(int B, int64_t chw, int planes, std::initializer_list<const void*> ptrs) {
     return (chw % 4 == 0 || (B == 1 && planes == 1)) && pf_aligned(ptrs);
 }
-// where element e of the images sits in a buffer of `planes` chw-sized planes per image, the eps plane first
-__device__ __forceinline__ int64_t pf_out_index(int64_t e, int64_t chw, int planes) { return planes == 1 ? e : e + (e / chw) * (int64_t)(planes - 1) * chw; }
 
 // ------------------------------------------------------------------ the probe and the dequantisation: one thread per Philox quad
 struct PfDrawArgs {
@@ -53,12 +51,12 @@ __global__ void __launch_bounds__(kPfThreads) pf_probe_kernel(PfDrawArgs a) {
     for (int j = 0; j < 4; ++j) z[j] = (r[j] >> 31) ? -1.0f : 1.0f;
     const int64_t e0 = 4 * q;
     if (a.vec && e0 + 3 < a.numel) {
-        const int64_t o = pf_out_index(e0, a.chw, a.planes);
+        const int64_t o = eps_index(e0, a.chw, a.planes);
         *reinterpret_cast<float4*>(a.dst + o) = make_float4(z[0], z[1], z[2], z[3]);
         if (a.planes == 2) *reinterpret_cast<float4*>(a.dst + o + a.chw) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
         for (int j = 0; j < 4 && e0 + j < a.numel; ++j) {
-            const int64_t o = pf_out_index(e0 + j, a.chw, a.planes);
+            const int64_t o = eps_index(e0 + j, a.chw, a.planes);
             a.dst[o] = z[j];
             if (a.planes == 2) a.dst[o + a.chw] = 0.0f;
         }
@@ -155,17 +153,13 @@ struct PfStageArgs {
 };
 
 __global__ void __launch_bounds__(kPfThreads) pf_stage_kernel(PfStageArgs a) {
-    const float* row = a.row;
-    long long i = 0;
-    if (a.st) {  // every thread reads the state here, in front of the block's barrier: what chain_advance relies on
-        i = a.st->i;
-        row = a.coef + 8 * i;
-    }
+    const ChainCursor k = chain_cursor(a.st, a.coef, a.row);
+    const float* row = k.row;
     const float c0 = row[0], c1 = row[1], c2 = row[2], c3 = row[3];
     const bool save = row[5] != 0.0f;
     const int64_t first = (int64_t)blockIdx.x * kPfThreads + threadIdx.x;
     if (first < a.n4) {
-        const int64_t e0 = 4 * first, eo = pf_out_index(e0, a.chw, a.planes);
+        const int64_t e0 = 4 * first, eo = eps_index(e0, a.chw, a.planes);
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
         const float4 xv = load4(a.x + e0), ev = load4(a.out + eo);
         const float4 sv = c1 != 0.0f ? load4(a.xs + e0) : zero, tv = c3 != 0.0f ? load4(a.es + e0) : zero;
@@ -178,14 +172,14 @@ __global__ void __launch_bounds__(kPfThreads) pf_stage_kernel(PfStageArgs a) {
     }
     const int64_t j = 4 * a.n4 + first;
     if (j < a.numel) {
-        const float xv = a.x[j], ev = a.out[pf_out_index(j, a.chw, a.planes)];
+        const float xv = a.x[j], ev = a.out[eps_index(j, a.chw, a.planes)];
         const float sv = c1 != 0.0f ? a.xs[j] : 0.0f, tv = c3 != 0.0f ? a.es[j] : 0.0f;
         if (save) a.xs[j] = xv, a.es[j] = ev;
         a.x[j] = pf_update(xv, sv, ev, tv, c0, c1, c2, c3);
     }
     if (a.st) {
         __syncthreads();
-        chain_advance(a.st, a.t_table, i, a.offset_inc, false);
+        chain_advance(a.st, a.t_table, k.i, a.offset_inc, false);
     }
 }
 

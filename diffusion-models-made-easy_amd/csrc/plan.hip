@@ -1893,6 +1893,19 @@ DMME_API int dmme_ddnm_chain_step(const dmme_plan* plan, const void* packed, flo
                        gray, planes, (hipStream_t)stream);
 }
 
+// what the steps that differentiate the denoiser (DPS, the likelihood's stage) ask of their plan
+static int require_differentiable_plan(const char* what, const dmme_plan* plan) {
+    DMME_REQUIRE(!plan->cond && (plan->cfg.arch == DMME_ARCH_DDPM || plan->cfg.arch == DMME_ARCH_IDDPM), DMME_ERR_INVALID,
+                 "%s: needs an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan (got architecture %d%s)", what, plan->cfg.arch,
+                 plan->cond ? ", class-conditional" : "");
+    DMME_REQUIRE(plan->pred == DMME_PRED_EPS, DMME_ERR_UNSUPPORTED,
+                 "%s: the plan's network predicts %s; the derivative of the x0 / v adapter is not built: an eps network only", what,
+                 plan->pred == DMME_PRED_X0 ? "x0" : "v");
+    DMME_REQUIRE(plan->thr_mode == DMME_THRESHOLD_NONE, DMME_ERR_UNSUPPORTED,
+                 "%s: the plan thresholds x0 (mode %d); the derivative of the clip is not built: threshold none only", what, plan->thr_mode);
+    return DMME_OK;
+}
+
 // DPS: kind DMME_CHAIN_DPS, which differentiates the denoiser itself: the keep form of the forward, the adjoint kernel (csrc/dps.hip) that
 // leaves d ||y - A x0|| / d eps (up to the per-image 1 / ||r||) in d_out, the input-only backward, the update that consumes both
 DMME_API int dmme_dps_chain_step(const dmme_plan* plan, const void* packed, const void* packed_bwd, float* x, float* model_out, void* workspace,
@@ -1901,14 +1914,7 @@ DMME_API int dmme_dps_chain_step(const dmme_plan* plan, const void* packed, cons
     DMME_REQUIRE(plan && packed && packed_bwd && x && model_out && workspace && bwd_workspace && y && Kh && Kw && g && d_out && dx && sumsq && step_coef &&
                      t_table && state,
                  DMME_ERR_INVALID, "dps_chain_step: null argument");
-    DMME_REQUIRE(!plan->cond && (plan->cfg.arch == DMME_ARCH_DDPM || plan->cfg.arch == DMME_ARCH_IDDPM), DMME_ERR_INVALID,
-                 "dps_chain_step: needs an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan (got architecture %d%s)", plan->cfg.arch,
-                 plan->cond ? ", class-conditional" : "");
-    DMME_REQUIRE(plan->pred == DMME_PRED_EPS, DMME_ERR_UNSUPPORTED,
-                 "dps_chain_step: the plan's network predicts %s; the derivative of the x0 / v adapter is not built: an eps network only",
-                 plan->pred == DMME_PRED_X0 ? "x0" : "v");
-    DMME_REQUIRE(plan->thr_mode == DMME_THRESHOLD_NONE, DMME_ERR_UNSUPPORTED,
-                 "dps_chain_step: the plan thresholds x0 (mode %d); the derivative of the clip is not built: threshold none only", plan->thr_mode);
+    if (int rc = require_differentiable_plan("dps_chain_step", plan)) return rc;
     int planes = 0;
     if (int rc = chain_step_front("dps_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_DPS, false, 0, nullptr, 8, 0, state, stream,
                                   planes, true))
@@ -1943,14 +1949,7 @@ DMME_API int dmme_pf_ll_chain_step(const dmme_plan* plan, const void* packed, co
     DMME_REQUIRE(plan && packed && packed_bwd && x && model_out && workspace && bwd_workspace && xs && es && d_out && dx && scratch && s_out && acc && step_coef &&
                      t_table && state,
                  DMME_ERR_INVALID, "pf_ll_chain_step: null argument");
-    DMME_REQUIRE(!plan->cond && (plan->cfg.arch == DMME_ARCH_DDPM || plan->cfg.arch == DMME_ARCH_IDDPM), DMME_ERR_INVALID,
-                 "pf_ll_chain_step: needs an unconditional DMME_ARCH_DDPM or DMME_ARCH_IDDPM plan (got architecture %d%s)", plan->cfg.arch,
-                 plan->cond ? ", class-conditional" : "");
-    DMME_REQUIRE(plan->pred == DMME_PRED_EPS, DMME_ERR_UNSUPPORTED,
-                 "pf_ll_chain_step: the plan's network predicts %s; the derivative of the x0 / v adapter is not built: an eps network only",
-                 plan->pred == DMME_PRED_X0 ? "x0" : "v");
-    DMME_REQUIRE(plan->thr_mode == DMME_THRESHOLD_NONE, DMME_ERR_UNSUPPORTED,
-                 "pf_ll_chain_step: the plan thresholds x0 (mode %d); the derivative of the clip is not built: threshold none only", plan->thr_mode);
+    if (int rc = require_differentiable_plan("pf_ll_chain_step", plan)) return rc;
     DMME_REQUIRE(!plan->mix, DMME_ERR_UNSUPPORTED, "pf_ll_chain_step: precision fp16r32 is an inference mode (no backward)");
     int planes = 0;
     if (int rc = chain_step_front("pf_ll_chain_step", plan, packed, x, nullptr, nullptr, model_out, workspace, DMME_CHAIN_PFODE, false, 0, nullptr, 8, 0, state,

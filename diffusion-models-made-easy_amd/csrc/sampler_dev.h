@@ -1,6 +1,7 @@
-// Device pieces shared by the translation units that hold sampler updates (kernels_sampler.hip: the kinds of common.h's table; ilvr.hip:
-// the plane-wise ILVR update): the Philox normals, DDPM's mean, the loop state of a replayable chain and its advance.  Every translation
-// unit that includes this is compiled with -ffp-contract=off (csrc/Makefile).
+// Device pieces shared by the translation units that hold sampler updates (kernels_sampler.hip: the kinds of common.h's table; ilvr.hip,
+// ddnm.hip, dps.hip, pfode.hip: the updates of the conditioned chain samplers): the Philox normals, DDPM's mean, the loop state of a
+// replayable chain, its cursor and its advance, a step's normals and the eps plane of a network output.  Every translation unit that
+// includes this is compiled with -ffp-contract=off (csrc/Makefile).
 #pragma once
 #include "common.h"
 
@@ -69,6 +70,38 @@ struct ChainState {
     unsigned long long reserved[2];
 };
 static_assert(sizeof(ChainState) == 64, "ChainState is eight 64-bit words (dmme_hip.h: dmme_chain_*)");
+
+// The top of a step's kernel, eager or chain: the row of the update's scalars, from the arguments (eager: `eager_row`, index 0, no stream) or
+// from the table at the loop state's index (chain), with the Philox stream's place.  Every thread calls this in front of the block's first
+// barrier: that all of them have read the state before any block takes its ticket is what chain_advance relies on.
+struct ChainCursor {
+    const float* row;
+    long long i;
+    unsigned long long seed, off;
+};
+__device__ __forceinline__ ChainCursor chain_cursor(const ChainState* st, const float* coef, const float* eager_row) {
+    ChainCursor k{eager_row, 0, 0ull, 0ull};
+    if (st) {
+        k.i = st->i, k.seed = st->seed, k.off = st->offset;
+        k.row = coef + 8 * k.i;
+    }
+    return k;
+}
+
+// the normals of stream `stream` for the quad at `element`: from memory where given (zin: [streams][numel]), else the draw at Philox counter
+// off + stream n4 + element / 4, which is where dmme_randn over the step's span puts them
+__device__ __forceinline__ void chain_noise4(const float* zin, int64_t numel, int64_t n4, unsigned long long seed, unsigned long long off, int stream,
+                                             int64_t element, float (&z)[4]) {
+    if (zin) {
+        const float4 v = load4(zin + stream * numel + element);
+        z[0] = v.x, z[1] = v.y, z[2] = v.z, z[3] = v.w;
+    } else {
+        normal4(seed, off + (uint64_t)stream * (uint64_t)n4 + (uint64_t)(element >> 2), z);
+    }
+}
+
+// where element e of the images sits in a network output of `planes` chw-sized planes per image, the eps plane first
+__device__ __forceinline__ int64_t eps_index(int64_t e, int64_t chw, int planes) { return planes == 1 ? e : e + (e / chw) * (int64_t)(planes - 1) * chw; }
 
 // The end of a chain kernel, after the block's __syncthreads(): every thread of this block has read the state (and is past its loads of it).
 // The block that takes the last ticket has, by construction, run after every block read the state (all others took their ticket after

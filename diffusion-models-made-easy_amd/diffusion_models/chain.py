@@ -29,18 +29,20 @@ class ChainTables:
         _lib.check(_lib.lib().dmme_chain_set(_lib.ptr(self.state), int(i), _lib.ptr(self.ttab), seed & 0xFFFFFFFFFFFFFFFF, int(offset), _lib.stream_ptr()), "dmme_chain_set")
 
 
+ROW_DRAWS = {}  # kind -> does a step over this table row read normals?  Each conditioned sampler states its rule beside its row layout and enters it here
+
+
 def chain_draws(kind: int, rows) -> bool:
     """does a chain of this kind over these table rows consume normals?  The host's statement of the kernels' noise rule (csrc/common.h:
-    kind_noise): the shipped DDIM kinds and DPM-Solver++ never do, the paper-form DDIM kinds only with a non-zero k2 somewhere, every kind
-    with a DDPM mean does, and so does RePaint (three streams per step).  A chain that draws nothing leaves torch's generator where the eager loop leaves it."""
+    kind_noise): the shipped DDIM kinds and DPM-Solver++ never do, the paper-form DDIM kinds only with a non-zero k2 somewhere, DDNM and
+    DPS where a row draws (`ROW_DRAWS`), every kind with a DDPM mean does, and so do RePaint and ILVR whatever their rows say.  A chain
+    that draws nothing leaves torch's generator where the eager loop leaves it."""
     if kind in (_lib.CHAIN_DDIM, _lib.CHAIN_DDIM_GUIDED, _lib.CHAIN_DPMPP, _lib.CHAIN_DPMPP_CFG):
         return False
     if kind in (_lib.CHAIN_GDDIM, _lib.CHAIN_GDDIM_CFG):
         return any(r[2] != 0.0 for r in rows)
-    if kind == _lib.CHAIN_DDNM:  # (cz of the posterior's noise, r1 of a folded jump)
-        return any(r[2] != 0.0 or r[7] != 0.0 for r in rows)
-    if kind == _lib.CHAIN_DPS:  # (c2 of the reverse step's noise)
-        return any(r[2] != 0.0 for r in rows)
+    if kind in (_lib.CHAIN_DDNM, _lib.CHAIN_DPS):
+        return any(ROW_DRAWS[kind](r) for r in rows)
     if kind == _lib.CHAIN_PFODE:  # (w of the likelihood's trace term: a stage that carries one draws a Rademacher probe)
         return any(r[4] != 0.0 for r in rows)
     return True
@@ -112,6 +114,27 @@ def walk(x: Tensor, first: int, count: int, step, recorder=None, reserve=None) -
     if recorder is not None:
         recorder.at(count, x)
     return x
+
+
+def eager_chain(x: Tensor, kind: int, tables, first: int, streams: int, call, history=None) -> Tensor:
+    """THE eager host loop of a conditioned sampler, in place on x: `first` steps from loop index `first` down over `tables`, each
+    `call(row, t, z)` with the table row, the timestep as a (1,) device tensor and the step's normals ([streams][numel], None where
+    `ROW_DRAWS[kind]` says the row reads none).  The normals come from dmme_randn at the offsets the captured chain's state walks through,
+    so the two agree bit for bit under the same seed; the span is taken where the chain's runner takes it (`chain_draws`), once the
+    recorder has accepted the walk."""
+    n, rows, ttab = tables
+    numel, row_draws = x.numel(), ROW_DRAWS[kind]
+    span = []
+    tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
+    z = torch.empty(streams * numel, dtype=torch.float32, device=x.device)
+
+    def step(k, i):
+        draws = row_draws(rows[i])
+        if draws:
+            _lib.check(_lib.lib().dmme_randn(_lib.ptr(z), z.numel(), span[0], span[1] + k * streams * (numel // 4), _lib.stream_ptr()), "dmme_randn")
+        call(rows[i], tt[i], z if draws else None)
+
+    return walk(x, first, first, step, history, lambda: span.extend(philox_reserve(x.device, streams * numel * first) if chain_draws(kind, rows) else (0, 0)))
 
 
 def capture(launch, check, carried=()):
@@ -280,3 +303,25 @@ class ChainRunner(ChainTables):
         torch.cuda.current_stream(self.x.device).synchronize()
         self.plan.check()
         return self.x
+
+    _side = ()  # the fixed buffers a subclass keeps beside x (read only: a chain fills them once), by attribute name
+
+    def run_copies(self, x: Tensor, side, first: int, recorder: Optional[HistoryRecorder] = None) -> Tensor:
+        """the chain from loop index `first` down to 0 on copies of x and of `side`, one tensor per name in `_side`; a new tensor"""
+        self.x.copy_(x)
+        for name, v in zip(self._side, side):
+            getattr(self, name).copy_(v)
+        return self.run(first, first, recorder).clone()
+
+
+class KeepForwardRunner(ChainRunner):
+    """a ChainRunner whose step keeps the forward's context for an input-only backward (DPS, the likelihood's stage): it hands over the
+    UNFOLDED weights (the keep form never reads the folded attention matrices) and, beside them, the backward's workspace and
+    data-gradient weights, brought up to date outside any capture"""
+
+    def _packed(self):
+        return self.model._bwd_buffers(self.plan)
+
+    def _weights_key(self):
+        p = self.plan
+        return super()._weights_key() + (p.packed_bwd_version, p.packed_bwd.data_ptr(), p.bws.data_ptr())

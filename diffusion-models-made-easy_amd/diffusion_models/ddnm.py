@@ -29,14 +29,15 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
-from ..common.noise import gaussian, philox_reserve
-from .chain import ChainRunner, walk
-from .ddpm import DDPM
-from .dpm_solver import _from_process, _row_arg, solver_grid
+from ..common.noise import gaussian
+from .chain import ROW_DRAWS, ChainRunner, eager_chain
+from .conditioned import GridProcess, check_mask, fp32_tables
+from .dpm_solver import _row_arg
 from .repaint import repaint_levels
 
 ROW = 8  # floats per table row: ca, cb, cz, A_t, B_t, lambda, r0, r1
 STREAMS = 2  # normal streams a step owns: z0 (the posterior's noise), z1 (the jump)
+ROW_DRAWS[_lib.CHAIN_DDNM] = lambda row: row[2] != 0.0 or row[7] != 0.0  # (cz of the posterior's noise, r1 of a folded jump)
 
 
 def ddnm_rows(alpha_bar, grid: Sequence[int], walk: Sequence[int], sigma_y: float = 0.0) -> Tuple[np.ndarray, List[int]]:
@@ -84,13 +85,11 @@ def ddnm_rows(alpha_bar, grid: Sequence[int], walk: Sequence[int], sigma_y: floa
     return rows, ttab
 
 
-def _row_draws(row) -> bool:
-    return row[2] != 0.0 or row[7] != 0.0
-
-
 class RestoreChainRunner(ChainRunner):
     """ChainRunner whose captured step is dmme_ddnm_chain_step: tables of 8 floats per index, the measurement and its mask in fixed buffers
     of measurement shape (B, Cm, h, w) (read only: a chain fills them once), two normal streams per step"""
+
+    _side = ("y", "mask")
 
     def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         super().__init__(process, x, use_graph, spec)
@@ -109,14 +108,10 @@ class RestoreChainRunner(ChainRunner):
         )
 
     def restore(self, x: Tensor, y: Tensor, mask: Tensor, first: int, recorder=None) -> Tensor:
-        """the chain from loop index `first` down to 0 on copies of the image, the measurement and its mask; a new tensor"""
-        self.x.copy_(x)
-        self.y.copy_(y)
-        self.mask.copy_(mask)
-        return self.run(first, first, recorder).clone()
+        return self.run_copies(x, (y, mask), first, recorder)
 
 
-class DDNM(DDPM):
+class DDNM(GridProcess):
     r"""DDNM+ over any unconditional noise-prediction network of the package (an IDDPM network's learned variance is not used), or an
     x0 / v network (`prediction=`).
 
@@ -127,6 +122,7 @@ class DDNM(DDPM):
 
     _chain_kind = _lib.CHAIN_DDNM
     _runner_class = RestoreChainRunner
+    _whole_chains = "DDNM runs whole chains: restore / generate"
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 100, scale: int = 1, gray: bool = False, sigma_y: float = 0.0,
                  travel_length: int = 1, travel_repeat: int = 1, start: float = 0.0001, end: float = 0.02, alpha_bar: Optional[Tensor] = None, *,
@@ -135,29 +131,14 @@ class DDNM(DDPM):
         for name, v in (("scale", scale), ("travel_length", travel_length), ("travel_repeat", travel_repeat)):
             if isinstance(v, bool) or int(v) != v or v < 1:
                 raise ValueError(f"{name} = {v!r}; an integer of at least 1")
-        if isinstance(sub_timesteps, bool) or int(sub_timesteps) != sub_timesteps or not 1 <= sub_timesteps <= timesteps:
-            raise ValueError(f"sub_timesteps = {sub_timesteps!r} outside 1..{timesteps}")
         if isinstance(sigma_y, bool) or not float(sigma_y) >= 0.0 or not np.isfinite(float(sigma_y)):
             raise ValueError(f"sigma_y = {sigma_y!r}; a finite noise level of at least 0")
-        if alpha_bar is not None:
-            self._use_alpha_bar(alpha_bar)
-        self.sub_timesteps, self.scale, self.gray, self.sigma_y = int(sub_timesteps), int(scale), bool(gray), float(sigma_y)
+        self._set_grid(sub_timesteps, alpha_bar)
+        self.scale, self.gray, self.sigma_y = int(scale), bool(gray), float(sigma_y)
         self.travel_length, self.travel_repeat = int(travel_length), int(travel_repeat)
-        ab64 = self.alpha_bar.reshape(-1).to(torch.float64).cpu().numpy()
-        grid = solver_grid(ab64, self.sub_timesteps, "linear")
-        self.n_levels = len(grid) - 1
-        self.register_buffer("tau", torch.tensor(grid, dtype=torch.int64), persistent=False)
-        self._tau_host, self._ab64 = grid, ab64
         self._walk = repaint_levels(self.n_levels, self.travel_length, self.travel_repeat)
-        rows, ttab = ddnm_rows(ab64, grid, self._walk, self.sigma_y)
-        self._tables = (len(ttab) - 1, [tuple(float(np.float32(v)) for v in r) for r in rows], ttab)
+        self._tables = fp32_tables(*ddnm_rows(self._ab64, self._tau_host, self._walk, self.sigma_y))
         self.n_rows = self._tables[0]
-
-    from_process = classmethod(_from_process)
-
-    def _chain_tables(self):
-        n, rows, ttab = self._tables
-        return n, list(rows), list(ttab)
 
     # ------------------------------------------------------------------ the operator
     def measurement_shape(self, image_shape) -> Tuple[int, int, int, int]:
@@ -172,23 +153,10 @@ class DDNM(DDPM):
         """the channels of the images a measurement of Cm channels comes from"""
         return int(getattr(self.model, "in_channels", 3)) if self.gray else int(Cm)
 
-    def _image(self, x: Tensor, what: str) -> Tensor:
-        if not (isinstance(x, Tensor) and x.dim() == 4 and x.is_floating_point()):
-            raise ValueError(f"{what}: a floating-point batch (B, C, H, W)")
-        return x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous()
-
     @staticmethod
     def _mask(mask, shape, device, none_value: float) -> Tensor:
         """(B|1, Cm|1, h, w) with values 0 or 1 -> contiguous fp32 of the measurement's shape; None: `none_value` everywhere"""
-        if mask is None:
-            return torch.full(tuple(shape), none_value, dtype=torch.float32, device=device)
-        m = torch.as_tensor(mask).detach().to(device=device, dtype=torch.float32)
-        B, Cm, h, w = shape
-        if m.dim() != 4 or m.shape[0] not in (1, B) or m.shape[1] not in (1, Cm) or tuple(m.shape[2:]) != (h, w):
-            raise ValueError(f"mask: shape {tuple(m.shape)} does not broadcast from (B|1, Cm|1, h, w) to the measurement's {tuple(shape)}")
-        if not bool(((m == 0) | (m == 1)).all()):
-            raise ValueError("mask: values must be 0 or 1 (1: measured): a fractional mask has no pseudo-inverse of this form")
-        return m.expand(B, Cm, h, w).contiguous()
+        return check_mask(mask, shape, device, none_value, channels="Cm", why=": a fractional mask has no pseudo-inverse of this form")
 
     @torch.no_grad()
     def degrade(self, x: Tensor, mask=None) -> Tensor:
@@ -214,25 +182,15 @@ class DDNM(DDPM):
 
     # ------------------------------------------------------------------ chains
     def _eager_chain(self, x: Tensor, y: Tensor, mask: Tensor, history=None) -> Tensor:
-        """the host loop over dmme_ddnm_step, in place on x: normals from dmme_randn at the offsets the captured chain's state walks
-        through, so the two agree bit for bit under the same seed"""
-        n, rows, ttab = self._tables
-        lib, numel = _lib.lib(), x.numel()
+        """the host loop over dmme_ddnm_step (`eager_chain`), in place on x"""
         B, Cc, H, W = x.shape
-        span = []  # (seed, offset) of the walk's normals, taken once the recorder has accepted the walk
-        tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
-        z2 = torch.empty(STREAMS * numel, dtype=torch.float32, device=x.device)
-        any_draws = any(_row_draws(r) for r in rows)
 
-        def step(k, i):
-            eps = self._eps(x, tt[i]).detach().to(torch.float32).contiguous()
-            draws = _row_draws(rows[i])
-            if draws:
-                _lib.check(lib.dmme_randn(_lib.ptr(z2), z2.numel(), span[0], span[1] + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
-            _lib.check(lib.dmme_ddnm_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(z2 if draws else None), _row_arg(rows[i]), B, Cc, H, W,
-                                          self.scale, int(self.gray), eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_ddnm_step")
+        def call(row, t, z):
+            eps = self._eps(x, t).detach().to(torch.float32).contiguous()
+            _lib.check(_lib.lib().dmme_ddnm_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(z), _row_arg(row), B, Cc, H, W, self.scale,
+                                                 int(self.gray), eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_ddnm_step")
 
-        return walk(x, n, n, step, history, lambda: span.extend(philox_reserve(x.device, STREAMS * numel * n) if any_draws else (0, 0)))
+        return eager_chain(x, _lib.CHAIN_DDNM, self._tables, self._tables[0], STREAMS, call, history)
 
     def _chain(self, x: Tensor, y: Tensor, mask: Tensor, history=None) -> Tensor:
         runner = self._buffered_runner("_runner", x.shape, x.device)
@@ -261,8 +219,3 @@ class DDNM(DDPM):
         shape = self.measurement_shape(img_size)
         zeros = torch.zeros(shape, dtype=torch.float32, device=self.beta.device)
         return self._chain(gaussian(tuple(img_size), device=zeros.device), zeros, zeros, history)
-
-    def sampling_step(self, *a, **kw):
-        raise NotImplementedError("DDNM runs whole chains: restore / generate")
-
-    denoise_once = sampling_step

@@ -257,15 +257,16 @@ class DDPM(nn.Module):
             self._all_t = torch.arange(0, n, device=device).unsqueeze(1)
         return self._all_t[t]
 
-    def chain_runner(self, x: Tensor, use_graph: bool = True, slot: str = "_runner", spec=None) -> Optional[ChainRunner]:
+    def chain_runner(self, x: Tensor, use_graph: bool = True, slot: str = "_runner", spec=None, cls=None) -> Optional[ChainRunner]:
         """runner bound to the image buffer `x` (cached per buffer / shape); None when the replayable step does not apply
-        (a model that is not a dmme_amd UNet, train mode, an image size that is not a multiple of 4)"""
+        (a model that is not a dmme_amd UNet, train mode, an image size that is not a multiple of 4).  `cls`: a runner class in place of
+        the process's `_runner_class` (a process whose chains do not all take the same step)"""
         if not self._replayable(x):
             return None
         r = getattr(self, slot, None)
         key = self._runner_key(x, use_graph)
         if r is None or r._key != key:
-            r = self._runner_class(self, x, use_graph, spec() if spec is not None else None)  # (spec: a callable, evaluated only when a runner is built)
+            r = (cls or self._runner_class)(self, x, use_graph, spec() if spec is not None else None)  # (spec: a callable, evaluated only when a runner is built)
             r._key = key
             setattr(self, slot, r)
         return r
@@ -280,14 +281,14 @@ class DDPM(nn.Module):
         """what a cached runner is good for: this buffer, this network (by identity) in this precision, this x0 thresholding"""
         return (x.data_ptr(), tuple(x.shape), self.model, self.model._dtype, use_graph, (self.threshold, self.threshold_percentile))
 
-    def _buffered_runner(self, slot: str, shape, device, spec=None, buf: str = "_gen_buf") -> Optional[ChainRunner]:
+    def _buffered_runner(self, slot: str, shape, device, spec=None, buf: str = "_gen_buf", cls=None) -> Optional[ChainRunner]:
         """the runner in `slot`, bound to an internal image buffer (attribute `buf`) of this shape on this device; both outlive the call:
         a second chain of the same shape re-uses the captured graph, the device tables and the buffers.  None where `chain_runner` is."""
         b = getattr(self, buf, None)
         if b is None or tuple(b.shape) != tuple(shape) or b.device != torch.device(device):
             b = torch.empty(tuple(shape), dtype=torch.float32, device=device)
             setattr(self, buf, b)
-        return self.chain_runner(b, slot=slot, spec=spec)
+        return self.chain_runner(b, slot=slot, spec=spec, cls=cls)
 
     def _run_chain(self, runner: Optional[ChainRunner], x: Tensor, first: int, count: int, step, history: Optional[HistoryRecorder] = None) -> Tensor:
         """`count` steps from loop index `first` downwards: x into the runner's buffer, one captured step (UNet + noise + update +

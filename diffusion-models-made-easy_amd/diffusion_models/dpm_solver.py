@@ -101,7 +101,7 @@ class DPMChainRunner(ChainRunner):
 
 
 def _row_arg(row):
-    """a table row of ROW floats as the C array the eager entry points take (this module's rows and RePaint's)"""
+    """a table row of ROW floats as the C array the eager entry points take (every kind whose rows are 8 floats)"""
     return (C.c_float * ROW)(*row)
 
 

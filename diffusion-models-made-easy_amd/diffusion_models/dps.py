@@ -27,13 +27,15 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
-from ..common.noise import gaussian, gaussian_like, philox_reserve
-from .chain import ChainRunner, walk
-from .ddpm import DDPM
-from .dpm_solver import _from_process, _row_arg, solver_grid
+from ..common.noise import gaussian, gaussian_like
+from .chain import ROW_DRAWS, KeepForwardRunner, eager_chain
+from .conditioned import GridProcess, check_mask, fp32_tables
+from .dpm_solver import _row_arg
 from .ilvr import resize_matrix
 
 ROW = 8  # floats per table row: c0, c1, c2, A_t, B_t, zeta, -, -
+STREAMS = 1  # normal streams a step owns: z (the reverse step)
+ROW_DRAWS[_lib.CHAIN_DPS] = lambda row: row[2] != 0.0  # (c2 of the reverse step's noise)
 OPERATORS = ("identity", "blur", "bicubic", "average")
 
 
@@ -154,10 +156,12 @@ def dps_rows(alpha_bar, grid: Sequence[int], zeta: float = 1.0) -> Tuple[np.ndar
     return rows, [int(t) for t in grid]
 
 
-class PosteriorChainRunner(ChainRunner):
+class PosteriorChainRunner(KeepForwardRunner):
     """ChainRunner whose captured step is dmme_dps_chain_step: the keep form of the forward, the adjoint kernel, the input-only backward
     and the update.  Tables of 8 floats per index; the measurement and its mask in fixed buffers (read only: a chain fills them once), the
     device copies of the operator's matrices, and the step's own buffers g, d_out, dx, sumsq; one normal stream per step."""
+
+    _side = ("y", "mask")
 
     def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         super().__init__(process, x, use_graph, spec)
@@ -171,15 +175,6 @@ class PosteriorChainRunner(ChainRunner):
         self.d_out = torch.zeros_like(self.out)
         self.sumsq = torch.zeros((B, Cc), dtype=torch.float32, device=x.device)
 
-    def _packed(self):
-        """the UNFOLDED weights (the keep form never reads the folded attention matrices) and, beside them, the backward's workspace
-        and data-gradient weights, brought up to date outside any capture"""
-        return self.model._bwd_buffers(self.plan)
-
-    def _weights_key(self):
-        p = self.plan
-        return super()._weights_key() + (p.packed_bwd_version, p.packed_bwd.data_ptr(), p.bws.data_ptr())
-
     def _call(self, packed):
         p = self.plan
         _lib.check(
@@ -191,14 +186,10 @@ class PosteriorChainRunner(ChainRunner):
         )
 
     def restore(self, x: Tensor, y: Tensor, mask: Tensor, first: int, recorder=None) -> Tensor:
-        """the chain from loop index `first` down to 0 on copies of the image, the measurement and its mask; a new tensor"""
-        self.x.copy_(x)
-        self.y.copy_(y)
-        self.mask.copy_(mask)
-        return self.run(first, first, recorder).clone()
+        return self.run_copies(x, (y, mask), first, recorder)
 
 
-class DPS(DDPM):
+class DPS(GridProcess):
     r"""DPS over any unconditional noise-prediction network of the package (an IDDPM network's learned variance is not used: the reverse
     step's variance is 1 - alpha).
 
@@ -210,6 +201,7 @@ class DPS(DDPM):
 
     _chain_kind = _lib.CHAIN_DPS
     _runner_class = PosteriorChainRunner
+    _whole_chains = "DPS runs whole chains: restore / generate"
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 1000, operator: Optional[SeparableOperator] = None, zeta: float = 1.0,
                  sigma_y: float = 0.0, start: float = 0.0001, end: float = 0.02, alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps",
@@ -219,36 +211,21 @@ class DPS(DDPM):
             raise NotImplementedError(f"DPS: prediction = {prediction!r}; the derivative of the x0 / v adapter is not built: an eps network only")
         if self.threshold != "none":
             raise NotImplementedError(f"DPS: threshold = {threshold!r}; the derivative of the clip is not built: threshold \"none\" only")
-        if isinstance(sub_timesteps, bool) or int(sub_timesteps) != sub_timesteps or not 1 <= sub_timesteps <= timesteps:
-            raise ValueError(f"sub_timesteps = {sub_timesteps!r} outside 1..{timesteps}")
         for name, v in (("zeta", zeta), ("sigma_y", sigma_y)):
             if isinstance(v, bool) or not float(v) >= 0.0 or not np.isfinite(float(v)):
                 raise ValueError(f"{name} = {v!r}; a finite number of at least 0")
         if operator is not None and not isinstance(operator, SeparableOperator):
             raise ValueError(f"operator = {operator!r}; a SeparableOperator (or None: the identity)")
-        if alpha_bar is not None:
-            self._use_alpha_bar(alpha_bar)
-        self.sub_timesteps, self.operator, self.zeta, self.sigma_y = int(sub_timesteps), operator, float(zeta), float(sigma_y)
-        ab64 = self.alpha_bar.reshape(-1).to(torch.float64).cpu().numpy()
-        grid = solver_grid(ab64, self.sub_timesteps, "linear")
-        self.n_levels = len(grid) - 1
-        self.register_buffer("tau", torch.tensor(grid, dtype=torch.int64), persistent=False)
-        self._tau_host, self._ab64 = grid, ab64
-        rows, ttab = dps_rows(ab64, grid, self.zeta)
-        self._tables = (len(ttab) - 1, [tuple(float(np.float32(v)) for v in r) for r in rows], ttab)
+        self._set_grid(sub_timesteps, alpha_bar)
+        self.operator, self.zeta, self.sigma_y = operator, float(zeta), float(sigma_y)
+        self._tables = fp32_tables(*dps_rows(self._ab64, self._tau_host, self.zeta))
         self.n_rows = self._tables[0]
         self._identities = {}
-
-    from_process = classmethod(_from_process)
 
     def set_threshold(self, mode: str, percentile: Optional[float] = None):
         if mode != "none":
             raise NotImplementedError(f"DPS: threshold = {mode!r}; the derivative of the clip is not built: threshold \"none\" only")
         return super().set_threshold(mode, percentile)
-
-    def _chain_tables(self):
-        n, rows, ttab = self._tables
-        return n, list(rows), list(ttab)
 
     # ------------------------------------------------------------------ the operator
     def _operator_for(self, H: int, W: int) -> SeparableOperator:
@@ -263,23 +240,7 @@ class DPS(DDPM):
             raise ValueError(f"DPS: {op!r} does not act on images of {H} x {W}")
         return op
 
-    def _image(self, x: Tensor, what: str) -> Tensor:
-        if not (isinstance(x, Tensor) and x.dim() == 4 and x.is_floating_point()):
-            raise ValueError(f"{what}: a floating-point batch (B, C, H, W)")
-        return x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous()
-
-    @staticmethod
-    def _mask(mask, shape, device, none_value: float) -> Tensor:
-        """(B|1, C|1, h, w) with values 0 or 1 -> contiguous fp32 of the measurement's shape; None: `none_value` everywhere"""
-        if mask is None:
-            return torch.full(tuple(shape), none_value, dtype=torch.float32, device=device)
-        m = torch.as_tensor(mask).detach().to(device=device, dtype=torch.float32)
-        B, Cc, h, w = shape
-        if m.dim() != 4 or m.shape[0] not in (1, B) or m.shape[1] not in (1, Cc) or tuple(m.shape[2:]) != (h, w):
-            raise ValueError(f"mask: shape {tuple(m.shape)} does not broadcast from (B|1, C|1, h, w) to the measurement's {tuple(shape)}")
-        if not bool(((m == 0) | (m == 1)).all()):
-            raise ValueError("mask: values must be 0 or 1 (1: measured)")
-        return m.expand(B, Cc, h, w).contiguous()
+    _mask = staticmethod(check_mask)  # (B|1, C|1, h, w) with values 0 or 1 -> contiguous fp32 of the measurement's shape
 
     @torch.no_grad()
     def degrade(self, x: Tensor, mask=None, noise: bool = True) -> Tensor:
@@ -301,36 +262,28 @@ class DPS(DDPM):
 
     # ------------------------------------------------------------------ chains
     def _eager_chain(self, x: Tensor, y: Tensor, mask: Tensor, history=None) -> Tensor:
-        """the host loop over the eager entry points (keep-forward, dmme_dps_adjoint, input-only backward, dmme_dps_step), in place on x:
-        normals from dmme_randn at the offsets the captured chain's state walks through, so the two agree bit for bit under the same seed"""
+        """the host loop over the eager entry points (keep-forward, dmme_dps_adjoint, input-only backward, dmme_dps_step; `eager_chain`),
+        in place on x"""
         model = self.model
         if not hasattr(model, "_forward_impl") or model.training:
             raise _lib.DmmeError("DPS differentiates the denoiser on the device: a dmme_amd UNet in eval mode")
-        n, rows, ttab = self._tables
-        lib, numel = _lib.lib(), x.numel()
+        lib = _lib.lib()
         B, Cc, H, W = x.shape
         op = self._operator_for(H, W)
         Kh, Kw = op.device(x.device)
-        span = []  # (seed, offset) of the walk's normals, taken once the recorder has accepted the walk
-        tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
-        z = torch.empty(numel, dtype=torch.float32, device=x.device)
         g, sumsq = torch.empty_like(x), torch.empty((B, Cc), dtype=torch.float32, device=x.device)
-        any_draws = any(r[2] != 0.0 for r in rows)
 
-        def step(k, i):
-            eps, saved = model._forward_impl(x, tt[i], want_ctx=True)
+        def call(row, t, z):
+            eps, saved = model._forward_impl(x, t, want_ctx=True)
             planes = eps[0].numel() // x[0].numel()
             d_out = torch.empty_like(eps)
-            _lib.check(lib.dmme_dps_adjoint(_lib.ptr(x), _lib.ptr(eps), planes, _row_arg(rows[i]), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(Kh), _lib.ptr(Kw), _lib.ptr(g),
+            _lib.check(lib.dmme_dps_adjoint(_lib.ptr(x), _lib.ptr(eps), planes, _row_arg(row), _lib.ptr(y), _lib.ptr(mask), _lib.ptr(Kh), _lib.ptr(Kw), _lib.ptr(g),
                                             _lib.ptr(d_out), _lib.ptr(sumsq), B, Cc, H, W, op.h, op.w, _lib.stream_ptr()), "dmme_dps_adjoint")
             dx = model._backward_input_impl(saved, d_out)
-            draws = rows[i][2] != 0.0
-            if draws:
-                _lib.check(lib.dmme_randn(_lib.ptr(z), numel, span[0], span[1] + k * (numel // 4), _lib.stream_ptr()), "dmme_randn")
-            _lib.check(lib.dmme_dps_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(g), _lib.ptr(dx), _lib.ptr(sumsq), _lib.ptr(z if draws else None), _row_arg(rows[i]), B,
-                                         Cc, H, W, planes, _lib.stream_ptr()), "dmme_dps_step")
+            _lib.check(lib.dmme_dps_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(g), _lib.ptr(dx), _lib.ptr(sumsq), _lib.ptr(z), _row_arg(row), B, Cc, H, W, planes,
+                                         _lib.stream_ptr()), "dmme_dps_step")
 
-        return walk(x, n, n, step, history, lambda: span.extend(philox_reserve(x.device, numel * n) if any_draws else (0, 0)))
+        return eager_chain(x, _lib.CHAIN_DPS, self._tables, self._tables[0], STREAMS, call, history)
 
     def _chain(self, x: Tensor, y: Tensor, mask: Tensor, history=None) -> Tensor:
         runner = self._buffered_runner("_runner", x.shape, x.device)
@@ -364,8 +317,3 @@ class DPS(DDPM):
         shape = self._operator_for(H, W).measurement_shape((B, Cc, H, W))
         zeros = torch.zeros(shape, dtype=torch.float32, device=self.beta.device)
         return self._chain(gaussian((B, Cc, H, W), device=zeros.device), zeros, zeros, history)
-
-    def sampling_step(self, *a, **kw):
-        raise NotImplementedError("DPS runs whole chains: restore / generate")
-
-    denoise_once = sampling_step

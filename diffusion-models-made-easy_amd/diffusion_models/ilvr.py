@@ -26,13 +26,14 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
-from ..common.noise import gaussian, philox_reserve
-from .chain import ChainRunner, walk
-from .ddpm import DDPM
-from .dpm_solver import _from_process, _row_arg, solver_grid
+from ..common.noise import gaussian
+from .chain import ROW_DRAWS, ChainRunner, eager_chain
+from .conditioned import GridProcess, fp32_tables
+from .dpm_solver import _row_arg
 
 ROW = 8  # floats per table row: c0, c1, c2, ka, ks, g, -, -
 STREAMS = 2  # normal streams a step owns: z0 (reverse step), z1 (the reference's noise)
+ROW_DRAWS[_lib.CHAIN_ILVR] = lambda row: row[2] != 0.0 or row[5] != 0.0 and row[4] != 0.0  # (z0, or z1 of a conditioned row: a stream whose coefficient is zero is not read)
 
 
 def _cubic(x: np.ndarray, a: float = -0.5) -> np.ndarray:
@@ -87,15 +88,12 @@ def ilvr_rows(alpha_bar, grid: Sequence[int], range_level: int = 0, reverse=None
     return rows, [int(t) for t in grid]
 
 
-def _row_streams(row) -> Tuple[bool, bool]:
-    """(z0 used, z1 used) by a row: the device's rule (a stream whose coefficient is zero, and z1 of an unconditioned row, is not read)"""
-    return row[2] != 0.0, row[5] != 0.0 and row[4] != 0.0
-
-
 class LikeChainRunner(ChainRunner):
     """ChainRunner whose captured step is dmme_ilvr_chain_step: tables of 8 floats per index, the reference image in a fixed buffer beside
     x (read only: a chain fills it once), the device copies of the two filter matrices, the streaming form's scratch, two normal streams
     per step"""
+
+    _side = ("ref",)
 
     def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         super().__init__(process, x, use_graph, spec)
@@ -114,13 +112,10 @@ class LikeChainRunner(ChainRunner):
         )
 
     def like(self, x: Tensor, ref: Tensor, first: int, recorder=None) -> Tensor:
-        """the chain from loop index `first` down to 0 on copies of the two images; a new tensor"""
-        self.x.copy_(x)
-        self.ref.copy_(ref)
-        return self.run(first, first, recorder).clone()
+        return self.run_copies(x, (ref,), first, recorder)
 
 
-class ILVR(DDPM):
+class ILVR(GridProcess):
     r"""ILVR over any unconditional noise-prediction network of the package (an IDDPM network's learned variance is not used: the reverse
     step's variance is beta), or an x0 / v network (`prediction=`).
 
@@ -131,39 +126,26 @@ class ILVR(DDPM):
 
     _chain_kind = _lib.CHAIN_ILVR
     _runner_class = LikeChainRunner
+    _whole_chains = "ILVR runs whole chains: sample_like / generate"
+    _image_noun = "image batch"
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 250, down_factor: int = 4, range_level: int = 0, start: float = 0.0001,
                  end: float = 0.02, alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
         super().__init__(model, timesteps, start, end, prediction=prediction, loss_weight=loss_weight, snr_gamma=snr_gamma, threshold=threshold, threshold_percentile=threshold_percentile)
         if isinstance(down_factor, bool) or int(down_factor) != down_factor or down_factor < 2:
             raise ValueError(f"down_factor = {down_factor!r}; an integer of at least 2")
-        if isinstance(sub_timesteps, bool) or int(sub_timesteps) != sub_timesteps or not 1 <= sub_timesteps <= timesteps:
-            raise ValueError(f"sub_timesteps = {sub_timesteps!r} outside 1..{timesteps}")
-        if alpha_bar is not None:
-            self._use_alpha_bar(alpha_bar)
-        self.sub_timesteps, self.down_factor = int(sub_timesteps), int(down_factor)
-        ab64 = self.alpha_bar.reshape(-1).to(torch.float64).cpu().numpy()
-        grid = solver_grid(ab64, self.sub_timesteps, "linear")
-        self.n_levels = len(grid) - 1
+        self._set_grid(sub_timesteps, alpha_bar)
+        self.down_factor = int(down_factor)
         if isinstance(range_level, bool) or int(range_level) != range_level or not 0 <= range_level <= self.n_levels:
             raise ValueError(f"range_level = {range_level!r} outside 0..{self.n_levels} (the grid's levels)")
         self.range_level = int(range_level)
-        self.register_buffer("tau", torch.tensor(grid, dtype=torch.int64), persistent=False)
-        self._tau_host, self._ab64 = grid, ab64
         self._tables = self._make_tables(self.range_level)
         self._free_tables = self._make_tables(self.n_levels + 1)  # `generate`: g = 0 in every row
         self._filter_cache = {}
 
-    from_process = classmethod(_from_process)
-
     def _make_tables(self, range_level: int):
         full = self.n_levels == self.timesteps
-        rows, ttab = ilvr_rows(self._ab64, self._tau_host, range_level, (self._c1, self._c2, self._sigma) if full else None)
-        return len(ttab) - 1, [tuple(float(np.float32(v)) for v in r) for r in rows], ttab
-
-    def _chain_tables(self):
-        n, rows, ttab = self._tables
-        return n, list(rows), list(ttab)
+        return fp32_tables(*ilvr_rows(self._ab64, self._tau_host, range_level, (self._c1, self._c2, self._sigma) if full else None))
 
     # ------------------------------------------------------------------ the filter
     def _filters(self, H: int, W: int, device) -> Tuple[Tensor, Tensor]:
@@ -175,11 +157,6 @@ class ILVR(DDPM):
         if key not in self._filter_cache:
             self._filter_cache[key] = tuple(torch.from_numpy(lowpass_matrix(n, N).astype(np.float32)).contiguous().to(device) for n in (H, W))
         return self._filter_cache[key]
-
-    def _image(self, x: Tensor, what: str) -> Tensor:
-        if not (isinstance(x, Tensor) and x.dim() == 4 and x.is_floating_point()):
-            raise ValueError(f"{what}: a floating-point image batch (B, C, H, W)")
-        return x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous()
 
     @staticmethod
     def _scratch(planes: int, H: int, W: int, device) -> Tensor:
@@ -198,36 +175,23 @@ class ILVR(DDPM):
         return dst
 
     # ------------------------------------------------------------------ chains
-    def _like_runner(self, slot: str, shape, dev, tables=None) -> Optional[LikeChainRunner]:
-        if tables is None:
-            return self._buffered_runner(slot, shape, dev)
-        return self._buffered_runner(slot, shape, dev, spec=lambda: (_lib.CHAIN_ILVR, tables), buf=slot + "_buf")
-
     def _eager_chain(self, x: Tensor, ref: Tensor, tables=None, history=None) -> Tensor:
-        """the host loop over dmme_ilvr_step, in place on x: normals from dmme_randn at the offsets the captured chain's state walks
-        through, so the two agree bit for bit under the same seed"""
-        n, rows, ttab = tables if tables is not None else self._tables
-        lib, numel = _lib.lib(), x.numel()
+        """the host loop over dmme_ilvr_step (`eager_chain`), in place on x"""
+        tables = tables if tables is not None else self._tables
         B, Cc, H, W = x.shape
         Ph, Pw = self._filters(H, W, x.device)
         scratch = self._scratch(B * Cc, H, W, x.device)
-        span = []  # (seed, offset) of the walk's normals, taken once the recorder has accepted the walk
-        tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
-        z2 = torch.empty(STREAMS * numel, dtype=torch.float32, device=x.device)
 
-        def step(k, i):
-            eps = self._eps(x, tt[i]).detach().to(torch.float32).contiguous()
-            draws = any(_row_streams(rows[i]))
-            if draws:
-                _lib.check(lib.dmme_randn(_lib.ptr(z2), z2.numel(), span[0], span[1] + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
-            _lib.check(lib.dmme_ilvr_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(ref), _lib.ptr(z2 if draws else None), _row_arg(rows[i]), _lib.ptr(Ph), _lib.ptr(Pw),
-                                          _lib.ptr(scratch), B, Cc, H, W, eps[0].numel() // x[0].numel(), 0, _lib.stream_ptr()), "dmme_ilvr_step")
+        def call(row, t, z):
+            eps = self._eps(x, t).detach().to(torch.float32).contiguous()
+            _lib.check(_lib.lib().dmme_ilvr_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(ref), _lib.ptr(z), _row_arg(row), _lib.ptr(Ph), _lib.ptr(Pw), _lib.ptr(scratch), B,
+                                                 Cc, H, W, eps[0].numel() // x[0].numel(), 0, _lib.stream_ptr()), "dmme_ilvr_step")
 
-        return walk(x, n, n, step, history, lambda: span.extend(philox_reserve(x.device, STREAMS * numel * n)))
+        return eager_chain(x, _lib.CHAIN_ILVR, tables, tables[0], STREAMS, call, history)
 
     def _chain(self, slot: str, x: Tensor, ref: Tensor, tables=None, history=None) -> Tensor:
         self._filters(x.shape[2], x.shape[3], x.device)  # (the size check, before a runner or a draw)
-        runner = self._like_runner(slot, x.shape, x.device, tables)
+        runner = self._table_runner(slot, x.shape, x.device, tables)
         if runner is None:
             return self._eager_chain(x, ref, tables, history)
         return runner.like(x, ref, (tables if tables is not None else self._tables)[0], history)
@@ -246,8 +210,3 @@ class ILVR(DDPM):
         zeros = torch.zeros(tuple(img_size), dtype=torch.float32, device=self.beta.device)
         self._filters(zeros.shape[2], zeros.shape[3], zeros.device)
         return self._chain("_free_runner", gaussian(img_size, device=zeros.device), zeros, self._free_tables, history)
-
-    def sampling_step(self, *a, **kw):
-        raise NotImplementedError("ILVR runs whole chains: sample_like / generate")
-
-    denoise_once = sampling_step

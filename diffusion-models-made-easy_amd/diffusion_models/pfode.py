@@ -23,7 +23,6 @@ tile the batch to average probes."""
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -33,9 +32,9 @@ from torch import Tensor, nn
 
 from .. import _lib
 from ..common.noise import gaussian, philox_reserve
-from .chain import ChainRunner, walk
-from .ddpm import DDPM
-from .dpm_solver import TAU_SCHEDULES, _from_process, solver_grid
+from .chain import ChainRunner, KeepForwardRunner, walk
+from .conditioned import WholeChainProcess, fp32_tables
+from .dpm_solver import TAU_SCHEDULES, _row_arg, solver_grid
 
 ROW = 8  # floats per table row: c0, c1, c2, c3, w, save, -, -
 DIRECTIONS = ("encode", "decode")
@@ -104,10 +103,6 @@ def pf_rows(alpha_bar, grid: Sequence[int], direction: str = "decode", likelihoo
     return rows, ttab
 
 
-def _row_arg(row):
-    return (C.c_float * ROW)(*row)
-
-
 class FlowChainRunner(ChainRunner):
     """ChainRunner whose captured step is dmme_pf_chain_step: the no-grad forward and one Heun stage.  Tables of 8 floats per index; `xs`
     and `es`, the state and the prediction at a step's first node, are fixed buffers that travel with x and the loop state."""
@@ -128,7 +123,7 @@ class FlowChainRunner(ChainRunner):
         )
 
 
-class LikelihoodChainRunner(FlowChainRunner):
+class LikelihoodChainRunner(KeepForwardRunner, FlowChainRunner):
     """ChainRunner whose captured step is dmme_pf_ll_chain_step: the keep form of the forward, the Rademacher probe written as d_out, the
     input-only backward, the probe dot into `acc` (a double per image, carried from stage to stage) and the Heun stage; one probe
     stream per stage.  `s` holds the last stage's per-image z^T J z, `dx` its J^T z."""
@@ -140,14 +135,6 @@ class LikelihoodChainRunner(FlowChainRunner):
         self.scratch = torch.zeros(int(_lib.lib().dmme_pf_scratch_floats(B, x[0].numel())), dtype=torch.float32, device=x.device)
         self.s = torch.zeros(B, dtype=torch.float32, device=x.device)
         self.acc = torch.zeros(B, dtype=torch.float64, device=x.device)
-
-    def _packed(self):
-        """the UNFOLDED weights and, beside them, the backward's workspace and data-gradient weights (PosteriorChainRunner's)"""
-        return self.model._bwd_buffers(self.plan)
-
-    def _weights_key(self):
-        p = self.plan
-        return super()._weights_key() + (p.packed_bwd_version, p.packed_bwd.data_ptr(), p.bws.data_ptr())
 
     def _carried(self):
         return super()._carried() + [self.acc]
@@ -162,7 +149,7 @@ class LikelihoodChainRunner(FlowChainRunner):
         )
 
 
-class ProbabilityFlow(DDPM):
+class ProbabilityFlow(WholeChainProcess):
     r"""The probability-flow ODE over any noise-prediction network of the package (an IDDPM network's learned variance is not used).
 
     `nodes`, `schedule` ("linear", "quadratic", "logsnr") and `t_min` give the integer grid (`pf_grid`); `grid=` gives it outright.
@@ -173,6 +160,7 @@ class ProbabilityFlow(DDPM):
 
     _chain_kind = _lib.CHAIN_PFODE
     _runner_class = FlowChainRunner
+    _whole_chains = "ProbabilityFlow runs whole walks: decode / generate / encode / log_likelihood"
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, nodes: int = 50, schedule: str = "linear", t_min: int = 1, start: float = 0.0001,
                  end: float = 0.02, alpha_bar: Optional[Tensor] = None, grid: Optional[Sequence[int]] = None, *, prediction: str = "eps",
@@ -191,17 +179,14 @@ class ProbabilityFlow(DDPM):
         self.nodes, self.schedule, self.t_min = len(g), kind, g[0]
         self.register_buffer("tau", torch.tensor(g, dtype=torch.int64), persistent=False)
         self._grid, self._ab64 = g, ab64
-        f32 = lambda rows_t: (len(rows_t[1]) - 1, [tuple(float(np.float32(v)) for v in r) for r in rows_t[0]], rows_t[1])
         self._tables = {
-            "decode": f32(pf_rows(ab64, g, "decode")),
-            "decode_raw": f32(pf_rows(ab64, g, "decode", final_denoise=False)),
-            "encode": f32(pf_rows(ab64, g, "encode")),
-            "likelihood": f32(pf_rows(ab64, g, "encode", likelihood=True)),
+            "decode": fp32_tables(*pf_rows(ab64, g, "decode")),
+            "decode_raw": fp32_tables(*pf_rows(ab64, g, "decode", final_denoise=False)),
+            "encode": fp32_tables(*pf_rows(ab64, g, "encode")),
+            "likelihood": fp32_tables(*pf_rows(ab64, g, "encode", likelihood=True)),
         }
         # log p(x_0) - log N(x_T) - acc, per dimension pair: (1/2)(ln abar_{g_n} - ln abar_{g_0})
         self._log_scale = 0.5 * (math.log(ab64[g[-1]]) - math.log(ab64[g[0]]))
-
-    from_process = classmethod(_from_process)
 
     def _chain_tables(self):
         n, rows, ttab = self._tables["decode"]
@@ -223,28 +208,10 @@ class ProbabilityFlow(DDPM):
         if getattr(model, "_dtype", None) == _lib.F16R32:
             raise NotImplementedError(f"ProbabilityFlow.{what}: precision fp16r32 is an inference mode without a backward; use fp32, bf16, fp16 or bf16x3")
 
-    def _image(self, x: Tensor, what: str) -> Tensor:
-        if not (isinstance(x, Tensor) and x.dim() == 4 and x.is_floating_point()):
-            raise ValueError(f"{what}: a floating-point batch (B, C, H, W)")
-        return x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous().clone()
-
     # ------------------------------------------------------------------ runners: one per table, each on a buffer of its own
     def _flow_runner(self, name: str, shape, device, cls=FlowChainRunner) -> Optional[ChainRunner]:
-        slot, buf = f"_pf_runner_{name}", f"_pf_buf_{name}"
-        b = getattr(self, buf, None)
-        if b is None or tuple(b.shape) != tuple(shape) or b.device != torch.device(device):
-            b = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-            setattr(self, buf, b)
-        if not self._replayable(b):
-            return None
-        r = getattr(self, slot, None)
-        key = self._runner_key(b, True)
-        if r is None or r._key != key:
-            n, rows, ttab = self._tables[name]
-            r = cls(self, b, True, (_lib.CHAIN_PFODE, (n, list(rows), list(ttab))))
-            r._key = key
-            setattr(self, slot, r)
-        return r
+        n, rows, ttab = self._tables[name]
+        return self._buffered_runner(f"_pf_runner_{name}", shape, device, spec=lambda: (_lib.CHAIN_PFODE, (n, list(rows), list(ttab))), buf=f"_pf_buf_{name}", cls=cls)
 
     # ------------------------------------------------------------------ the eager host loops over the eager entry points
     def _eager_walk(self, x: Tensor, name: str, history=None, threshold: bool = True) -> Tensor:
@@ -295,13 +262,11 @@ class ProbabilityFlow(DDPM):
         """x_0 from the latent x_T: the Heun walk g_n -> g_0, closed by one Euler stage g_0 -> 0 (`final_denoise=False`: the state at
         t_min).  Deterministic: nothing is drawn.  `history`: a HistoryRecorder for the walk's frames (one per stage)."""
         name = "decode" if final_denoise else "decode_raw"
-        x = self._image(x_T, "decode")
+        x = self._image(x_T, "decode", copy=True)
         runner = self._flow_runner(name, x.shape, x.device)
         if runner is None:
             return self._eager_walk(x, name, history)
-        n = self._tables[name][0]
-        runner.x.copy_(x)
-        return runner.run(n, n, history).clone()
+        return runner.run_copies(x, (), self._tables[name][0], history)
 
     @torch.no_grad()
     def generate(self, img_size: Tuple[int, int, int, int], history=None) -> Tensor:
@@ -312,13 +277,11 @@ class ProbabilityFlow(DDPM):
     def encode(self, x_0: Tensor) -> Tensor:
         """the latent x_T of the images x_0, taken as the state at t_min: the Heun walk g_0 -> g_n"""
         self._require_plain_eps("encode")
-        x = self._image(x_0, "encode")
+        x = self._image(x_0, "encode", copy=True)
         runner = self._flow_runner("encode", x.shape, x.device)
         if runner is None:
             return self._eager_walk(x, "encode", threshold=False)
-        n = self._tables["encode"][0]
-        runner.x.copy_(x)
-        return runner.run(n, n).clone()
+        return runner.run_copies(x, (), self._tables["encode"][0])
 
     @torch.no_grad()
     def log_likelihood(self, x_0: Tensor, dequantize: bool = False) -> LogLikelihood:
@@ -326,7 +289,7 @@ class ProbabilityFlow(DDPM):
         and the same probes under the same seed).  `dequantize`: uniform noise of one pixel step (2/255) is added first, as the published
         bits/dim figures do.  Returns (log_p, prior, divergence) in float64 and the latent x_T."""
         self._require_plain_eps("log_likelihood")
-        x = self._image(x_0, "log_likelihood")
+        x = self._image(x_0, "log_likelihood", copy=True)
         B, chw = x.shape[0], x[0].numel()
         lib = _lib.lib()
         if dequantize:
@@ -336,10 +299,8 @@ class ProbabilityFlow(DDPM):
         if runner is None:
             latent, acc = self._eager_likelihood(x)
         else:
-            n = self._tables["likelihood"][0]
-            runner.x.copy_(x)
             runner.acc.zero_()
-            latent, acc = runner.run(n, n).clone(), runner.acc.clone()
+            latent, acc = runner.run_copies(x, (), self._tables["likelihood"][0]), runner.acc.clone()
         scratch = torch.zeros(int(lib.dmme_pf_scratch_floats(B, chw)), dtype=torch.float32, device=x.device)
         prior = torch.zeros(B, dtype=torch.float64, device=x.device)
         _lib.check(lib.dmme_pf_prior(_lib.ptr(latent), B, chw, _lib.ptr(scratch), _lib.ptr(prior), _lib.stream_ptr()), "dmme_pf_prior")
@@ -351,8 +312,3 @@ class ProbabilityFlow(DDPM):
         ll = self.log_likelihood(x_0, dequantize)
         D = ll.latent[0].numel()
         return -ll.log_p / (D * math.log(2.0)) + math.log2(255.0 / 2.0)
-
-    def sampling_step(self, *a, **kw):
-        raise NotImplementedError("ProbabilityFlow runs whole walks: decode / generate / encode / log_likelihood")
-
-    denoise_once = sampling_step

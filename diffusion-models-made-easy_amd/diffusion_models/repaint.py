@@ -27,13 +27,14 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
-from ..common.noise import gaussian, gaussian_like, philox_reserve
-from .chain import ChainRunner, walk
-from .ddpm import DDPM
-from .dpm_solver import _from_process, _row_arg, solver_grid
+from ..common.noise import gaussian, gaussian_like
+from .chain import ROW_DRAWS, ChainRunner, eager_chain
+from .conditioned import GridProcess, check_mask, fp32_tables
+from .dpm_solver import _row_arg
 
 ROW = 8  # floats per table row: c0, c1, c2, ka, ks, r0, r1, -
 STREAMS = 3  # normal streams a step owns: z0 (reverse step), z1 (known pixels), z2 (jump)
+ROW_DRAWS[_lib.CHAIN_REPAINT] = lambda row: row[2] != 0.0 or row[4] != 0.0 or row[6] != 0.0  # (a stream whose coefficient is zero is not read)
 
 
 def repaint_levels(n: int, jump_length: int = 10, resamples: int = 10) -> List[int]:
@@ -92,13 +93,11 @@ def repaint_rows(alpha_bar, grid: Sequence[int], walk: Sequence[int], reverse=No
     return rows, ttab
 
 
-def _row_draws(row) -> bool:
-    return row[2] != 0.0 or row[4] != 0.0 or row[6] != 0.0
-
-
 class PaintChainRunner(ChainRunner):
     """ChainRunner whose captured step is dmme_repaint_chain_step: tables of 8 floats per index, the known image and its mask in fixed
     buffers beside x (read only: a chain fills them once), three normal streams per step"""
+
+    _side = ("known", "mask")
 
     def __init__(self, process, x: Tensor, use_graph: bool = True, spec=None):
         super().__init__(process, x, use_graph, spec)
@@ -115,14 +114,10 @@ class PaintChainRunner(ChainRunner):
         )
 
     def paint(self, x: Tensor, known: Tensor, mask: Tensor, first: int, recorder=None) -> Tensor:
-        """the chain from loop index `first` down to 0 on copies of the three images; a new tensor"""
-        self.x.copy_(x)
-        self.known.copy_(known)
-        self.mask.copy_(mask)
-        return self.run(first, first, recorder).clone()
+        return self.run_copies(x, (known, mask), first, recorder)
 
 
-class RePaint(DDPM):
+class RePaint(GridProcess):
     r"""RePaint / SDEdit over any unconditional noise-prediction network of the package (an IDDPM network's learned variance is not used:
     the reverse step's variance is beta), or an x0 / v network (`prediction=`).
 
@@ -132,6 +127,8 @@ class RePaint(DDPM):
 
     _chain_kind = _lib.CHAIN_REPAINT
     _runner_class = PaintChainRunner
+    _whole_chains = "RePaint runs whole chains: inpaint / edit / generate"
+    _image_noun = "image batch"
 
     def __init__(self, model: nn.Module, timesteps: int = 1000, sub_timesteps: int = 250, jump_length: int = 10, resamples: int = 10, start: float = 0.0001,
                  end: float = 0.02, alpha_bar: Optional[Tensor] = None, *, prediction: str = "eps", loss_weight: str = "uniform", snr_gamma: float = 5.0, threshold: str = "none", threshold_percentile: float = 0.995) -> None:
@@ -139,80 +136,37 @@ class RePaint(DDPM):
         for name, v in (("jump_length", jump_length), ("resamples", resamples)):
             if isinstance(v, bool) or int(v) != v or v < 1:
                 raise ValueError(f"{name} = {v!r}; an integer of at least 1")
-        if isinstance(sub_timesteps, bool) or int(sub_timesteps) != sub_timesteps or not 1 <= sub_timesteps <= timesteps:
-            raise ValueError(f"sub_timesteps = {sub_timesteps!r} outside 1..{timesteps}")
-        if alpha_bar is not None:
-            self._use_alpha_bar(alpha_bar)
-        self.sub_timesteps, self.jump_length, self.resamples = int(sub_timesteps), int(jump_length), int(resamples)
-        ab64 = self.alpha_bar.reshape(-1).to(torch.float64).cpu().numpy()
-        grid = solver_grid(ab64, self.sub_timesteps, "linear")
-        self.n_levels = len(grid) - 1
-        self.register_buffer("tau", torch.tensor(grid, dtype=torch.int64), persistent=False)
-        self._tau_host, self._ab64 = grid, ab64
+        self._set_grid(sub_timesteps, alpha_bar)
+        self.jump_length, self.resamples = int(jump_length), int(resamples)
         self._walk = repaint_levels(self.n_levels, self.jump_length, self.resamples)
         self._tables = self._make_tables(self._walk)
         self._plain_tables = self._make_tables(list(range(self.n_levels, -1, -1)))  # SDEdit's: loop index = level
         self.n_rows = self._tables[0]
 
-    from_process = classmethod(_from_process)
-
     def _make_tables(self, walk):
         full = self.n_levels == self.timesteps
-        rows, ttab = repaint_rows(self._ab64, self._tau_host, walk, (self._c1, self._c2, self._sigma) if full else None)
-        return len(ttab) - 1, [tuple(float(np.float32(v)) for v in r) for r in rows], ttab
-
-    def _chain_tables(self):
-        n, rows, ttab = self._tables
-        return n, list(rows), list(ttab)
-
-    # ------------------------------------------------------------------ arguments
-    def _image(self, x: Tensor, what: str) -> Tensor:
-        if not (isinstance(x, Tensor) and x.dim() == 4 and x.is_floating_point()):
-            raise ValueError(f"{what}: a floating-point image batch (B, C, H, W)")
-        return x.detach().to(device=self.beta.device, dtype=torch.float32).contiguous()
+        return fp32_tables(*repaint_rows(self._ab64, self._tau_host, walk, (self._c1, self._c2, self._sigma) if full else None))
 
     @staticmethod
     def _mask(mask: Optional[Tensor], like: Tensor) -> Tensor:
         """(B|1, C|1, H, W) with values in [0, 1] -> contiguous fp32 of `like`'s shape; None: nothing is known"""
-        if mask is None:
-            return torch.zeros_like(like)
-        m = torch.as_tensor(mask).detach().to(device=like.device, dtype=torch.float32)
-        B, Cc, H, W = like.shape
-        if m.dim() != 4 or m.shape[0] not in (1, B) or m.shape[1] not in (1, Cc) or tuple(m.shape[2:]) != (H, W):
-            raise ValueError(f"mask: shape {tuple(m.shape)} does not broadcast from (B|1, C|1, H, W) to {tuple(like.shape)}")
-        if not bool(((m >= 0) & (m <= 1)).all()):
-            raise ValueError("mask: values must lie in [0, 1] (1: known pixel, 0: generate)")
-        return m.expand(B, Cc, H, W).contiguous()
-
-    def _paint_runner(self, slot: str, shape, dev, tables=None) -> Optional[PaintChainRunner]:
-        if tables is None:
-            return self._buffered_runner(slot, shape, dev)
-        return self._buffered_runner(slot, shape, dev, spec=lambda: (_lib.CHAIN_REPAINT, tables), buf=slot + "_buf")
+        return check_mask(mask, tuple(like.shape), like.device, 0.0, binary=False)
 
     # ------------------------------------------------------------------ chains
     def _eager_chain(self, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None, history=None) -> Tensor:
-        """the host loop over dmme_repaint_step, in place on x: normals from dmme_randn at the offsets the captured chain's state walks
-        through, so the two agree bit for bit under the same seed"""
-        n, rows, ttab = tables if tables is not None else self._tables
-        first = n if first is None else int(first)
-        lib, numel = _lib.lib(), x.numel()
-        span = []  # (seed, offset) of the walk's normals, taken once the recorder has accepted the walk
-        tt = torch.tensor(ttab, dtype=torch.int64, device=x.device).unsqueeze(1)
-        z3 = torch.empty(STREAMS * numel, dtype=torch.float32, device=x.device)
+        """the host loop over dmme_repaint_step (`eager_chain`), in place on x"""
+        tables = tables if tables is not None else self._tables
 
-        def step(k, i):
-            eps = self._eps(x, tt[i]).detach().to(torch.float32).contiguous()
-            draws = _row_draws(rows[i])
-            if draws:
-                _lib.check(lib.dmme_randn(_lib.ptr(z3), z3.numel(), span[0], span[1] + k * STREAMS * (numel // 4), _lib.stream_ptr()), "dmme_randn")
-            _lib.check(lib.dmme_repaint_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(z3 if draws else None), _row_arg(rows[i]),
-                                             x.shape[0], x[0].numel(), eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_repaint_step")
+        def call(row, t, z):
+            eps = self._eps(x, t).detach().to(torch.float32).contiguous()
+            _lib.check(_lib.lib().dmme_repaint_step(_lib.ptr(x), _lib.ptr(eps), _lib.ptr(known), _lib.ptr(mask), _lib.ptr(z), _row_arg(row), x.shape[0], x[0].numel(),
+                                                    eps[0].numel() // x[0].numel(), _lib.stream_ptr()), "dmme_repaint_step")
 
-        return walk(x, first, first, step, history, lambda: span.extend(philox_reserve(x.device, STREAMS * numel * first)))
+        return eager_chain(x, _lib.CHAIN_REPAINT, tables, tables[0] if first is None else int(first), STREAMS, call, history)
 
     def _chain(self, slot: str, x: Tensor, known: Tensor, mask: Tensor, tables=None, first: Optional[int] = None, history=None) -> Tensor:
         first = (tables if tables is not None else self._tables)[0] if first is None else first
-        runner = self._paint_runner(slot, x.shape, x.device, tables)
+        runner = self._table_runner(slot, x.shape, x.device, tables)
         if runner is None:
             return self._eager_chain(x, known, mask, tables, first, history)
         return runner.paint(x, known, mask, first, history)
@@ -250,8 +204,3 @@ class RePaint(DDPM):
         """`inpaint` with nothing known: the walk from pure noise"""
         zeros = torch.zeros(tuple(img_size), dtype=torch.float32, device=self.beta.device)
         return self._chain("_runner", gaussian(img_size, device=zeros.device), zeros, zeros, history=history)
-
-    def sampling_step(self, *a, **kw):
-        raise NotImplementedError("RePaint runs whole chains: inpaint / edit / generate")
-
-    denoise_once = sampling_step
